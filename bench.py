@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — (photo, render) pairs/s of the 3D-FM GAN forward hot path on MI355X, with the upfirdn2d roofline.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, warm up, time K steps, optionally write the last timed
+step's outputs (--dump-outputs), print the line.  --full adds everything else, in the same process as before: the
+upfirdn2d / modulated-conv rooflines and the per-kernel breakdown, the labelled split-operand leg, pairs256 and cfg2,
+the training legs (child processes) and the CPU baseline — inside a total time budget (FMGAN_BENCH_FULL_BUDGET).
 
 N>1 under torch.distributed.run (RANK / WORLD_SIZE in the environment): this process is one of the N ranks.  N>1 started
 plainly: this process touches no GPU, starts the N ranks itself as children (one per GPU, rendezvous on 127.0.0.1) and
@@ -69,6 +74,15 @@ WORKLOADS = {
 # the lazy regularisers recur every 16 (R1) and 4 (path length) iterations: any 16 consecutive iterations hold exactly
 # one R1 step and four path-length steps, so a timed window of 16 IS the amortised cost of an iteration
 TRAINSTEP_WINDOW = 16
+# --full: seconds the whole run may take (the training legs are time-boxed against what is left of it, minus the time
+# kept for rebuilding the models and the CPU baseline after them); a leg that does not fit is reported as skipped
+FULL_BUDGET_S = float(os.environ.get('FMGAN_BENCH_FULL_BUDGET', '540'))
+FULL_TAIL_S = 90.0
+# --dump-outputs: an output larger than DUMP_WHOLE_BYTES is written as a fixed sample of DUMP_SAMPLE elements, drawn by
+# a seeded permutation of its flat indices (same arguments -> same inputs -> same sample positions)
+DUMP_WHOLE_BYTES = 48 << 20
+DUMP_SAMPLE = 1 << 23
+DUMP_SEED = 2024
 
 
 _T0 = time.time()
@@ -128,15 +142,31 @@ def build_models(size, device):
     return {k: m.to(device) for k, m in nets.items()}
 
 
+def immediate(m):
+    """m called with MIOpen's immediate-mode solution for its convolutions (cudnn.benchmark off for the call)."""
+    def call(x):
+        prev = torch.backends.cudnn.benchmark
+        torch.backends.cudnn.benchmark = False
+        try:
+            return m(x)
+        finally:
+            torch.backends.cudnn.benchmark = prev
+    return call
+
+
 def make_step(nets, batch, device, rank):
     from Util.network_util import Forward_Inference_3_Encoder
+    # The two ResNet encoders run on a side stream beside the pSp encoder, off the step's critical path: their
+    # convolutions take MIOpen's immediate-mode solution, which spares the measured find's kernel compilation (most of
+    # a cold first step).  The pSp encoder keeps the measured choice (cudnn.benchmark in main()).
+    e_tsr, e_w = immediate(nets['e_tsr']), immediate(nets['e_w'])
     gen = torch.Generator(device='cpu').manual_seed(1234 + rank)
     photo = (torch.rand(batch, 3, 256, 256, generator=gen) * 2 - 1).to(device)     # resident in HBM before timing
     render = (torch.rand(batch, 3, 256, 256, generator=gen) * 2 - 1).to(device)
 
     def forward(p, r):
         with torch.no_grad():
-            return Forward_Inference_3_Encoder(p, r, nets['e_tsr'], nets['e_w'], nets['e_wp'], nets['g'])
+            return Forward_Inference_3_Encoder(p, r, e_tsr, e_w, nets['e_wp'], nets['g'])
 
     def step():
         return forward(photo, render)
@@ -210,8 +240,14 @@ def warm_miopen_cache():
 
 def train_leg(name, steps, world, timeout_s):
     """Run `bench.py --workload <name>` as a child (same ranks, next rendezvous port) and return its JSON record, or
-    {'skipped': reason}.  Every rank calls this; rank 0's child prints the line."""
+    {'skipped': reason}.  Every rank calls this; rank 0's child prints the line.  The time box is the smaller of
+    timeout_s and what the --full budget leaves (the same on every rank); below a minute the leg is not started."""
     import subprocess
+    left = agree(FULL_BUDGET_S - FULL_TAIL_S - (time.time() - _T0), world, dist.ReduceOp.MIN)
+    if left < 60:
+        return {'skipped': f'{name}: not started, {max(left, 0):.0f} s left of the --full budget '
+                           f'(FMGAN_BENCH_FULL_BUDGET={FULL_BUDGET_S:.0f} s)'}
+    timeout_s = min(timeout_s, left)
     env = dict(os.environ)
     if world > 1:
         env['MASTER_PORT'] = str(int(env.get('MASTER_PORT', '29500')) + {'train256': 7, 'trainstep256': 13, 'trainstep1024': 19}.get(name, 23))
@@ -222,7 +258,8 @@ def train_leg(name, steps, world, timeout_s):
     try:
         pr = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=None, text=True, timeout=timeout_s)
     except subprocess.TimeoutExpired:
-        return {'skipped': f'{name}: not finished within {timeout_s:.0f} s (MIOpen compiling backward kernels on a cold cache)'}
+        return {'skipped': f'{name}: not finished within its time box of {timeout_s:.0f} s (MIOpen compiling backward '
+                           f'kernels on a cold cache)'}
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith('{')]
     if pr.returncode != 0 or not lines:
         return {'skipped': f'{name}: child exited with code {pr.returncode}' if int(os.environ.get('RANK', '0')) == 0 else 'n/a'}
@@ -239,7 +276,19 @@ def dist_info(world):
     return {'backend': None, 'ranks': 1, 'launcher': None}
 
 
-def timed(step, steps, warmup, world):
+def agree(x, world, op):
+    """The same float on every rank (MAX / MIN over ranks); x itself with one rank."""
+    if world > 1:
+        dev = 'cuda' if dist.get_backend() == 'nccl' else 'cpu'
+        t = torch.tensor([x], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=op)
+        x = t.item()
+    return x
+
+
+def timed(step, steps, warmup, world, keep_last=None):
+    """Wall time of `steps` calls of step() after `warmup` untimed ones (MAX over ranks).  keep_last (a list) receives
+    what the last timed call returned; every earlier result is dropped at once, as when nothing is kept."""
     for _ in range(warmup):
         step()
     gpu = torch.cuda.is_available()
@@ -248,19 +297,32 @@ def timed(step, steps, warmup, world):
     if gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        step()
+    for i in range(steps):
+        if keep_last is not None and i == steps - 1:
+            keep_last.append(step())
+        else:
+            step()
     if gpu:
         torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    dt = time.perf_counter() - t0
-    if world > 1:
-        dev = 'cuda' if dist.get_backend() == 'nccl' else 'cpu'
-        t = torch.tensor([dt], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = t.item()
-    return dt
+    return agree(time.perf_counter() - t0, world, dist.ReduceOp.MAX)
+
+
+def dump_outputs(dirname, outputs):
+    """Write each output as <dirname>/<name>.npy in float32: whole when it is at most DUMP_WHOLE_BYTES, else the fixed
+    seeded sample of DUMP_SAMPLE elements of its flattened values as <name>_sample.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach().float()
+        if t.numel() * 4 > DUMP_WHOLE_BYTES:
+            g = torch.Generator(device='cpu').manual_seed(DUMP_SEED)
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], f'{name}_sample'
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        log(f'wrote {name}.npy {list(a.shape)} float32')
 
 
 def committed_traffic():
@@ -469,14 +531,22 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--workload', default='pairs1024', choices=sorted(WORKLOADS))
     ap.add_argument('--batch', type=int, default=0, help='pairs per GPU (default: the workload\'s)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline (rooflines, '
+                    'per-kernel breakdown, split-operand leg, pairs256, cfg2, training legs, CPU baseline)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step as DIR/<name>.npy '
+                    '(float32; a fixed seeded sample of an output above 48 MiB)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: no pairs256, cfg2 or training legs')
     ap.add_argument('--graph', action='store_true', help='also time a HIP-graph replay of the forward and report it as '
                     'value (measured: no gain at these sizes, the step is GPU-bound)')
-    ap.add_argument('--no-train', action='store_true', help='skip the training legs (train256, trainstep256) of the default run')
+    ap.add_argument('--no-train', action='store_true', help='with --full: no training legs')
     ap.add_argument('--plumbing', action='store_true', help='no GPU work: a stand-in step through the same rendezvous, '
                     'sharding, barrier + MAX-over-ranks timing and JSON contract (CPU/gloo test of the N>1 launch path)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and (args.plumbing or args.workload.startswith('train')):
+        ap.error('--dump-outputs writes the image of a forward workload (pairs1024, pairs256)')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
     if args.plumbing:
@@ -504,6 +574,7 @@ def main():
     batch = args.batch or wl['batch']
     log(f'building models for {args.workload}')
     nets = build_models(wl['size'], device)
+    log('models on the device')
     if args.workload.startswith('train'):
         if args.workload == 'train256':
             step, inputs = make_train_step(nets, batch, device, rank, world)
@@ -552,22 +623,27 @@ def main():
         step()
         torch.cuda.synchronize()
         log(f'warm-up step {i + 1}/{args.warmup} done')
-    _native.set_observer(timer)
-    dt_eager = timed(step, args.steps, 0, world)      # eager launches; the headline kernel is bracketed by HIP events
+    last = [] if args.dump_outputs else None
+    if args.full:
+        _native.set_observer(timer)       # the headline kernel is bracketed by HIP events (roofline)
+    dt_eager = timed(step, args.steps, 0, world, None if args.graph else last)      # eager launches
     _native.set_observer(None)
     dt = dt_eager
     graphed = None
     if args.graph:
         from Util.hip_graph import GraphedForward
         graphed = GraphedForward(step.forward, inputs)
-        dt = timed(lambda: graphed(*inputs), args.steps, 2, world)   # the same forward, replayed as one HIP graph
+        dt = timed(lambda: graphed(*inputs), args.steps, 2, world, last)   # the same forward, replayed as one HIP graph
     pairs_per_s = world * batch * args.steps / dt
     log(f'{args.workload}: {pairs_per_s:.1f} pairs/s')
+    if last and rank == 0:
+        dump_outputs(args.dump_outputs, {'image': last[0]})
+    del last
     # LABELLED variant, never `value`: the same forward with the modulated convs' fp32 contraction emulated on the bf16
     # matrix pipe (operands split into three bf16 pieces, six MFMAs per product, fp32 accumulation: fp32 accuracy, held to
     # the fp32 path's gates by tests/test_hip_modconv_bf16.py).  Timed with the same barriers right after the headline.
     x3 = None
-    if args.workload == 'pairs1024' and not args.graph:
+    if args.full and args.workload == 'pairs1024' and not args.graph:
         def step_x3():
             with _native.modconv_precision('bf16x3'):
                 return step()
@@ -584,7 +660,8 @@ def main():
         'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
         'config': {'workload': f"{args.workload}: {wl['desc']}", 'pairs_per_gpu': batch, 'global_pairs': batch * world,
                    'image_size': wl['size'], 'parallelism': f'replicas x{world} (batch-sharded, no collective)',
-                   'launch': 'eager' if graphed is None else 'hip-graph replay of the whole forward', **dist_info(world)},
+                   'launch': 'eager' if graphed is None else 'hip-graph replay of the whole forward', **dist_info(world),
+                   'full': args.full},
         'eager': {'value': world * batch * args.steps / dt_eager, 'ms_per_step': 1e3 * dt_eager / args.steps},
     }
     if x3 is not None:
@@ -592,7 +669,7 @@ def main():
 
     # roofline of the dominant HBM kernel (upfirdn2d headline call), algorithmic bytes = 4*(in + out)
     summ = timer.summary()
-    if (('upfirdn2d', head) in summ):
+    if args.full and ('upfirdn2d', head) in summ:
         ms, n = summ[('upfirdn2d', head)]
         # algorithmic bytes of the blur: input + output (the fused noise row adds 1/C of the output and is not counted)
         bytes_alg = 4.0 * head[0] * (head[1] * head[2] + head[3] * head[4])
@@ -637,40 +714,41 @@ def main():
                                         'avg_launch_ms': ms_op}
         del xin
 
-    # per-kernel breakdown (separate, fully instrumented pass; not part of `value`)
-    full = LaunchTimer(lambda name, info: True)
-    _native.set_observer(full)
-    step()
-    torch.cuda.synchronize()
-    _native.set_observer(None)
-    fs = full.summary()
-    tot = {}
-    for (name, info), (ms, n) in fs.items():
-        tot[name] = tot.get(name, 0.0) + ms * n
-    conv = [(info, ms) for (name, info), (ms, n) in fs.items() if name == 'modconv2d']
-    wino = [(info, ms) for (name, info), (ms, n) in fs.items() if name == 'modconv2d_winograd']
-    if conv:
-        def flops(i):
-            b, cin, cout, h, w, mode = i
-            return 2.0 * 9 * cin * cout * b * h * w
-        best = max(conv, key=lambda t: flops(t[0]))
-        tf = flops(best[0]) / (best[1] * 1e-3) / 1e12
-        # all layers: ALGORITHMIC flops of the direct form over the time of whatever form ran them — the layers
-        # served in Winograd form (16 instead of 36 products per 2x2 tile) can therefore read above the matrix peak
-        tot_tf = sum(flops(i) for i, _ in conv + wino) / (sum(ms for _, ms in conv + wino) * 1e-3) / 1e12
-        out['roofline_modconv'] = {'bound': 'mfma', 'kernel': f'modconv_mfma_f32 {best[0]} (largest layer on the direct MFMA kernel)',
-                                   'achieved': tf, 'peak': FP32_MFMA_PEAK_TF, 'unit': 'TFLOP/s', 'frac': tf / FP32_MFMA_PEAK_TF,
-                                   'all_layers_achieved': tot_tf,
-                                   'direct_layers_achieved': sum(flops(i) for i, _ in conv) / (sum(ms for _, ms in conv) * 1e-3) / 1e12}
-        if wino:
-            out['roofline_modconv']['winograd_layers'] = {
-                'count': len(wino), 'ms': round(sum(ms for _, ms in wino), 3),
-                'algorithmic_tflops': sum(flops(i) for i, _ in wino) / (sum(ms for _, ms in wino) * 1e-3) / 1e12,
-                'what': 'plain 3x3 layers served as F(2x2,3x3): own transform kernels + 16 batched fp32 GEMMs (hipBLASLt); '
-                        'algorithmic flops of the direct form / time'}
-    out['ms_by_op_instrumented'] = {k: round(v, 3) for k, v in sorted(tot.items())}
+    if args.full:
+        # per-kernel breakdown (separate, fully instrumented pass; not part of `value`)
+        full = LaunchTimer(lambda name, info: True)
+        _native.set_observer(full)
+        step()
+        torch.cuda.synchronize()
+        _native.set_observer(None)
+        fs = full.summary()
+        tot = {}
+        for (name, info), (ms, n) in fs.items():
+            tot[name] = tot.get(name, 0.0) + ms * n
+        conv = [(info, ms) for (name, info), (ms, n) in fs.items() if name == 'modconv2d']
+        wino = [(info, ms) for (name, info), (ms, n) in fs.items() if name == 'modconv2d_winograd']
+        if conv:
+            def flops(i):
+                b, cin, cout, h, w, mode = i
+                return 2.0 * 9 * cin * cout * b * h * w
+            best = max(conv, key=lambda t: flops(t[0]))
+            tf = flops(best[0]) / (best[1] * 1e-3) / 1e12
+            # all layers: ALGORITHMIC flops of the direct form over the time of whatever form ran them — the layers
+            # served in Winograd form (16 instead of 36 products per 2x2 tile) can therefore read above the matrix peak
+            tot_tf = sum(flops(i) for i, _ in conv + wino) / (sum(ms for _, ms in conv + wino) * 1e-3) / 1e12
+            out['roofline_modconv'] = {'bound': 'mfma', 'kernel': f'modconv_mfma_f32 {best[0]} (largest layer on the direct MFMA kernel)',
+                                       'achieved': tf, 'peak': FP32_MFMA_PEAK_TF, 'unit': 'TFLOP/s', 'frac': tf / FP32_MFMA_PEAK_TF,
+                                       'all_layers_achieved': tot_tf,
+                                       'direct_layers_achieved': sum(flops(i) for i, _ in conv) / (sum(ms for _, ms in conv) * 1e-3) / 1e12}
+            if wino:
+                out['roofline_modconv']['winograd_layers'] = {
+                    'count': len(wino), 'ms': round(sum(ms for _, ms in wino), 3),
+                    'algorithmic_tflops': sum(flops(i) for i, _ in wino) / (sum(ms for _, ms in wino) * 1e-3) / 1e12,
+                    'what': 'plain 3x3 layers served as F(2x2,3x3): own transform kernels + 16 batched fp32 GEMMs (hipBLASLt); '
+                            'algorithmic flops of the direct form / time'}
+        out['ms_by_op_instrumented'] = {k: round(v, 3) for k, v in sorted(tot.items())}
 
-    if not args.no_secondary and args.workload == 'pairs1024':
+    if args.full and not args.no_secondary and args.workload == 'pairs1024':
         del nets, step, inputs
         torch.cuda.empty_cache()
         wl2 = WORKLOADS['pairs256']
@@ -723,7 +801,7 @@ def main():
         _, inputs = make_step(nets, 1, device, rank)
 
     del graphed
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log('cpu baseline (bounded sample of the CPU path)')
         out['cpu_baseline'] = cpu_baseline(nets, inputs, wl['size'])
         log('cpu baseline done')

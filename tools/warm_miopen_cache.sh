@@ -8,7 +8,8 @@ OUT=$REPO/gpurun_out/miopen_cache
 mkdir -p $OUT/db $OUT/cache
 export MIOPEN_USER_DB_PATH=$OUT/db MIOPEN_CUSTOM_CACHE_DIR=$OUT/cache
 cd $REPO
-python bench.py --steps 2 --warmup 1 --no-cpu-baseline > gpurun_out/warm_bench.json 2> gpurun_out/warm_bench.err || true
-tail -3 gpurun_out/warm_bench.err
+LOG=$(dirname $OUT)
+python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $LOG/warm_bench.json 2> $LOG/warm_bench.err || true
+tail -3 $LOG/warm_bench.err
 du -sh $OUT $OUT/db $OUT/cache
 ls -la $OUT/db $OUT/cache | head -20
