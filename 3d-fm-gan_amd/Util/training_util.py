@@ -1,16 +1,21 @@
 """Adversarial losses and regularisers of the training step (reference: Util/training_util.py:24-58, 103-113).
 
 The pieces the training iteration needs: the non-saturating logistic GAN pair, R1 on real images, the path-length
-regulariser, the L1 reconstruction loss, and the wrappers of the perceptual (LPIPS) and identity (ArcFace) terms
-(Util/training_util.py:115-127, 131-205).  R1 and path length differentiate *through* a first derivative, i.e. they
-exercise the double-backward of the HIP ops (upfirdn2d, fused_bias_act) and of the modulated conv.  The landmark /
-face-region terms need `face_alignment`, a third-party package that is absent offline; they stay out.
+regulariser, the L1 reconstruction loss, the wrappers of the perceptual (LPIPS) and identity (ArcFace) terms
+(Util/training_util.py:115-127, 131-205), and the face-regional loss of the dual-supervision iterations
+(Util/training_util.py:228-256; one HIP kernel per direction, op/face_region.py).  R1 and path length differentiate
+*through* a first derivative, i.e. they exercise the double-backward of the HIP ops (upfirdn2d, fused_bias_act) and of
+the modulated conv.  Only the landmark heat-map term is left out: it needs `face_alignment`, a third-party package that
+is absent offline.
 """
 import math
 
 import torch
 from torch import autograd
 from torch.nn import functional as F
+
+from op import _native
+from op.face_region import face_region_loss
 
 
 def d_logistic_loss(real_pred, fake_pred):
@@ -83,6 +88,22 @@ def Face_Identity_Loss(output_tensor, target_tensor, face_rec_model, loss_type='
     if loss_type == 'MSE':
         return F.mse_loss(output_feature, target_feature)
     return torch.mean(1 - F.cosine_similarity(output_feature, target_feature))
+
+
+def Get_Render_Mask(render_img):
+    """Float 0/1 mask [N, H, W] of where the render shows the face: mean over channels > -1 (training_util.py:228-238).
+    Computed by the HIP kernel on the render's device and returned THERE; the reference returns a CPU FloatTensor, so its
+    callers' `.to(device)` keeps working (a no-op now).  The decision is bit-identical to torch's
+    `render_img.mean(1) > -1` on the same GPU."""
+    return _native.render_mask(render_img)
+
+
+def Face_Regional_Loss(r_img, g_img, device=None):
+    """L2 loss on the face region of the render (training_util.py:240-256): mean((r*m - g*m)^2) over [N, C, H, W], m from
+    Get_Render_Mask(r_img).  0-dim tensor, differentiable w.r.t. g_img (renders are data).  `device` is kept for the
+    reference's signature; the term runs where the tensors are.  Render and image must have the same shape (ValueError
+    otherwise: the reference broadcasts there, e.g. 256^2 renders against 1024^2 outputs)."""
+    return face_region_loss(r_img, g_img)
 
 
 def requires_grad(model, flag=True):

@@ -57,6 +57,10 @@ def lib():
     _sig(L.fmgan_fused_bias_act_bwd_f32, [vp] * 4 + [ll, i, f, f, vp])
     _sig(L.fmgan_prelu_backward_blocks, [ll, i])
     _sig(L.fmgan_prelu_backward_f32, [vp] * 5 + [ll, i, vp])
+    _sig(L.fmgan_face_region_blocks, [i, ll])
+    _sig(L.fmgan_face_region_loss_f32, [vp] * 3 + [i, i, ll, vp])
+    _sig(L.fmgan_face_region_backward_f32, [vp] * 4 + [i, i, ll, vp])
+    _sig(L.fmgan_render_mask_f32, [vp] * 2 + [i, i, ll, vp])
     _sig(L.fmgan_modconv_demod_f32, [vp] * 3 + [i] * 4 + [f, f, vp])
     _sig(L.fmgan_modconv_wsq_f32, [vp] * 2 + [i] * 3 + [vp])
     _sig(L.fmgan_modconv_demod_wsq_f32, [vp] * 3 + [i] * 3 + [f, f, vp])
@@ -338,6 +342,65 @@ def prelu_backward(x, grad, slope):
         return None
     check(st, 'prelu_backward')
     return gx, partial.sum(0)
+
+
+def _face_region_shape(r, g):
+    """(r, g) contiguous, (B, C, H*W) — after the checks shared by the three face-region entry points: shapes first
+    (ValueError naming both, before anything touches a device), then device and dtype (RuntimeError, no fallback)."""
+    if r.ndim != 4 or (g is not None and tuple(r.shape) != tuple(g.shape)):
+        got = f'render {tuple(r.shape)}' + ('' if g is None else f' and image {tuple(g.shape)}')
+        raise ValueError(f'face_region: {got}: expected [N, C, H, W] tensors of one shape (the face-regional loss '
+                         f'compares the render with the generated image pixel by pixel; renders are not resampled)')
+    for t, name in ((r, 'render'), (g, 'image')):
+        if t is not None:
+            require_gpu(t, name)
+            fp(t)
+    r = r.contiguous()
+    g = g.contiguous() if g is not None else None
+    b, c, h, w = r.shape
+    return r, g, (b, c, h * w)
+
+
+def face_region_loss(r, g):
+    """Per-sample sums S[b] = sum_{c,y,x} m * (r - g)^2 with m = mean_c(r) > -1 (Util/training_util.py:228-256):
+    r (render), g (generated image) [B, C, H, W] f32 of one shape -> S [B] f32.  Fixed-order per-block partials from
+    the kernel, summed here: bit-reproducible.  loss = S.sum() / numel; face_diff_score = S / (C*H*W)."""
+    r, g, (b, c, hw) = _face_region_shape(r, g)
+    with on_device(r) as stream:
+        partial = torch.empty((b, lib().fmgan_face_region_blocks(b, hw)), dtype=torch.float32, device=r.device)
+        tok = _observer.begin('face_region', (b, c, hw, 0))
+        check(lib().fmgan_face_region_loss_f32(fp(r), fp(g), fp(partial), b, c, hw, stream), 'face_region_loss')
+        _observer.end(tok)
+    return partial.sum(1)
+
+
+def face_region_loss_backward(r, g, grad_loss):
+    """Gradient of mean(m * (r - g)^2) w.r.t. g: grad_loss * 2/numel * m * (g - r), exactly 0 outside the mask.
+    grad_loss: the upstream gradient as a one-element f32 tensor ON THE DEVICE, read by the kernel (no .item())."""
+    r, g, (b, c, hw) = _face_region_shape(r, g)
+    gl = grad_loss.reshape(-1)
+    if gl.numel() != 1:
+        raise ValueError(f'face_region_loss_backward: grad_loss must hold one element, got {tuple(grad_loss.shape)}')
+    gl = gl.to(device=r.device, dtype=torch.float32).contiguous()
+    dg = torch.empty_like(g)
+    with on_device(r) as stream:
+        tok = _observer.begin('face_region', (b, c, hw, 1))
+        check(lib().fmgan_face_region_backward_f32(fp(r), fp(g), fp(gl), fp(dg), b, c, hw, stream),
+              'face_region_loss_backward')
+        _observer.end(tok)
+    return dg
+
+
+def render_mask(r):
+    """Get_Render_Mask (Util/training_util.py:228-238) on the GPU: r [N, C, H, W] f32 -> float 0/1 mask [N, H, W]
+    (mean_c(r) > -1, the same decision as torch's r.mean(1) > -1 on the same device)."""
+    r, _, (b, c, hw) = _face_region_shape(r, None)
+    mask = torch.empty((b, r.shape[2], r.shape[3]), dtype=torch.float32, device=r.device)
+    with on_device(r) as stream:
+        tok = _observer.begin('face_region', (b, c, hw, 2))
+        check(lib().fmgan_render_mask_f32(fp(r), fp(mask), b, c, hw, stream), 'render_mask')
+        _observer.end(tok)
+    return mask
 
 
 def modconv_demod(weight, style, scale, eps=1e-8, wsq=None):

@@ -6,9 +6,12 @@ drives its GPUs through single-process nn.DataParallel.  This module re-states t
 
     D_Loss_BackProp   :448-477   logistic D loss on (reference image, generated image), G/encoders frozen
     D_Reg_BackProp    :479-493   R1 on the reference images every d_reg_every iterations (second order)
-    G_Loss_BackProp   :495-558   non-saturating G loss + weighted reconstruction losses, G + encoders trained
+    G_Loss_BackProp   :495-558   non-saturating G loss + weighted reconstruction losses (+ the face-regional loss
+                                 on dual-supervision batches), G + encoders trained
     G_Reg_BackProp    :561-596   path-length regulariser every g_reg_every iterations on batch / shrink (second order)
     accumulate        :195-200   EMA of G into g_ema            Optimizer_Initilization :399-444
+    Trainer.train_iteration :777-822   the schedule of train(): one dual-supervision iteration in every ds_freq, one
+                                 extreme-pose iteration in every ex_ds_freq of those, D_edit (if given) as their D
 
 What is different, on purpose:
   * gradients are averaged over ranks (RCCL all-reduce: DDP buckets, or Miscellaneous.distributed.gather_grad) instead
@@ -19,10 +22,15 @@ What is different, on purpose:
   * the LPIPS and ArcFace terms (:529,:535) are computed when `lpips_model` / `face_rec_model` are passed, with the
     reference's weights and arithmetic; their pretrained weights are not available offline, so
     Module_Fix_Setup builds the two networks (lpips/, Util/arcface_pytorch/) with their own initialisation — the cost of
-    the iteration is that of the reference's, the loss VALUES are not.  The landmark heat-map and face-region terms
-    (:538-545) need the third-party `face_alignment` package (absent; both weights default to 0 in the reference's
-    reconstruction setting, train_3_encoder_hyperparams.py:66-68) and are not provided; `extra_losses` takes any
-    further (name, weight, fn(output, reference) -> scalar) terms.
+    the iteration is that of the reference's, the loss VALUES are not.  The face-regional term (:544-547, weights
+    rec/ds/ep = 0/20/100, train_3_encoder_hyperparams.py:69-71) is plain tensor arithmetic and runs on its own HIP
+    kernel (op/face_region.py); it needs renders of the output's size, so at 1024^2 outputs from 256^2 renders a
+    dual-supervision iteration raises ValueError (the reference broadcasts there; resampling is not provided).  The
+    landmark heat-map term (:538-542) needs the third-party `face_alignment` package (absent; its weight is 0 in the
+    reference's setting, train_3_encoder_hyperparams.py:66-68) and is not provided; `extra_losses` takes any further
+    (name, weight, fn(output, reference) -> scalar) terms.
+  * the schedule is opt-in: Trainer.step(...) without flags is a reconstruction iteration, exactly as before;
+    Trainer.train_iteration(...) draws the flags and the batch as train() does.
 """
 import types
 
@@ -30,10 +38,11 @@ import numpy as np
 import torch
 from torch import nn, optim
 
+import dataset
 from Miscellaneous import distributed as D_
 from Util.network_util import Forward_Inference_3_Encoder, MODULATION_ENCODING
-from Util.training_util import (Face_Identity_Loss, L1_Loss, LPIPS_Loss, accumulate, d_logistic_loss, d_r1_loss,
-                                g_nonsaturating_loss, requires_grad)
+from Util.training_util import (Face_Identity_Loss, Face_Regional_Loss, L1_Loss, LPIPS_Loss, accumulate,
+                                d_logistic_loss, d_r1_loss, g_nonsaturating_loss, requires_grad)
 
 
 def default_args(**over):
@@ -43,7 +52,8 @@ def default_args(**over):
         tsr_train=True, w_train=True, w_plus_train=True,
         lr=0.001, rec_batch=16, r1=10, d_reg_every=16, use_g_reg=True, g_reg_every=4, generator_path_reg_weight=2,
         path_reg_batch_shrink=2, l1_loss_lambda=3, lpips_loss_lambda=3, ep_lpips_l1_weight_shrink=10,
-        face_id_loss_lambda=30, face_id_loss_type='MSE', grad_sync='ddp')
+        face_id_loss_lambda=30, face_id_loss_type='MSE', grad_sync='ddp',
+        ds_freq=2, ex_ds_freq=3, rec_face_reg_loss_lambda=0, ds_face_reg_loss_lambda=20, ep_face_reg_loss_lambda=100)
     for k, v in over.items():
         setattr(a, k, v)
     return a
@@ -157,11 +167,22 @@ def _trained(args, G, E_Tsr, E_W, E_W_Plus):
     return nets
 
 
+def face_reg_lambda(args, ds_flag, extreme_ds_flag):
+    """Weight of the face-regional term for this batch (train_3_encoder.py:521-526)."""
+    if not ds_flag:
+        return args.rec_face_reg_loss_lambda
+    if not extreme_ds_flag:
+        return args.ds_face_reg_loss_lambda
+    return args.ep_face_reg_loss_lambda
+
+
 def G_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, D, g_input, r_input, g_ref, args, loss_dict, g_enc_optim,
                     lpips_model=None, face_rec_model=None, fa_model=None, iter_idx=0, extreme_ds_flag=False,
                     ds_flag=False, extra_losses=()):
     """Update G and the encoders on the adversarial + reconstruction losses (train_3_encoder.py:495-558; the
-    reference's argument order).  lpips_model / face_rec_model = None leaves that term out."""
+    reference's argument order).  lpips_model / face_rec_model = None leaves that term out.  The face-regional term
+    is added last, with face_reg_lambda(args, ds_flag, extreme_ds_flag); at weight 0 (reconstruction batches) it is not
+    computed and loss_dict['face_reg'] is a zero, which is what the reference's 0 * term contributes."""
     requires_grad(G, True)
     requires_grad(E_Tsr, args.tsr_train)
     requires_grad(E_W, args.w_train)
@@ -187,6 +208,12 @@ def G_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, D, g_input, r_input, g_ref, args, l
     for name, weight, fn in extra_losses:
         loss_dict[name] = weight * fn(g_output, g_ref)
         total_loss = total_loss + loss_dict[name]
+    face_reg_loss_lambda = face_reg_lambda(args, ds_flag, extreme_ds_flag)
+    if face_reg_loss_lambda:
+        loss_dict['face_reg'] = face_reg_loss_lambda * Face_Regional_Loss(r_input, g_output)
+        total_loss = total_loss + loss_dict['face_reg']
+    else:
+        loss_dict['face_reg'] = torch.zeros((), device=g_output.device)
     nets = _trained(args, G, E_Tsr, E_W, E_W_Plus)
     for n in nets:
         n.zero_grad()
@@ -237,8 +264,9 @@ def G_Reg_BackProp(G, E_Tsr, E_W, E_W_Plus, g_input, r_input, args, mean_path_le
 class Trainer:
     """State of `train()` (train_3_encoder.py:756-828) for one rank: wrapped networks, g_ema, optimisers, counters.
 
-    nets: dict with G, E_Tsr, E_W, E_W_Plus, D (bare modules on this rank's device; BatchNorm of the encoders in eval
-    mode).  grad_sync: 'ddp' wraps them in DistributedDataParallel, 'flat' in Replica + gather_grad."""
+    nets: dict with G, E_Tsr, E_W, E_W_Plus, D and optionally D_edit, the editing discriminator of the
+    dual-supervision iterations (bare modules on this rank's device; BatchNorm of the encoders in eval mode, SURVEY
+    F13).  grad_sync: 'ddp' wraps them in DistributedDataParallel, 'flat' in Replica + gather_grad."""
 
     def __init__(self, nets, args, device=None, g_ema=None, lpips_model=None, face_rec_model=None):
         import copy
@@ -254,25 +282,63 @@ class Trainer:
         unused = {'G': True, 'E_W_Plus': args.w_plus_sliced_layer is not None}
         self.nets = {k: D_.data_parallel(m, device, overlap=ddp, find_unused_parameters=unused.get(k, False))
                      for k, m in nets.items()}
-        self.g_enc_optim, self.d_optim, _ = Optimizer_Initilization(
-            args, self.bare['G'], self.bare['E_Tsr'], self.bare['E_W'], self.bare['E_W_Plus'], self.bare['D'])
+        self.g_enc_optim, self.d_optim, self.d_edit_optim = Optimizer_Initilization(
+            args, self.bare['G'], self.bare['E_Tsr'], self.bare['E_W'], self.bare['E_W_Plus'], self.bare['D'],
+            self.bare.get('D_edit'))
+        self.device = device
         self.accum = 0.5 ** (32 / (10 * 1000))
         self.mean_path_length = 0
         self.iter_idx = 0
+        self.ds_count = 0
         self.loss_dict = {'r1': torch.zeros((), device=device), 'g_reg': torch.zeros((), device=device)}
 
-    def step(self, g_input, r_input, g_ref, ppl_choice=None):
-        """One iteration: D, (R1), G, (path length), EMA — the order of train_3_encoder.py:801-822."""
+    def ds_flags(self):
+        """(ds_flag, extreme_ds_flag) of the coming iteration, self.iter_idx (train_3_encoder.py:780-786): every
+        ds_freq-th iteration is a dual-supervision one, and every ex_ds_freq-th of those uses the extreme-pose batch;
+        ds_count counts the dual-supervision iterations."""
+        a = self.args
+        if self.iter_idx % a.ds_freq != a.ds_freq - 1:
+            return False, False
+        extreme_ds_flag = self.ds_count % a.ex_ds_freq == a.ex_ds_freq - 1
+        self.ds_count += 1
+        return True, extreme_ds_flag
+
+    def discriminator(self, ds_flag=False):
+        """(wrapped network, optimiser) on the D side of an iteration: D_edit on dual-supervision batches when it was
+        given (train_3_encoder.py:788-796), D otherwise."""
+        if ds_flag and 'D_edit' in self.nets:
+            return self.nets['D_edit'], self.d_edit_optim
+        return self.nets['D'], self.d_optim
+
+    def step(self, g_input, r_input, g_ref, ppl_choice=None, ds_flag=False, extreme_ds_flag=False):
+        """One iteration: D, (R1), G, (path length), EMA — the order of train_3_encoder.py:801-822.  Without flags a
+        reconstruction iteration.  ds_flag: a dual-supervision batch — D_edit (when given) and its optimiser take D's
+        place in the D loss, R1 and the G step's adversarial term (:788-796), and the G step adds the face-regional
+        term; extreme_ds_flag: an extreme-pose batch (L1 shrunk, face-id reference = input, face-regional weight 100)."""
         a, n, ld = self.args, self.nets, self.loss_dict
-        G, E_Tsr, E_W, E_W_Plus, Dn = n['G'], n['E_Tsr'], n['E_W'], n['E_W_Plus'], n['D']
-        D_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, Dn, g_input, r_input, g_ref, a, ld, self.d_optim)
+        G, E_Tsr, E_W, E_W_Plus = n['G'], n['E_Tsr'], n['E_W'], n['E_W_Plus']
+        Dn, d_optim = self.discriminator(ds_flag)
+        D_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, Dn, g_input, r_input, g_ref, a, ld, d_optim)
         if self.iter_idx % a.d_reg_every == 0:
-            ld['r1'] = D_Reg_BackProp(g_ref, Dn, a, self.d_optim)
+            ld['r1'] = D_Reg_BackProp(g_ref, Dn, a, d_optim)
         G_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, Dn, g_input, r_input, g_ref, a, ld, self.g_enc_optim,
-                        self.lpips_model, self.face_rec_model, None, self.iter_idx)
+                        self.lpips_model, self.face_rec_model, None, self.iter_idx, extreme_ds_flag, ds_flag)
         if self.iter_idx % a.g_reg_every == 0 and a.use_g_reg:
             ld['g_reg'], _, self.mean_path_length = G_Reg_BackProp(G, E_Tsr, E_W, E_W_Plus, g_input, r_input, a,
                                                                    self.mean_path_length, self.g_enc_optim, ppl_choice)
         accumulate(self.g_ema, self.bare['G'], self.accum)
         self.iter_idx += 1
         return ld
+
+    def train_iteration(self, rec_loader, ds_loader, ep_loader=None, ppl_choice=None):
+        """One iteration of train()'s schedule (train_3_encoder.py:780-812): the flags, the batch from the loader they
+        select (dataset.Data_Loading: reconstruction, partner-paired, or partner-paired extreme pose at half the batch),
+        then step().  Loaders are iterators of (photo, render) batches.  Returns (loss_dict, ds_flag, extreme_ds_flag)."""
+        ds_flag, extreme_ds_flag = self.ds_flags()
+        if extreme_ds_flag and ep_loader is None:
+            raise ValueError('train_iteration: an extreme-pose iteration is due (ex_ds_freq) and ep_loader is None')
+        device = self.device if self.device is not None else next(self.bare['G'].parameters()).device
+        g_input, r_input, g_ref = dataset.Data_Loading(rec_loader, ds_loader, ds_flag, device, extreme_loader=ep_loader,
+                                                       extreme_ds_flag=extreme_ds_flag)
+        ld = self.step(g_input, r_input, g_ref, ppl_choice, ds_flag, extreme_ds_flag)
+        return ld, ds_flag, extreme_ds_flag

@@ -185,6 +185,27 @@ int fmgan_prelu_backward_f32(const float *x, const float *grad, const float *slo
                              float *partial, long long rows, int channels, void *stream);
 
 /*
+ * Face-regional loss of the dual-supervision G step (Util/training_util.py:228-256, Get_Render_Mask +
+ * Face_Regional_Loss) on a render r and a generated image g, both [batch, channels, hw] contiguous f32 (hw = H*W):
+ *   m[b,p] = (sum_c r[b,c,p]) * (1/C) > -1, with the serial fp32 channel sum and the float factor of ATen's
+ *            r.mean(1) (bit-identical to it for channels <= 4)
+ *   fmgan_face_region_loss_f32     : partial[b, blk] = sum over block blk's pixels of sample b of m * (r - g)^2;
+ *                                    partial [batch, fmgan_face_region_blocks(batch, hw)], fixed association (no atomics):
+ *                                    the caller sums each row (S[b]); loss = sum_b S[b] / (batch*channels*hw)
+ *   fmgan_face_region_backward_f32 : grad_g = grad_loss[0] * 2/(batch*channels*hw) * m * (g - r), 0 where m = 0;
+ *                                    grad_loss is a DEVICE scalar (no host synchronisation)
+ *   fmgan_render_mask_f32          : mask [batch, hw] = m as 0.f / 1.f
+ * 16-byte loads when hw % 4 == 0 and the pointers are 16-byte aligned, otherwise a scalar form with the same arithmetic
+ * in the same order (same bits).  FMGAN_EOVERFLOW when batch*channels*hw does not fit a long long.
+ */
+int fmgan_face_region_blocks(int batch, long long hw);
+int fmgan_face_region_loss_f32(const float *r, const float *g, float *partial, int batch, int channels, long long hw,
+                               void *stream);
+int fmgan_face_region_backward_f32(const float *r, const float *g, const float *grad_loss, float *grad_g, int batch,
+                                   int channels, long long hw, void *stream);
+int fmgan_render_mask_f32(const float *r, float *mask, int batch, int channels, long long hw, void *stream);
+
+/*
  * Demodulation coefficients of ModulatedConv2d (stylegan2.py:258-262):
  *   demod[b,o] = rsqrt( sum_{i,k} (scale * weight[o,i,k] * style[b,i])^2 + eps )
  *   weight [cout, cin, ktaps] f32 (the [1,cout,cin,k,k] parameter), style [batch, cin] f32,
