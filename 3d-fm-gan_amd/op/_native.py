@@ -227,6 +227,15 @@ def upfirdn2d_strided(in_ptr, device, major, in_h, in_w, plane_stride, row_strid
     return out
 
 
+def blur_noise_bias_act_serves(batch, channels, in_h, in_w, plane_stride, row_stride, kernel_shape, pad):
+    """Would blur_noise_bias_act launch a kernel for this shape (host logic, nothing runs)?  False is the case in which
+    it returns None: neither the row-march nor the plane-tile kernel serves the plane size or a FIR wider than 4 taps."""
+    kh, kw = kernel_shape
+    pad0, pad1 = pad
+    return lib().fmgan_blur_noise_bias_act_select(None, None, None, batch, channels, in_h, in_w, plane_stride, row_stride,
+                                                  kh, kw, pad0, pad1, pad0, pad1) > 0
+
+
 def blur_noise_bias_act(in_ptr, device, batch, channels, in_h, in_w, plane_stride, row_stride, kernel, pad, noise,
                         noise_weight, bias, alpha, scale, force_path=-1, out=None):
     """blur -> (+noise) -> +bias -> lrelu*scale in one pass over a strided f32 input; returns [B,C,out_h,out_w] or None
@@ -519,6 +528,34 @@ def wino_weight(wt):
     with on_device(wt) as stream:
         check(lib().fmgan_wino_weight_f32(fp(wt), fp(u), cin, cout, stream), 'wino_weight')
     return u
+
+
+def wino_input(x, style):
+    """The input transform alone: x [B,cin,H,W] (H, W even), style [B,cin] -> V [16, cin, B*(H/2)*(W/2)]."""
+    require_gpu(x, 'input')
+    x, style = x.contiguous(), style.contiguous()
+    b, cin, h, w = x.shape
+    v = torch.empty((16, cin, b * (h // 2) * (w // 2)), dtype=torch.float32, device=x.device)
+    with on_device(x) as stream:
+        check(lib().fmgan_wino_input_f32(fp(x), fp(style), fp(v), b, cin, h, w, stream), 'wino_input')
+    return v
+
+
+def wino_output(m, demod, batch, h, w, noise=None, noise_weight=None, bias=None, fuse_act=False, alpha=0.2,
+                act_scale=2 ** 0.5):
+    """The output transform + StyledConv epilogue alone: M [16, cout, B*(H/2)*(W/2)] -> out [B,cout,H,W]."""
+    require_gpu(m, 'm')
+    m = m.contiguous()
+    cout = m.shape[1]
+    if m.shape[0] != 16 or m.shape[2] != batch * (h // 2) * (w // 2):
+        raise RuntimeError('wino_output: M must be [16, cout, B*(H/2)*(W/2)]')
+    out = torch.empty((batch, cout, h, w), dtype=torch.float32, device=m.device)
+    nz = noise.contiguous() if noise is not None else None
+    with on_device(m) as stream:
+        check(lib().fmgan_wino_output_f32(fp(m), fp(demod), fp(nz), fp(noise_weight), fp(bias), fp(out), batch, cout, h, w,
+                                          1 if nz is None else nz.shape[0], int(bool(fuse_act)), float(alpha),
+                                          float(act_scale), stream), 'wino_output')
+    return out
 
 
 def modconv2d_winograd(x, wt, style, demod, noise=None, noise_weight=None, bias=None, fuse_act=False, alpha=0.2,

@@ -355,19 +355,24 @@ class StyledConv(nn.Module):
                                                    act.negative_slope, act.scale, out=out_)
             nbytes = 4 * shape[0] * shape[1] * shape[2]
             ws = None
-            if placement.active() and nbytes >= placement.MIN_BYTES:
+            if (placement.active() and nbytes >= placement.MIN_BYTES
+                    and _native.blur_noise_bias_act_serves(b, c, 2 * h + 1, 2 * w + 1, ps, rs, conv.blur.kernel.shape,
+                                                           (pad0, pad1))):
                 # the largest buffers of the forward: a persistent pair whose placement was selected by measurement
-                # (op/placement.py: the same kernel runs at 4.85 or 5.17 TB/s depending on which two blocks it gets)
+                # (op/placement.py: the same kernel runs at 4.85 or 5.17 TB/s depending on which two blocks it gets).
+                # Only where the fused blur has a kernel for the shape: otherwise consume() launches nothing, the
+                # selection would time a no-op and the persistent output would never be written.
                 ws = placement.workspace(self, (b, c, h, w), shape, (b, c, oh, ow), input.device, produce, consume)
             if ws is not None:
                 buf, out = ws.buf, ws.out
                 produce(buf)
-                consume(buf, out)
+                if consume(buf, out) is None:
+                    raise RuntimeError('StyledConv: the fused blur declined a shape its selection reported as served')
             else:
                 buf = torch.empty(shape, dtype=torch.float32, device=input.device)
                 produce(buf)
                 out = consume(buf, None)
-                if out is None:   # shapes neither kernel serves (planes > ~110^2 narrower than 64): two passes
+                if out is None:   # neither kernel serves it (planes > ~110^2 narrower than 64, FIRs wider than 4 taps): two passes
                     out = _native.upfirdn2d_strided(buf.data_ptr() + 4 * off, input.device, b * c, 2 * h + 1, 2 * w + 1, ps,
                                                     rs, conv.blur.kernel, pad0, pad1, pad0, pad1).view(b, c, oh, ow)
                     out = _native.noise_bias_act(out, noise, self.noise.weight, act.bias, act.negative_slope, act.scale)

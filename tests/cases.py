@@ -122,6 +122,18 @@ GENERATOR_CASES = [
     dict(name='g1024_full', size=1024, n_mlp=8, shape=None, b=1, mode='latent', stride=32),
 ]
 
+# The headline configuration (bench.py's pairs1024 shard): batch 8, full width.  Kept OUT of GENERATOR_CASES — the CPU
+# oracle test and gen_generator / gen_fp64 iterate that list and a B = 8 1024^2 CPU forward takes minutes.  Fixture:
+# tests/golden/generator_b8.npz (every image of the RGB pyramid, fp32 and fp64), tools/make_golden.py gen_generator_b8.
+GENERATOR_B8_CASE = dict(name='g1024_b8', size=1024, n_mlp=8, shape=None, b=8, mode='latent')
+
+
+def b8_stride(res):
+    """Sample stride of the res x res image of the RGB pyramid: whole images up to 32^2, 16 x 16 samples of every larger
+    one (all 8 samples of the batch; fp32 + float64 of nine images stay under 1 MiB; the stats vector covers the rest)."""
+    return 1 if res <= 32 else res // 16
+
+
 E2E_CASES = [
     dict(name='e2e_256', size=256, b=1, tsr_encode='Photo Image', sliced_layer=None, use_tanh=False, stride=8),
     dict(name='e2e_256_render_tanh', size=256, b=2, tsr_encode='Render Image', sliced_layer=list(range(4, 14)),

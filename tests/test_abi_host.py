@@ -366,3 +366,18 @@ def test_winograd_selection_rule_is_host_logic():
         assert not stylegan2.winograd_pays(8, 512, 512, 64, 64)
     finally:
         stylegan2.WINOGRAD = old
+
+
+def test_fused_blur_selection_declines_firs_wider_than_four_taps():
+    """fmgan_blur_noise_bias_act_select is host logic: the 4-tap blur of every upsampling layer has a kernel (plane-tile for
+    small planes, row-march / LDS-DMA ring for wide ones); a 5-tap FIR such as [1,4,6,4,1] has none, which is the case in
+    which _native.blur_noise_bias_act returns None and StyledConv takes the two-pass form (and no placement workspace)."""
+    from op import _native
+    L = _lib()
+    for b, c, h in ((8, 512, 17), (8, 256, 129), (8, 32, 1025)):
+        _, off, ps, rs = _native.aligned_rows_shape(b, c, h, h, 1)
+        assert L.fmgan_blur_noise_bias_act_select(None, None, None, b, c, h, h, ps, rs, 4, 4, 1, 1, 1, 1) in (1, 2, 5)
+        assert _native.blur_noise_bias_act_serves(b, c, h, h, ps, rs, (4, 4), (1, 1))
+        _, off, ps, rs = _native.aligned_rows_shape(b, c, h, h, 2)
+        assert L.fmgan_blur_noise_bias_act_select(None, None, None, b, c, h, h, ps, rs, 5, 5, 2, 1, 2, 1) == -2
+        assert not _native.blur_noise_bias_act_serves(b, c, h, h, ps, rs, (5, 5), (2, 1))

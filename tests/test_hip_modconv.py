@@ -7,16 +7,13 @@ import torch
 
 import cases
 import synth
+from parity import tol as _tol, window_check as _window_check
 
 pytestmark = pytest.mark.gpu
 
 
 def dev():
     return torch.device('cuda', 0)
-
-
-def _tol(ref, k=2e-5):
-    return dict(atol=k * max(1.0, float(np.abs(ref).max())), rtol=1e-5)
 
 
 def _load(module, kind, seed):
@@ -213,6 +210,125 @@ def test_winograd_form_vs_c_oracle(cfg, act):
     assert torch.equal(_native.modconv2d_winograd(xd, wt, sd, dm, **kw), y)          # bit-reproducible
     with pytest.raises(RuntimeError):
         _native.modconv2d_winograd(xd[:, :, :-1], wt, sd, dm)                          # odd height
+
+
+# ---------------------------------------------------------------------------------------- Winograd transforms, alone
+# The three kernels of csrc/winograd.hip are grid-stride loops over one work item per (sample, channel, 2x2 tile) — or per
+# (cout, cin) pair — launched with at most num_CU * 32 blocks of 256 threads.  test_winograd_form_vs_c_oracle stays below
+# 10^5 work items: one trip.  Here every kernel gets more than two full trips' worth, at a power-of-two plane and at a
+# ragged even one, against a float64 statement of Bt (s.d) B, G g Gt and At M A (+ epilogue) on the same device tensors.
+#
+# Bounds, derived from the operation counts in csrc/winograd.hip (u = 2^-24, gamma(n) = n u / (1 - n u); a value that passes
+# through n rounded operations carries a relative error of at most gamma(n); products by 0.5 are exact):
+#   input   v = +-d +-d' (+-d'' +-d''')   with d = fl(x * s): one product and two levels of adds on each of 4 terms
+#           |v - exact| <= gamma(3) * 4 * max|x s|
+#   weight  u = sum of 9 taps with weights in {1, 1/2, 1/4} whose magnitudes sum to at most 9/4: two adds per stage, two stages
+#           |u - exact| <= gamma(4) * 9/4 * max|wt|
+#   output  y = (sum of 9 +-m, four levels of adds) * demod                                  -> 5 operations
+#           then + fl(nw * noise), + bias, * alpha (negative side), * act_scale              -> 4 more
+#           |y - exact| <= gamma(5) * 9 max|m| max|demod|                                                        (fuse_act = 0)
+#           |y - exact| <= gamma(9) * (9 max|m| max|demod| + |nw| max|noise| + max|bias|) * act_scale            (fuse_act = 1)
+#           (the leaky ReLU is 1-Lipschitz, so a sign decided differently near 0 stays inside the same bound)
+_WINO_U = 2.0 ** -24
+
+
+def _gamma(n):
+    return n * _WINO_U / (1 - n * _WINO_U)
+
+
+def _two_trips():
+    """Work items of two full trips of the transforms' capped grid on this device."""
+    return 2 * torch.cuda.get_device_properties(0).multi_processor_count * 32 * 256
+
+
+def _wino_mats(d):
+    bt = torch.tensor([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=torch.float64, device=d)
+    g = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=torch.float64, device=d)
+    at = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=torch.float64, device=d)
+    return bt, g, at
+
+
+@pytest.mark.parametrize('cfg', [(8, 520, 64, 64), (16, 2048, 18, 30)], ids=['b8_c520_64x64', 'b16_c2048_18x30'])
+def test_winograd_input_transform_past_two_grid_trips_vs_float64(cfg):
+    from op import _native
+    b, c, h, w = cfg
+    th, tw = h // 2, w // 2
+    assert b * c * th * tw > _two_trips()
+    d = dev()
+    gen = torch.Generator(device=d).manual_seed(77)
+    x = torch.randn(b, c, h, w, device=d, generator=gen)
+    s = 1.0 + 0.5 * torch.randn(b, c, device=d, generator=gen)
+    v = _native.wino_input(x, s)
+    bt = _wino_mats(d)[0]
+    bound = _gamma(3) * 4 * float((x.double() * s.double()[:, :, None, None]).abs().max())
+    worst = 0.0
+    for b0 in range(0, b, 4):                       # float64 reference a few samples at a time (memory)
+        xs = torch.nn.functional.pad(x[b0:b0 + 4].double() * s[b0:b0 + 4].double()[:, :, None, None], (1, 1, 1, 1))
+        tiles = xs.unfold(2, 4, 2).unfold(3, 4, 2)                                    # [b, c, th, tw, 4, 4]
+        ref = torch.einsum('ar,bcyxrq,kq->akcbyx', bt, tiles, bt)                     # Bt d B
+        nb = tiles.shape[0]
+        got = v.view(4, 4, c, b, th, tw)[:, :, :, b0:b0 + nb]
+        assert torch.isfinite(got).all()
+        worst = max(worst, float((got.double() - ref).abs().max()))
+        del xs, tiles, ref
+    print(f'wino_input {cfg}: max error {worst:.3e}, bound {bound:.3e}')
+    assert worst <= bound, (worst, bound)
+
+
+def test_winograd_weight_transform_past_two_grid_trips_vs_float64():
+    from op import _native
+    cin, cout = 2050, 2056
+    assert cin * cout > _two_trips()
+    d = dev()
+    gen = torch.Generator(device=d).manual_seed(78)
+    wt = torch.randn(cin, 9, cout, device=d, generator=gen)
+    u = _native.wino_weight(wt)
+    g = _wino_mats(d)[1]
+    taps = wt.double().permute(0, 2, 1).reshape(cin, cout, 3, 3)
+    ref = torch.einsum('ar,iorq,kq->akoi', g, taps, g).reshape(16, cout, cin)     # G g Gt
+    bound = _gamma(4) * 9 / 4 * float(wt.abs().max())
+    assert torch.isfinite(u).all()
+    worst = float((u.double() - ref).abs().max())
+    print(f'wino_weight {cin}x{cout}: max error {worst:.3e}, bound {bound:.3e}')
+    assert worst <= bound, (worst, bound)
+
+
+@pytest.mark.parametrize('variant', ['noise_per_sample', 'noise_shared', 'no_act', 'no_demod'])
+@pytest.mark.parametrize('cfg', [(8, 520, 64, 64), (16, 2048, 18, 30)], ids=['b8_c520_64x64', 'b16_c2048_18x30'])
+def test_winograd_output_transform_past_two_grid_trips_vs_float64(cfg, variant):
+    from op import _native
+    b, c, h, w = cfg
+    th, tw = h // 2, w // 2
+    assert b * c * th * tw > _two_trips()
+    d = dev()
+    gen = torch.Generator(device=d).manual_seed(79)
+    m = torch.randn(16, c, b * th * tw, device=d, generator=gen)
+    dm = None if variant == 'no_demod' else 0.5 + torch.rand(b, c, device=d, generator=gen)
+    act = variant != 'no_act'
+    noise = torch.randn(1 if variant == 'noise_shared' else b, 1, h, w, device=d, generator=gen) if act else None
+    nw = torch.tensor([0.3], device=d)
+    bias = 0.1 * torch.randn(c, device=d, generator=gen)
+    alpha, act_scale = 0.2, 2 ** 0.5
+    y = _native.wino_output(m, dm, b, h, w, noise=noise, noise_weight=nw if act else None, bias=bias if act else None,
+                            fuse_act=act, alpha=alpha, act_scale=act_scale)
+    at = _wino_mats(d)[2]
+    mm = m.double().view(4, 4, c, b, th, tw)
+    ref = torch.einsum('ja,aqobyx,kq->boyjxk', at, mm, at).reshape(b, c, h, w)      # At M A
+    dmax = 1.0
+    if dm is not None:
+        ref = ref * dm.double()[:, :, None, None]
+        dmax = float(dm.max())
+    mag = 9 * float(m.abs().max()) * dmax
+    if act:
+        pre = ref + float(nw.double()) * noise.double() + bias.double()[None, :, None, None]
+        ref = torch.where(pre > 0, pre, pre * float(np.float32(alpha))) * float(np.float32(act_scale))
+        bound = _gamma(9) * (mag + float(nw) * float(noise.abs().max()) + float(bias.abs().max())) * act_scale
+    else:
+        bound = _gamma(5) * mag
+    assert torch.isfinite(y).all()
+    worst = float((y.double() - ref).abs().max())
+    print(f'wino_output {cfg} {variant}: max error {worst:.3e}, bound {bound:.3e}')
+    assert worst <= bound, (worst, bound)
 
 
 def test_rgb_fusable_is_host_logic_and_unsupported_shapes_are_refused():
@@ -477,30 +593,7 @@ def test_modconv_random_shapes_vs_c_oracle():
 # nb*cin*h*w < 2^31 elements; buffer-load staging only for tensors shorter than the parked voffset 0xFFFFFFF0 bytes)
 # must compute correctly; shapes just outside return FMGAN_EOVERFLOW without launching (tests/test_abi_host.py).
 # The tensors are 4-9 GB, so the check is the convolution's locality: output windows (all four corners, the last
-# rows/columns, the middle) against the C oracle run on the matching input crop.
-def _window_check(xd, wgt, s, y, mode, y0, x0, wh, ww):
-    from oracle import c_oracle
-    b, cin, h, w = xd.shape
-    if mode == 0:          # out[y,x] <- in[y-1..y+1, x-1..x+1]
-        iy0, ix0 = y0 - 1, x0 - 1
-        ih, iw = wh + 2, ww + 2
-    else:                  # mode 1: out[Y,X] <- in[(Y-2)/2 .. Y/2]; window start even
-        assert y0 % 2 == 0 and x0 % 2 == 0
-        iy0, ix0 = y0 // 2 - 1, x0 // 2 - 1
-        ih, iw = wh // 2 + 2, ww // 2 + 2
-    crop = torch.zeros(b, cin, ih, iw)
-    sy0, sx0 = max(iy0, 0), max(ix0, 0)
-    sy1, sx1 = min(iy0 + ih, h), min(ix0 + iw, w)
-    crop[:, :, sy0 - iy0:sy1 - iy0, sx0 - ix0:sx1 - ix0] = xd[:, :, sy0:sy1, sx0:sx1].cpu()
-    ref = c_oracle.modulated_conv2d(crop.numpy(), wgt.numpy(), s.numpy(), mode=mode, demodulate=True)
-    if mode == 0:
-        ref = ref[:, :, 1:1 + wh, 1:1 + ww]
-    else:                  # crop row r holds input row iy0 + r: output row Y = 2*(iy0 + r) + ky
-        oy, ox = y0 - 2 * iy0, x0 - 2 * ix0
-        ref = ref[:, :, oy:oy + wh, ox:ox + ww]
-    got = y[:, :, y0:y0 + wh, x0:x0 + ww].cpu().numpy()
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    np.testing.assert_allclose(got, ref, **_tol(ref))
+# rows/columns, the middle) against the C oracle run on the matching input crop (tests/parity.py: window_check).
 
 
 @pytest.mark.parametrize('cfg', [

@@ -164,6 +164,35 @@ def gen_generator():
     print('generator', len(out))
 
 
+def gen_generator_b8():
+    """cases.GENERATOR_B8_CASE: the reference Generator(1024, 512, 8) at batch 8 (the benchmark's shard), every image of
+    its RGB pyramid (return_rgb_list=True), in fp32 and in float64 -> generator_b8.npz.  Outputs only; whole images up
+    to 32^2, strided samples above (cases.b8_stride).  CPU wall time: 70 s for the two forwards together on a 16-core
+    box; two runs gave identical files."""
+    c = cases.GENERATOR_B8_CASE
+    out = {}
+    with torch.no_grad():
+        for dt, suffix in ((torch.float32, 'sub'), (torch.float64, 'sub64')):
+            g = stylegan2.Generator(c['size'], 512, c['n_mlp'], generator_net_shape=c['shape'])
+            g.load_state_dict(synth.state_dict('generator', g.state_dict(), seed=4))
+            g.to(dt).eval()
+            lat = synth.tensor(c['name'] + '/latent', (c['b'], g.n_latent, 512)).to(dt)
+            tsr = synth.tensor(c['name'] + '/tsr', (c['b'], 512, 4, 4)).to(dt)
+            rgbs = g(None, latent_styles=[lat], input_is_latent=True, use_external_input_tensor=True,
+                     external_input_tensor=tsr, randomize_noise=False, return_rgb_list=True)
+            assert len(rgbs) == g.log_size - 1 and tuple(rgbs[-1].shape) == (c['b'], 3, c['size'], c['size'])
+            for i, img in enumerate(rgbs):
+                key = f"{c['name']}/rgb{i}"
+                out[f'{key}/{suffix}'] = subsample(img, cases.b8_stride(img.shape[-1]))
+                assert out[f'{key}/{suffix}'].size <= 8 * 3 * 32 * 32
+                if dt == torch.float32:
+                    out[key + '/stats'] = stats(img)
+                print(' ', key, suffix, tuple(img.shape), float(img.abs().max()), flush=True)
+            del g, rgbs
+    np.savez_compressed(os.path.join(OUT, 'generator_b8.npz'), **out)
+    print('generator_b8', len(out))
+
+
 class _GWrap:
     """Forward_Inference_3_Encoder touches g_ema.module (Util/network_util.py:317-318) and never
     passes noise: expose .module and pin randomize_noise=False."""
@@ -505,4 +534,4 @@ if __name__ == '__main__':
          'generator': gen_generator, 'e2e': gen_encoders_e2e, 'discriminator': gen_discriminator,
          'image_io': gen_image_io, 'e2e_grad': gen_e2e_grad, 'fp64': gen_fp64, 'train_step': gen_train_step,
          'train_step_1024': gen_train_step_1024, 'face_id': gen_face_id,
-         'e2e_grad_latents': gen_e2e_grad_latents}[w]()
+         'e2e_grad_latents': gen_e2e_grad_latents, 'generator_b8': gen_generator_b8}[w]()
