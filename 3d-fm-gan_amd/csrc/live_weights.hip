@@ -10,7 +10,7 @@
 //   kind 0  dst[k] = src[k] * scale                                  (EqualLinear weight*scale, bias*lr_mul)
 //   kind 1  wt[i][t][o] = scale * W[o][i][t]   and   wsq[o][i] = sum_t W[o][i][t]^2
 //           (MFMA A-operand layout of ModulatedConv2d + the demodulation sums; same arithmetic, same order as
-//           modconv_weight_prep_f32 / modconv_wsq_f32 in modconv.hip -> identical bits)
+//           modconv_weight_prep_f32 / modconv_wsq_f32 in modconv_prep.hip -> identical bits)
 // Kind 1 is an LDS-tiled transpose: a block owns 64 output channels x 16 input channels x ktaps; reads are runs of
 // 16*ktaps contiguous floats per output channel (576 B for 3x3), writes are runs of 64 contiguous floats (256 B).
 // (32 x 8 tiles — 288-byte reads, 128-byte writes — ran the refresh of Generator(1024) at ~0.8 TB/s.)

@@ -1,5 +1,5 @@
 // ModulatedConv2d with bf16 operands and fp32 accumulation on v_mfma_f32_32x32x16_bf16 (gfx950) — the reduced-precision
-// contraction of BASELINE config 5's bf16 leg.  NOT the parity path: the fp32 kernel (modconv.hip) stays the default and
+// contraction of BASELINE config 5's bf16 leg.  NOT the parity path: the fp32 kernel (modconv_fwd.hip) stays the default and
 // the only one the parity tests of the forward hot path see.
 //
 // Same operator as fmgan_modconv2d_f32 (stylegan2.py:250-298 restated input-modulated):
@@ -85,7 +85,7 @@ struct BFParams {
 
 // LDS-DMA (`buffer_load_dwordx4 ... lds`): 64 lanes x 16 bytes land at lds + lane * 16 (wave-uniform base) from
 // rsrc base + voff (per lane, range-checked) + soff (wave-uniform); no VGPR destination.  (Device-pass guard: the host
-// pass of hipcc drops the host stub of a template kernel whose body names this builtin directly — see modconv.hip.)
+// pass of hipcc drops the host stub of a template kernel whose body names this builtin directly — see modconv_fwd.hip.)
 template <typename RSRC>
 __device__ __forceinline__ void dma16_to_lds(RSRC rsrc, void* lds, unsigned voff, unsigned soff) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void modconv_mfma_bf16(const BFParams p) {
       }
       __builtin_amdgcn_sched_barrier(0);
     } else {
-      // (tap = ky*3+kx, input-offset index j -> (ro, co) = (1,1) (1,0) (0,1) (0,0), phase = py*2+px); modconv.hip
+      // (tap = ky*3+kx, input-offset index j -> (ro, co) = (1,1) (1,0) (0,1) (0,0), phase = py*2+px); modconv_fwd.hip
       constexpr int T[9][3] = {{0, 0, 0}, {2, 1, 0}, {6, 2, 0}, {8, 3, 0}, {1, 0, 1}, {7, 2, 1}, {3, 0, 2}, {5, 1, 2}, {4, 0, 3}};
       bf16x8 bq[4][RNP];
 #pragma unroll
@@ -389,7 +389,7 @@ int launch_bf16(BFParams& p, hipStream_t s) {
 // — the three dropped cross terms (am*bl, al*bm, al*bl) are at the size of ONE fp32 rounding of the product.  Six bf16
 // MFMAs with fp32 accumulation therefore reproduce the fp32 contraction to fp32 accuracy at 16/6 = 2.7x its matrix-pipe
 // rate.  Forward modes 0 and 1 only (inference); a LABELLED path — the parity path and every headline number stay on
-// v_mfma_f32_32x32x2_f32 (modconv.hip).  Held by tests/test_hip_modconv_bf16.py to the fp32 kernel's own tolerances
+// v_mfma_f32_32x32x2_f32 (modconv_fwd.hip).  Held by tests/test_hip_modconv_bf16.py to the fp32 kernel's own tolerances
 // (per layer and end to end against the float64 fixtures).
 //   * tile: 32 output channels x (4*RNP rows x 32 columns) positions per block, 4 waves on the same channels;
 //     LDS per 16-channel chunk: 3 weight pieces [piece][tap][k-half][32][8] = 27 KB + 3 patch pieces — 60 KB for

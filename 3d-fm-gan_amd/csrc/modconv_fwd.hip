@@ -18,7 +18,7 @@
 //   * Transposed (upsampling) conv = 4 output phases of the same contraction; a block owns one row
 //     parity and both column parities so each lane stores the two adjacent columns as one 8-byte store.
 //   * Tiny layers (4x4 .. 8x8) pack several samples into one pixel tile.
-// Demodulation: one wave per output channel, sum over Cin by wave-shuffle butterfly.
+// Demodulation and the weight layouts: modconv_prep.hip; weight gradients: modconv_wgrad.hip; the stand-alone ToRGB: torgb.hip.
 #include <type_traits>
 #include "common.h"
 #include <cstdio>
@@ -48,91 +48,6 @@ __device__ __forceinline__ const float* uniform_ptr(const float* q) {
   return (const float*)(((unsigned long long)hi << 32) | lo);
 }
 __device__ __forceinline__ unsigned uniform_u32(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// ------------------------------------------------------------------ demod
-// PRE: W is the per-(o,i) sum of squared taps [cout][cin] (modconv_wsq_f32, cached with the weight) instead of the
-// raw weight — the same fma chains in the same order, so both variants give identical bits.
-template <bool PRE>
-__global__ __launch_bounds__(256) void modconv_demod_f32(const float* __restrict__ W,
-                                                         const float* __restrict__ style,
-                                                         float* __restrict__ demod, int batch, int cout, int cin,
-                                                         int ktaps, float scale, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (o >= cout) return;  // wave-uniform
-  const float* wo = W + (long long)o * cin * (PRE ? 1 : ktaps);
-  constexpr int MAXJ = 8;
-  const bool cached = cin <= 64 * MAXJ;
-  float wsq[MAXJ];
-  if (cached) {
-#pragma unroll
-    for (int j = 0; j < MAXJ; ++j) {
-      const int i = lane + 64 * j;
-      float q = 0.f;
-      if (i < cin) {
-        if constexpr (PRE) q = wo[i];
-        else
-          for (int t = 0; t < ktaps; ++t) { const float w = wo[i * ktaps + t]; q = fmaf(w, w, q); }
-      }
-      wsq[j] = q;
-    }
-  }
-  // PRE (inference): one wave per (output channel, sample) — the grid's y extent covers the batch, so the samples' style
-  // loads are independent waves instead of `batch` dependent round trips inside one wave.  The raw-weight form keeps one
-  // wave per channel (it squares nine taps per weight; repeating that per sample would cost more than it hides).
-  for (int b = blockIdx.y; b < batch; b += gridDim.y) {
-    const float* sb = style + (long long)b * cin;
-    float acc = 0.f;
-    if (cached) {
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) {
-        const int i = lane + 64 * j;
-        if (i < cin) { const float m = sb[i]; acc = fmaf(wsq[j], m * m, acc); }
-      }
-    } else {
-      for (int i = lane; i < cin; i += 64) {
-        float q = 0.f;
-        if constexpr (PRE) q = wo[i];
-        else
-          for (int t = 0; t < ktaps; ++t) { const float w = wo[i * ktaps + t]; q = fmaf(w, w, q); }
-        const float m = sb[i];
-        acc = fmaf(q, m * m, acc);
-      }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) demod[(long long)b * cout + o] = 1.0f / sqrtf(scale * scale * acc + eps);
-  }
-}
-
-__global__ __launch_bounds__(256) void modconv_wsq_f32(const float* __restrict__ W, float* __restrict__ wsq,
-                                                       long long n, int ktaps) {
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (long long)gridDim.x * blockDim.x) {
-    float q = 0.f;
-    for (int t = 0; t < ktaps; ++t) { const float w = W[idx * ktaps + t]; q = fmaf(w, w, q); }
-    wsq[idx] = q;
-  }
-}
-
-// ------------------------------------------------------------------ weight prep
-// kind 0 (forward):                          wt[i][t][o] = scale * W[o][i][t]
-// kind 1 (data-gradient of the plain conv):  wt[o][t][i] = scale * W[o][i][ktaps-1-t]   (taps flipped, roles swapped)
-// kind 2 (data-gradient of the transposed):  wt[o][t][i] = scale * W[o][i][t]           (roles swapped)
-__global__ __launch_bounds__(256) void modconv_weight_prep_f32(const float* __restrict__ W, float* __restrict__ wt,
-                                                               int cout, int cin, int ktaps, float scale, int kind) {
-  const long long total = (long long)cout * cin * ktaps;
-  const int cols = kind == 0 ? cout : cin;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)(idx % cols);
-    const long long rt = idx / cols;
-    const int t = (int)(rt % ktaps), r = (int)(rt / ktaps);
-    float v;
-    if (kind == 0) v = W[((long long)c * cin + r) * ktaps + t];
-    else v = W[((long long)r * cin + c) * ktaps + (kind == 1 ? ktaps - 1 - t : t)];
-    wt[idx] = scale * v;
-  }
-}
 
 // ------------------------------------------------------------------ MFMA conv
 struct MCParams {
@@ -230,12 +145,50 @@ __device__ __forceinline__ float mc_epilogue(float v, const MCParams& p, float n
 //         pipelines give identical bits).  Patch slots outside the image rely on the buffer range check: their
 //         voffset is parked out of range and the DMA writes zeros (tools/exp/dma_probe.hip).  Chunks that the range check
 //         cannot serve (a partial last chunk, tensors of 4 GB and more, ragged Cout) are filled synchronously instead.
-template <int MODE, int RM, int RNP, int WM, int WN, bool RGB = false, int MINB = 2, int KC_ = MC_KC, int PIPE = 0>
-__global__ __launch_bounds__(256, MINB) void modconv_mfma_f32(const MCParams p) {
+// Tile: one of the named tile types below (its name shows in the mangled symbol and in rocprofv3 output).
+//   MODE           see above
+//   RM x RNP       32 x 32 accumulators per wave: rows of 32 output channels x groups of 32 positions
+//   WM x WN        waves of the block along output channels x positions (4 in all)
+//   MINB           blocks per CU the register budget is set for (launch bounds: 512 / MINB registers per lane)
+//   KC             input channels per LDS chunk
+//   PIPE           see above
+template <int MODE_, int RM_, int RNP_, int WM_, int WN_, int MINB_, int KC_, int PIPE_>
+struct TileShape {
+  static constexpr int MODE = MODE_, RM = RM_, RNP = RNP_, WM = WM_, WN = WN_, MINB = MINB_, KC = KC_, PIPE = PIPE_;
+  static constexpr int BM = 32 * RM * WM, BN = 32 * RNP * WN;   // output channels x positions of a block
+};
+// Named <conv><BM>x<BN><pipeline>[Kc4][R<registers per lane>]: Reg = register prefetch, Dma = LDS-DMA; Kc4 = 4-channel
+// chunks (8 otherwise); R... where two tiles differ in nothing but the register budget.
+//                                         MODE  RM  RNP  WM  WN  MINB     KC  PIPE
+struct Plain128x128Reg         : TileShape<   0,  2,   2,  2,  2,    2, MC_KC,    0> {};
+struct Plain128x128DmaKc4      : TileShape<   0,  2,   2,  2,  2,    3,     4,    1> {};
+struct Plain128x256DmaKc4      : TileShape<   0,  4,   2,  1,  4,    2,     4,    1> {};   // 0.75 LDS reads / MFMA
+struct Plain64x128Reg          : TileShape<   0,  2,   1,  1,  4,    3, MC_KC,    0> {};
+struct Plain64x128Dma          : TileShape<   0,  2,   1,  1,  4,    3,     8,    1> {};
+struct Plain64x256DmaKc4       : TileShape<   0,  2,   2,  1,  4,    3,     4,    1> {};   // 3 blocks per CU
+struct Plain32x128Reg          : TileShape<   0,  1,   1,  1,  4,    4, MC_KC,    0> {};
+struct Plain32x128Dma          : TileShape<   0,  1,   1,  1,  4,    4,     8,    1> {};
+struct Plain32x256DmaKc4R128   : TileShape<   0,  1,   2,  1,  4,    4,     4,    1> {};   // in a 128-register budget (4 blocks per CU, no spills)
+struct Stride2x128x128Reg      : TileShape<   2,  2,   2,  2,  2,    2, MC_KC,    0> {};
+struct Stride2x64x128Reg       : TileShape<   2,  2,   1,  1,  4,    2, MC_KC,    0> {};
+struct Stride2x32x128Reg       : TileShape<   2,  1,   1,  1,  4,    2, MC_KC,    0> {};
+struct Transposed64x128Reg     : TileShape<   1,  2,   1,  1,  4,    2, MC_KC,    0> {};
+struct Transposed64x128Dma     : TileShape<   1,  2,   1,  1,  4,    2,     8,    1> {};
+struct Transposed32x128Reg     : TileShape<   1,  1,   1,  1,  4,    3, MC_KC,    0> {};
+struct Transposed32x128DmaR128 : TileShape<   1,  1,   1,  1,  4,    4,     8,    1> {};   // 4 blocks per CU instead of 3
+#ifdef FMGAN_EXPERIMENTS   // tiles no default and no fall-back reaches: measured, kept for A/B runs (see mc_variant)
+struct Plain32x256Dma          : TileShape<   0,  1,   2,  1,  4,    3,     8,    1> {};   // 3 blocks per CU
+struct Plain32x256DmaKc4R96    : TileShape<   0,  1,   2,  1,  4,    5,     4,    1> {};   // 4-channel chunks: 5-6 blocks per CU
+struct Transposed32x256Dma     : TileShape<   1,  1,   2,  1,  4,    2,     8,    1> {};   // 32 x 256 positions
+struct Transposed32x128DmaR170 : TileShape<   1,  1,   1,  1,  4,    3,     8,    1> {};
+#endif
+
+template <class Tile, bool RGB>
+__global__ __launch_bounds__(256, Tile::MINB) void modconv_mfma_f32(const MCParams p) {
+  constexpr int MODE = Tile::MODE, RM = Tile::RM, RNP = Tile::RNP, WM = Tile::WM, WN = Tile::WN, KC = Tile::KC, PIPE = Tile::PIPE;
   static_assert(!RGB || MODE == 0, "the RGB epilogue belongs to the plain conv");
-  constexpr int KC = KC_;
   static_assert(PIPE == 1 || KC == MC_KC, "the register pipeline is built for 8-channel chunks");
-  constexpr int BM = 32 * RM * WM;
+  constexpr int BM = Tile::BM;
   constexpr int NPH = MODE == 1 ? 4 : 1;   // output phases per position
   static_assert(WM * WN == 4, "4 waves per block");
   extern __shared__ float smem[];
@@ -290,7 +243,7 @@ __global__ __launch_bounds__(256, MINB) void modconv_mfma_f32(const MCParams p) 
     const int pos = (wn * RNP + g) * 32 + l31;
     const int tx = pos & (TW - 1), r = pos >> tw_log2;
     const int ty = r % seg_th, nbi = r / seg_th;
-    // (a thin segment's tile may hold fewer than BN positions — launch_cfg shrinks it until its patch fits the main
+    // (a thin segment's tile may hold fewer than BN positions — launch_tile shrinks it until its patch fits the main
     // segment's LDS image: the rows past nb * th read sample nb - 1's patch and are never stored)
     pbase[g] = min(nbi, seg_nb - 1) * samp + SP * ty * PWP + SP * tx + (XORG - ORG);
     pos_b[g] = nbi < seg_nb ? b0 + nbi : p.batch; pos_y[g] = y0 + ty; pos_x[g] = x0 + tx;
@@ -1098,10 +1051,12 @@ constexpr size_t MC_LDS_MAX = 160 * 1024;    // LDS of a CU
 
 // Returns FMGAN_OK, an error, or +1 when this variant cannot serve the shape (PIPE 1 with an LDS image over the limit):
 // the caller then launches the register-pipeline variant.
-template <int MODE, int RM, int RNP, int WM, int WN, int MINB = 2, int KC = MC_KC, int PIPE = 0>
-int launch_cfg(MCParams& p, hipStream_t s) {
-  if constexpr (MODE != 0) { if (p.rgb_out) return FMGAN_EUNSUPPORTED; }
-  constexpr int BM = 32 * RM * WM, BN = 32 * RNP * WN;
+// FUSES_RGB: the tile's kernel with the ToRGB epilogue is built too, for launches with p.rgb_out.
+template <class Tile, bool FUSES_RGB>
+int launch_tile(MCParams& p, hipStream_t s) {
+  constexpr int MODE = Tile::MODE, MINB = Tile::MINB, KC = Tile::KC, PIPE = Tile::PIPE, BM = Tile::BM, BN = Tile::BN;
+  static_assert(!FUSES_RGB || MODE == 0, "the RGB epilogue belongs to the plain conv");
+  if constexpr (!FUSES_RGB) { if (p.rgb_out) return FMGAN_EUNSUPPORTED; }
   constexpr int SP = MODE == 2 ? 2 : 1;
   p.o_tiles = (p.cout + BM - 1) / BM;
   long long blocks = 0;
@@ -1159,7 +1114,7 @@ int launch_cfg(MCParams& p, hipStream_t s) {
       // one block per CU may use more than the 64 KB a launch gets by default (160 KB per CU on gfx950)
       static bool raised = false;
       if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_mfma_f32<MODE, RM, RNP, WM, WN, false, MINB, KC, PIPE>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_mfma_f32<Tile, false>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)MC_LDS_MAX) != hipSuccess) {
           (void)hipGetLastError();
           return 1;
@@ -1168,43 +1123,101 @@ int launch_cfg(MCParams& p, hipStream_t s) {
       }
     }
   }
-  if constexpr (MODE == 0) {
+  if constexpr (FUSES_RGB) {
     if (p.rgb_out) {
       if (p.o_tiles != 1 || p.ksplit != 1) return FMGAN_EUNSUPPORTED;
-      hipLaunchKernelGGL((modconv_mfma_f32<0, RM, RNP, WM, WN, true, MINB, KC, PIPE>), dim3((unsigned)blocks, 1), dim3(256), lds, s, p);
+      hipLaunchKernelGGL((modconv_mfma_f32<Tile, true>), dim3((unsigned)blocks, 1), dim3(256), lds, s, p);
       return fmgan_check_launch();
     }
   }
-  hipLaunchKernelGGL((modconv_mfma_f32<MODE, RM, RNP, WM, WN, false, MINB, KC, PIPE>), dim3((unsigned)blocks, p.ksplit), dim3(256), lds, s, p);
+  hipLaunchKernelGGL((modconv_mfma_f32<Tile, false>), dim3((unsigned)blocks, p.ksplit), dim3(256), lds, s, p);
   return fmgan_check_launch();
 }
 
-// Which pipeline variant serves (mode, cfg): 'A' = register prefetch, 'B'/'C' = LDS-DMA variants.  Defaults are the
-// measured winners (profiles/r02_modconv_variants.md).  Only the experiments build (make experiments:
-// -DFMGAN_EXPERIMENTS, tools/exp/lib/libfmgan_hip_exp.so) reads FMGAN_MC_V<mode><cfg>=A|B|C, FMGAN_MC_DEBUG and
-// FMGAN_MC_CLOCKPTR; the product library has no environment switch and no ablation code path.
-inline char mc_variant(int mode, int cfg) {
-#ifndef FMGAN_EXPERIMENTS
-  static const char defaults[3][3] = {{'C', 'C', 'E'}, {'A', 'B', 'D'}, {'A', 'A', 'A'}};   // comments: see below
-  return defaults[mode][cfg];
+// ---- the tile table: every tile a (mode, cfg) can run on, by variant letter.  'A' = register prefetch (serves every
+// shape: the fall-back of the others), 'B'..'E' = LDS-DMA variants.  The FIRST entry of a (mode, cfg) is its default, the
+// measured winner (profiles/r02_modconv_variants.md).  The product build holds the defaults and what launch_any can turn them
+// into; the experiments build (make experiments: -DFMGAN_EXPERIMENTS, tools/exp/lib/libfmgan_hip_exp.so) adds the other
+// measured tiles, the fused-ToRGB kernels of the tiles a fused launch only reaches through a variant switch, and alone reads
+// FMGAN_MC_V<mode><cfg>=A..E, FMGAN_MC_DEBUG and FMGAN_MC_CLOCKPTR; the product library has no environment switch, no
+// ablation code path and no kernel it cannot launch.
+// measured on MI355X (profiles/r02_modconv_variants.md): plain conv, Cout >= 96: 128 x 256 tile by LDS-DMA (C);
+// Cout >= 48: 64 x 256 in 4-channel chunks, three blocks per CU (C; 1470 -> 1390 us at 512^2 against 8-channel chunks
+// at two blocks per CU, possible since the scalar wave index freed ~25 VGPRs); Cout < 48: 32 x 256, three blocks per CU
+// (C: 1701 us at 1024^2; 32 x 128 by LDS-DMA 1809, register pipeline 1760-1790, 32 x 512 1873);
+// transposed conv: LDS-DMA (B) for every width.
+// Round 3 (profiles/r03_modconv_block_phases.md, r03_modconv_layers_ab.md), after the wide patch and the buffer-store
+// epilogue: Cout < 48 plain: 32 x 256 in 4-channel chunks (24 KB of LDS): E = in a 128-register budget, 4 blocks per
+// CU instead of 3, no spills (1446 -> 1361 us at 1024^2, with the fused ToRGB 1852 -> 1796-1800); D = in a 96-register
+// budget, 5 blocks per CU, 55-90 spilled dwords: 1 % behind E (1377 / 1806-1826).  Transposed 32-channel tile in a
+// 128-register budget (D: 4 blocks per CU instead of 3, 7 spilled dwords in the epilogue; 785 -> 757 us at 512^2).
+struct TileEntry {
+  int mode, cfg;           // cfg: pick_cfg's output-channel class, 0 = 128, 1 = 64, 2 = 32 channels per block
+  char variant;
+  int BM, BN;              // output channels x positions of the launched block
+  bool fuses_rgb;          // takes launches with the ToRGB epilogue (p.rgb_out)
+  int (*launch)(MCParams&, hipStream_t);
+};
+template <class Tile, bool FUSES_RGB = false>
+constexpr TileEntry tile_entry(int cfg, char variant) {
+  return {Tile::MODE, cfg, variant, Tile::BM, Tile::BN, FUSES_RGB, &launch_tile<Tile, FUSES_RGB>};
+}
+#ifdef FMGAN_EXPERIMENTS
+constexpr bool MC_EXP = true;
 #else
+constexpr bool MC_EXP = false;
+#endif
+constexpr TileEntry MC_TILES[] = {
+    // plain conv.  (A fused-ToRGB launch on the 128- and 64-channel classes never takes 'C' and takes 'B' only when
+    // FMGAN_MC_V0<cfg> asks for it: launch_any.)
+    tile_entry<Plain128x256DmaKc4>(0, 'C'),
+    tile_entry<Plain128x128DmaKc4, MC_EXP>(0, 'B'),
+    tile_entry<Plain128x128Reg, true>(0, 'A'),
+    tile_entry<Plain64x256DmaKc4>(1, 'C'),
+    tile_entry<Plain64x128Dma, MC_EXP>(1, 'B'),
+    tile_entry<Plain64x128Reg, true>(1, 'A'),
+    tile_entry<Plain32x256DmaKc4R128, true>(2, 'E'),
+    tile_entry<Plain32x128Dma, true>(2, 'B'),
+    tile_entry<Plain32x128Reg, true>(2, 'A'),
+#ifdef FMGAN_EXPERIMENTS
+    tile_entry<Plain32x256Dma, true>(2, 'C'),
+    tile_entry<Plain32x256DmaKc4R96, true>(2, 'D'),
+#endif
+    // transposed conv (pick_cfg has no 128-channel class for it)
+    tile_entry<Transposed64x128Dma>(1, 'B'),
+    tile_entry<Transposed64x128Reg>(1, 'A'),
+    tile_entry<Transposed32x128DmaR128>(2, 'D'),
+    tile_entry<Transposed32x128Reg>(2, 'A'),
+#ifdef FMGAN_EXPERIMENTS
+    tile_entry<Transposed32x256Dma>(1, 'C'),
+    tile_entry<Transposed32x128DmaR170>(2, 'B'),
+    tile_entry<Transposed32x256Dma>(2, 'C'),
+#endif
+    // stride-2 conv
+    tile_entry<Stride2x128x128Reg>(0, 'A'),
+    tile_entry<Stride2x64x128Reg>(1, 'A'),
+    tile_entry<Stride2x32x128Reg>(2, 'A'),
+};
+
+// null: this (mode, cfg) has no tile for the letter
+inline const TileEntry* find_tile(int mode, int cfg, char variant) {
+  for (const TileEntry& e : MC_TILES)
+    if (e.mode == mode && e.cfg == cfg && e.variant == variant) return &e;
+  return nullptr;
+}
+
+inline char mc_variant(int mode, int cfg) {
+  char v = 'A';
+  for (const TileEntry& e : MC_TILES)
+    if (e.mode == mode && e.cfg == cfg) { v = e.variant; break; }
+#ifdef FMGAN_EXPERIMENTS
   // (read per call: the A/B tools sweep variants inside one process)
-  // measured on MI355X (profiles/r02_modconv_variants.md): plain conv, Cout >= 96: 128 x 256 tile by LDS-DMA (C);
-  // Cout >= 48: 64 x 256 in 4-channel chunks, three blocks per CU (C; 1470 -> 1390 us at 512^2 against 8-channel chunks
-  // at two blocks per CU, possible since the scalar wave index freed ~25 VGPRs); Cout < 48: 32 x 256, three blocks per CU
-  // (C: 1701 us at 1024^2; 32 x 128 by LDS-DMA 1809, register pipeline 1760-1790, 32 x 512 1873);
-  // transposed conv: LDS-DMA (B) for every width.
-  // Round 3 (profiles/r03_modconv_block_phases.md, r03_modconv_layers_ab.md), after the wide patch and the buffer-store
-  // epilogue: Cout < 48 plain: 32 x 256 in 4-channel chunks (24 KB of LDS): E = in a 128-register budget, 4 blocks per
-  // CU instead of 3, no spills (1446 -> 1361 us at 1024^2, with the fused ToRGB 1852 -> 1796-1800); D = in a 96-register
-  // budget, 5 blocks per CU, 55-90 spilled dwords: 1 % behind E (1377 / 1806-1826).  Transposed 32-channel tile in a
-  // 128-register budget (D: 4 blocks per CU instead of 3, 7 spilled dwords in the epilogue; 785 -> 757 us at 512^2).
-  const char defaults[3][3] = {{'C', 'C', 'E'}, {'A', 'B', 'D'}, {'A', 'A', 'A'}};
   char name[32];
   snprintf(name, sizeof(name), "FMGAN_MC_V%d%d", mode, cfg);
   const char* e = getenv(name);
-  return (e && e[0] >= 'A' && e[0] <= 'E') ? e[0] : defaults[mode][cfg];
+  if (e && e[0] >= 'A' && e[0] <= 'E') v = e[0];
 #endif
+  return v;
 }
 
 // Tile configurations (output channels x positions per block; blocks per CU the register budget allows):
@@ -1228,13 +1241,17 @@ inline int pick_cfg(int mode, int cout, long long positions) {
   return cout >= 48 ? 1 : 2;
 }
 
-inline void cfg_dims(int mode, int cfg, int& BM, int& BN) {
+// The PLANNING MODEL of a cfg — what pick_ksplit, count_blocks and rgb_fusable reckon with: 128 positions per block for
+// every cfg and 2 / 3 / 4 co-resident blocks per CU.  Not the launched tile (MC_TILES): the 256-position tiles and the
+// transposed 32-channel default (4 blocks per CU, modelled as 3) differ from it.  Split-K factors and workspace sizes
+// follow from these values, so they stay as they are when a tile changes.
+inline void model_tile_dims(int mode, int cfg, int& BM, int& BN) {
   (void)mode;
   const int bm[3] = {128, 64, 32};
   BM = bm[cfg]; BN = 128;
 }
 
-inline int cfg_blocks_per_cu(int mode, int cfg) {
+inline int model_blocks_per_cu(int mode, int cfg) {
   if (mode == 1) return cfg == 2 ? 3 : 2;
   return cfg == 0 ? 2 : (cfg == 1 ? (mode == 0 ? 3 : 2) : 4);
 }
@@ -1255,50 +1272,22 @@ inline int launch_any(int mode, int cfg, MCParams& p, hipStream_t s) {
   // the 128-position tiles (and their split-K plan)
   // (mid-size launches — 16^2 .. 32^2 at B=8 — then take the LDS-DMA pipeline on the 128-position tile: 119 vs 126 us
   // and 380 vs 396 us; below ~1500 positions the register pipeline is as fast or faster)
-  if (mode == 0 && v == 'C') {
-    const bool small = p.ksplit > 1 || blocks_with(p, cfg == 0 ? 128 : (cfg == 1 ? 64 : 32), 256) < 2LL * FMGAN_NUM_CU;
+  const TileEntry* e = nullptr;
+  if (mode == 0 && v == 'C' && (e = find_tile(0, cfg, 'C')) != nullptr) {
+    const bool small = p.ksplit > 1 || blocks_with(p, e->BM, e->BN) < 2LL * FMGAN_NUM_CU;
     if (cfg < 2 && (small || p.rgb_out)) v = (!p.rgb_out && (long long)p.batch * p.h * p.w >= 1536) ? 'B' : 'A';
     else if (cfg == 2 && small) v = 'B';
   }
-  if (mode == 0 && (v == 'D' || v == 'E')) {
-    const bool small = p.ksplit > 1 || blocks_with(p, 32, 256) < 2LL * FMGAN_NUM_CU;
+  // ('D' and 'E' are tiles of the 32-channel class; the rule measures with their size whatever the cfg)
+  if (mode == 0 && (v == 'D' || v == 'E') && (e = find_tile(0, 2, v)) != nullptr) {
+    const bool small = p.ksplit > 1 || blocks_with(p, e->BM, e->BN) < 2LL * FMGAN_NUM_CU;
     if (small) v = 'B';
   }
   int st = 1;
-  if (mode == 0) {
-    switch (cfg) {
-      case 0:
-        if (v == 'B') st = launch_cfg<0, 2, 2, 2, 2, 3, 4, 1>(p, s);
-        else if (v == 'C') st = launch_cfg<0, 4, 2, 1, 4, 2, 4, 1>(p, s);                      // 128 x 256: 0.75 reads / MFMA
-        return st != 1 ? st : launch_cfg<0, 2, 2, 2, 2>(p, s);
-      case 1:
-        if (v == 'B') st = launch_cfg<0, 2, 1, 1, 4, 3, 8, 1>(p, s);
-        else if (v == 'C') st = launch_cfg<0, 2, 2, 1, 4, 3, 4, 1>(p, s);                      // 64 x 256, 4-channel chunks: 3 blocks per CU
-        return st != 1 ? st : launch_cfg<0, 2, 1, 1, 4, 3>(p, s);
-      default:
-        if (v == 'B') st = launch_cfg<0, 1, 1, 1, 4, 4, 8, 1>(p, s);
-        else if (v == 'C') st = launch_cfg<0, 1, 2, 1, 4, 3, 8, 1>(p, s);                      // 32 x 256, 3 blocks per CU
-        else if (v == 'D') st = launch_cfg<0, 1, 2, 1, 4, 5, 4, 1>(p, s);                      // 32 x 256, 4-channel chunks: 5-6 blocks per CU
-        else if (v == 'E') st = launch_cfg<0, 1, 2, 1, 4, 4, 4, 1>(p, s);                      // the same in a 128-register budget (4 blocks per CU, no spills)
-        return st != 1 ? st : launch_cfg<0, 1, 1, 1, 4, 4>(p, s);
-    }
-  }
-  if (mode == 2) {
-    switch (cfg) {
-      case 0: return launch_cfg<2, 2, 2, 2, 2>(p, s);
-      case 1: return launch_cfg<2, 2, 1, 1, 4>(p, s);
-      default: return launch_cfg<2, 1, 1, 1, 4>(p, s);
-    }
-  }
-  if (cfg == 1) {
-    if (v == 'B') st = launch_cfg<1, 2, 1, 1, 4, 2, 8, 1>(p, s);
-    else if (v == 'C') st = launch_cfg<1, 1, 2, 1, 4, 2, 8, 1>(p, s);                          // 32 x 256 positions
-    return st != 1 ? st : launch_cfg<1, 2, 1, 1, 4>(p, s);
-  }
-  if (v == 'B') st = launch_cfg<1, 1, 1, 1, 4, 3, 8, 1>(p, s);
-  else if (v == 'C') st = launch_cfg<1, 1, 2, 1, 4, 2, 8, 1>(p, s);
-  else if (v == 'D') st = launch_cfg<1, 1, 1, 1, 4, 4, 8, 1>(p, s);                            // as B in a 128-register budget: 4 blocks per CU
-  return st != 1 ? st : launch_cfg<1, 1, 1, 1, 4, 3>(p, s);
+  if (v != 'A' && (e = find_tile(mode, cfg, v)) != nullptr) st = e->launch(p, s);
+  if (st != 1) return st;
+  e = find_tile(mode, cfg, 'A');                        // the register pipeline serves what the LDS-DMA tile could not
+  return e ? e->launch(p, s) : FMGAN_EUNSUPPORTED;
 }
 
 // Blocks of one launch (all segments), for a given tile configuration.
@@ -1310,7 +1299,7 @@ inline void out_dims(int mode, int h, int w, int& oh, int& ow) {
 
 inline long long count_blocks(int mode, int cfg, int batch, int cout, int h, int w) {
   int BM, BN;
-  cfg_dims(mode, cfg, BM, BN);
+  model_tile_dims(mode, cfg, BM, BN);
   if (mode == 2) out_dims(2, h, w, h, w);   // positions = outputs
   MCParams::Seg sg[3] = {{0, 0, h, w}, {h, 0, 1, w + 1}, {0, w, h, 1}};   // any order: only the sum matters
   long long blocks = 0;
@@ -1328,10 +1317,10 @@ inline int pick_ksplit(int mode, int batch, int cin, int cout, int h, int w) {
   const int cfg = pick_cfg(mode, cout, (long long)batch * poh * pow_);
   const long long blocks = count_blocks(mode, cfg, batch, cout, h, w);
   const int chunks = (cin + MC_KC - 1) / MC_KC;
-  const int slots = FMGAN_NUM_CU * cfg_blocks_per_cu(mode, cfg);   // co-resident blocks (VGPR-limited)
+  const int slots = FMGAN_NUM_CU * model_blocks_per_cu(mode, cfg);   // co-resident blocks (VGPR-limited)
   if (blocks >= 4LL * slots || chunks < 4) return 1;
   int BM, BN;
-  cfg_dims(mode, cfg, BM, BN);
+  model_tile_dims(mode, cfg, BM, BN);
   // time unit: one chunk of one block.  Finish pass: (2*ks + 1) * out_bytes at ~4 TB/s against ~5 us per full-size chunk
   const double mfma_per_chunk = (double)(BM / 32) * (BN / 32) * (mode == 1 ? 9 : 9) * (MC_KC / 2) / 4.0;  // per wave
   const double t_chunk_us = mfma_per_chunk * 64.0 / 2360.0 * 2.0;       // two blocks share each SIMD
@@ -1349,564 +1338,7 @@ inline int pick_ksplit(int mode, int batch, int cin, int cout, int h, int w) {
   return best;
 }
 
-// ------------------------------------------------------------------ weight gradient of the plain conv (MFMA)
-// gw[o,i,ky,kx] = sum_{b,y,x} (d[b,o] * go[b,o,y,x]) * (s[b,i] * x[b,i,y+ky-1,x+kx-1])
-// GEMM with M = Cout (A rows), N = Cin (B columns), K = pixels; the 9 taps are 9 accumulators that share the A
-// operand and read B at 9 constant offsets of the staged halo patch.  A block owns a 32(o) x 32(i) tile; its four
-// waves take the four 32-pixel quarters of each 128-pixel tile (so a chunk is 16 K-steps x 9 MFMAs per wave) and are
-// summed through LDS at the end; the pixel range is split over blocks (fixed-order finish, no atomics).
-struct WGParams {
-  const float* go; const float* d; const float* x; const float* s; float* partial;
-  int batch, cin, cout, h, w;
-  int tw_log2, th, tiles_x, tiles_y, ntiles, ksplit, tiles_per_split, o_tiles, i_tiles;
-};
-
-__global__ __launch_bounds__(256, 2) void modconv_wgrad_f32(const WGParams p) {
-  constexpr int SA = 129;                      // Gz row stride (128 pixels + 1: conflict-free across o)
-  extern __shared__ float smem[];
-  const int TW = 1 << p.tw_log2, PWP = TW + 2, PH = p.th + 2;
-  const int SB = PH * PWP + 1 + ((PH * PWP) & 1);   // odd stride: conflict-free across i
-  float* Gz = smem;                            // [32][SA]
-  float* Us = smem + 32 * SA;                  // [32][SB]
-  // wave index as an SGPR: LDS-DMA destinations (M0), piece guards and tile offsets derived from it stay scalar
-  // (left in a VGPR, every `buffer_load ... lds` sat in a waterfall loop with v_readfirstlane)
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, khalf = lane >> 5;
-  const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
-  const int o_tile = lb % p.o_tiles;
-  const int i_tile = (lb / p.o_tiles) % p.i_tiles;
-  const int ks = lb / (p.o_tiles * p.i_tiles);
-  const int o0 = o_tile * 32, i0 = i_tile * 32;
-  const int hw = p.h * p.w;
-
-  f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-  const int t_begin = ks * p.tiles_per_split, t_end = min(p.ntiles, t_begin + p.tiles_per_split);
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    const int tx = tile % p.tiles_x;
-    const int ty = (tile / p.tiles_x) % p.tiles_y;
-    const int b = tile / (p.tiles_x * p.tiles_y);
-    const int y0 = ty * p.th, x0 = tx * TW;
-    __syncthreads();
-    // A: 32 output channels x 128 pixels of d*go
-    for (int idx = tid; idx < 32 * 128; idx += 256) {
-      const int o = idx >> 7, pix = idx & 127;
-      const int y = y0 + (pix >> p.tw_log2), x = x0 + (pix & (TW - 1));
-      float v = 0.f;
-      if (o0 + o < p.cout && y < p.h && x < p.w) {
-        const long long ch = (long long)b * p.cout + o0 + o;
-        v = p.go[ch * hw + y * p.w + x];
-        if (p.d) v *= p.d[ch];
-      }
-      Gz[o * SA + pix] = v;
-    }
-    // B: 32 input channels x halo patch of s*x
-    const int patch = PH * PWP;
-    for (int idx = tid; idx < 32 * patch; idx += 256) {
-      const int i = idx / patch, q = idx - i * patch;
-      const int y = y0 + q / PWP - 1, x = x0 + q % PWP - 1;
-      float v = 0.f;
-      if (i0 + i < p.cin && y >= 0 && y < p.h && x >= 0 && x < p.w) {
-        const long long ch = (long long)b * p.cin + i0 + i;
-        v = p.x[ch * hw + y * p.w + x] * p.s[ch];
-      }
-      Us[i * SB + q] = v;
-    }
-    __syncthreads();
-    const float* ga = Gz + l31 * SA + wave * 32 + khalf;
-    const float* ub = Us + l31 * SB;
-    float a_cur, b_cur[9], a_nxt = 0.f, b_nxt[9];
-    auto fetch = [&](float& a, float (&bb)[9], int j) {
-      const int pix = wave * 32 + 2 * j + khalf;
-      const int off = (pix >> p.tw_log2) * PWP + (pix & (TW - 1));
-      a = ga[2 * j];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) bb[t] = ub[off + (t / 3) * PWP + (t % 3)];
-    };
-    fetch(a_cur, b_cur, 0);
-#pragma unroll 4
-    for (int j = 0; j < 16; ++j) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (j + 1 < 16) fetch(a_nxt, b_nxt, j + 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int t = 0; t < 9; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur, b_cur[t], acc[t], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      a_cur = a_nxt;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) b_cur[t] = b_nxt[t];
-    }
-  }
-  // sum the four waves through LDS, one tap at a time, and write the block's partial slab [ks][t][o][i]
-  float* red = smem;   // [4][32][33]
-  float* slab = p.partial + (long long)ks * 9 * p.cout * p.cin;
-  for (int t = 0; t < 9; ++t) {
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int o = (r & 3) + 8 * (r >> 2) + 4 * khalf;
-      red[(wave * 32 + o) * 33 + l31] = acc[t][r];
-    }
-    __syncthreads();
-    for (int e = tid; e < 32 * 32; e += 256) {
-      const int o = e >> 5, i = e & 31;
-      const float v = red[o * 33 + i] + red[(32 + o) * 33 + i] + red[(64 + o) * 33 + i] + red[(96 + o) * 33 + i];
-      if (o0 + o < p.cout && i0 + i < p.cin) slab[((long long)t * p.cout + o0 + o) * p.cin + i0 + i] = v;
-    }
-  }
-}
-
-// gw[o][i][t] = scale * sum_ks partial[ks][t][o][i]
-__global__ __launch_bounds__(256) void modconv_wgrad_finish_f32(const float* __restrict__ partial, float* __restrict__ gw,
-                                                                int cout, int cin, int ksplit, float scale) {
-  const int total = cout * cin * 9;
-  for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
-    const int t = idx % 9, oi = idx / 9;
-    float v = 0.f;
-    for (int ks = 0; ks < ksplit; ++ks) v += partial[((long long)ks * 9 + t) * cout * cin + oi];
-    gw[idx] = v * scale;
-  }
-}
-
-
-// ---- 64 x 64 weight-gradient tile (round 2).  The 32 x 32 kernel above spends most of its time filling LDS: every
-// 144 MFMAs of a wave need a new 128-pixel tile, and a block re-reads gz / u for a quarter of the output a 64 x 64 tile
-// covers.  Here a block owns 64 (o) x 64 (i), its four waves the four 32 x 32 quadrants, and ALL of them walk the same
-// 2 x TW pixels per step: 2 TW/2... = TW K-steps x 9 MFMAs = 288 MFMAs per wave between two barriers (TW = 32), with the
-// pixel pair of an MFMA (its K = 2) taken from the two rows — so consecutive K-steps move one pixel along x and the
-// 3 x 3 window of the shifted operand slides: 3 new LDS reads per step instead of 9 (+1 for gz): 4 reads per 9 MFMAs.
-struct WG64Params {
-  // R[t][a][b] = sum_{n,y,x} (sa[n,a] * A[n,a,y,x]) * (sb[n,b] * B[n,b, SP*y + ky - ORG, SP*x + kx - ORG])
-  //   SP = 1, ORG = 1: plain conv        A = go [cout, h, w],          B = x  [cin, h, w]         gw[o=a][i=b]
-  //   SP = 2, ORG = 0: transposed conv   A = x  [cin, h, w],           B = go [cout, 2h+1, 2w+1]  gw[o=b][i=a]
-  //   SP = 2, ORG = 0: stride-2 conv     A = go [cout, h', w'],        B = x  [cin, h, w]         gw[o=a][i=b]
-  const float* A; const float* sa; const float* B; const float* sb; float* partial;
-  int batch, ca, cb, ha, wa, hb, wb;
-  int tiles_x, tiles_y, ntiles, ksplit, tiles_per_split, a_tiles, b_tiles;
-};
-
-template <int TWL2, int SP>
-__global__ __launch_bounds__(256, 2) void modconv_wgrad64_f32(const WG64Params p) {
-  constexpr int TW = 1 << TWL2, ORG = SP == 1 ? 1 : 0;
-  constexpr int PA = 2 * TW + 1;                          // odd pitches: conflict-free over channels
-  constexpr int BR = SP + 3, PWP = SP * (TW - 1) + 3;     // rows / columns of the shifted operand's patch
-  constexpr int PB = (BR * PWP) | 1;
-  // per thread: float4 of A; of B: float4 of the row interiors + the scalars left over
-  constexpr int NA4 = 64 * 2 * TW / 4 / 256;
-  constexpr int RV = SP == 1 ? TW / 4 : PWP / 4;          // float4 per patch row (SP 1: the aligned interior x0 .. x0+TW-1)
-  constexpr int RS = PWP - 4 * RV;                        // scalars per patch row (SP 1: the two halo columns)
-  constexpr int NB4 = (64 * BR * RV + 255) / 256, NBS = (64 * BR * RS + 255) / 256;
-  extern __shared__ float smem[];
-  float* As = smem;               // [64][PA]
-  float* Bs = smem + 64 * PA;     // [64][PB]
-  // wave index as an SGPR: LDS-DMA destinations (M0), piece guards and tile offsets derived from it stay scalar
-  // (left in a VGPR, every `buffer_load ... lds` sat in a waterfall loop with v_readfirstlane)
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, khalf = lane >> 5;
-  const int aq = wave >> 1, bq = wave & 1;
-  const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
-  const int a_tile = lb % p.a_tiles;
-  const int b_tile = (lb / p.a_tiles) % p.b_tiles;
-  const int ks = lb / (p.a_tiles * p.b_tiles);
-  const int a0 = a_tile * 64, b0 = b_tile * 64;
-  const long long hwa = (long long)p.ha * p.wa, hwb = (long long)p.hb * p.wb;
-  // A rows start 16-byte aligned and a float4 never straddles the right edge (B is read with dword-aligned vectors)
-  const bool vec = (p.wa & 3) == 0 && (((uintptr_t)p.A) & 15) == 0 && (((uintptr_t)p.B) & 3) == 0;
-
-  f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-  // ---- staging plan: everything a tile step needs is loaded into registers while the previous step is on the
-  // matrix pipe and written to LDS after the barrier (the forward kernel's register pipeline)
-  f32x4 a4[NA4], b4[NB4];
-  float bs[NBS], sa_n = 1.f, sb_n = 1.f, sa_lane = 1.f, sb_lane = 1.f;
-  const int my_a = a0 + aq * 32 + l31, my_b = b0 + bq * 32 + l31;
-  auto decode = [&](int tile, int& n, int& y0, int& x0) {
-    const int tx = tile % p.tiles_x;
-    const int ty = (tile / p.tiles_x) % p.tiles_y;
-    n = tile / (p.tiles_x * p.tiles_y);
-    y0 = ty * 2; x0 = tx * TW;
-  };
-  // patch (row r, column c) of the shifted operand <-> its pixel
-  auto issue = [&](int tile) {
-    int n, y0, x0;
-    decode(tile, n, y0, x0);
-    sa_n = (p.sa && my_a < p.ca) ? p.sa[(long long)n * p.ca + my_a] : (my_a < p.ca ? 1.f : 0.f);
-    sb_n = (p.sb && my_b < p.cb) ? p.sb[(long long)n * p.cb + my_b] : (my_b < p.cb ? 1.f : 0.f);
-    if (!vec) return;
-#pragma unroll
-    for (int k = 0; k < NA4; ++k) {
-      const int q = tid + 256 * k;
-      const int a = q / (2 * TW / 4), rem = q % (2 * TW / 4);
-      const int y = y0 + rem / (TW / 4), x = x0 + 4 * (rem % (TW / 4));
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (a0 + a < p.ca && y < p.ha && x < p.wa)
-        v = *reinterpret_cast<const f32x4*>(p.A + ((long long)n * p.ca + a0 + a) * hwa + (long long)y * p.wa + x);
-      a4[k] = v;
-    }
-    const int by0 = SP * y0 - ORG, bx0 = SP * x0 - ORG;
-#pragma unroll
-    for (int k = 0; k < NB4; ++k) {
-      const int q = tid + 256 * k;
-      const int b = q / (BR * RV), rem = q % (BR * RV);
-      const int y = by0 + rem / RV, c = (SP == 1 ? 1 : 0) + 4 * (rem % RV), x = bx0 + c;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (q < 64 * BR * RV && b0 + b < p.cb && y >= 0 && y < p.hb) {
-        const float* src = p.B + ((long long)n * p.cb + b0 + b) * hwb + (long long)y * p.wb + x;
-        if (x >= 0 && x + 3 < p.wb) {
-          const f32x4_u t = *reinterpret_cast<const f32x4_u*>(src);
-          v.x = t.x; v.y = t.y; v.z = t.z; v.w = t.w;
-        } else {
-          if (x + 0 >= 0 && x + 0 < p.wb) v.x = src[0];
-          if (x + 1 >= 0 && x + 1 < p.wb) v.y = src[1];
-          if (x + 2 >= 0 && x + 2 < p.wb) v.z = src[2];
-          if (x + 3 >= 0 && x + 3 < p.wb) v.w = src[3];
-        }
-      }
-      b4[k] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < NBS; ++k) {
-      const int q = tid + 256 * k;
-      const int b = q / (BR * RS), rem = q % (BR * RS);
-      const int r = rem / RS, e = rem % RS;
-      // SP 1: the two halo columns 0 and TW+1; SP 2: the column(s) after the last float4
-      const int c = SP == 1 ? (e ? TW + 1 : 0) : 4 * RV + e;
-      const int y = by0 + r, x = bx0 + c;
-      bs[k] = (q < 64 * BR * RS && b0 + b < p.cb && y >= 0 && y < p.hb && x >= 0 && x < p.wb)
-                  ? p.B[((long long)n * p.cb + b0 + b) * hwb + (long long)y * p.wb + x] : 0.f;
-    }
-  };
-  auto commit = [&](int tile) {
-    sa_lane = sa_n; sb_lane = sb_n;
-    if (vec) {
-#pragma unroll
-      for (int k = 0; k < NA4; ++k) {
-        const int q = tid + 256 * k;
-        const int a = q / (2 * TW / 4), rem = q % (2 * TW / 4);
-        float* dst = As + a * PA + 4 * rem;                // (row r, column 4*c4) = r*TW + 4*c4 = 4*rem
-        dst[0] = a4[k].x; dst[1] = a4[k].y; dst[2] = a4[k].z; dst[3] = a4[k].w;
-      }
-#pragma unroll
-      for (int k = 0; k < NB4; ++k) {
-        const int q = tid + 256 * k;
-        if (q < 64 * BR * RV) {
-          const int b = q / (BR * RV), rem = q % (BR * RV);
-          float* dst = Bs + b * PB + (rem / RV) * PWP + (SP == 1 ? 1 : 0) + 4 * (rem % RV);
-          dst[0] = b4[k].x; dst[1] = b4[k].y; dst[2] = b4[k].z; dst[3] = b4[k].w;
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < NBS; ++k) {
-        const int q = tid + 256 * k;
-        if (q < 64 * BR * RS) {
-          const int b = q / (BR * RS), rem = q % (BR * RS);
-          const int r = rem / RS, e = rem % RS;
-          Bs[b * PB + r * PWP + (SP == 1 ? (e ? TW + 1 : 0) : 4 * RV + e)] = bs[k];
-        }
-      }
-      return;
-    }
-    // widths that are no multiple of 4 / unaligned tensors: guarded scalar fill, not prefetched
-    int n, y0, x0;
-    decode(tile, n, y0, x0);
-    for (int idx = tid; idx < 64 * 2 * TW; idx += 256) {
-      const int a = idx / (2 * TW), rc = idx - a * 2 * TW;
-      const int y = y0 + (rc >> TWL2), x = x0 + (rc & (TW - 1));
-      float v = 0.f;
-      if (a0 + a < p.ca && y < p.ha && x < p.wa) v = p.A[((long long)n * p.ca + a0 + a) * hwa + (long long)y * p.wa + x];
-      As[a * PA + rc] = v;
-    }
-    for (int idx = tid; idx < 64 * BR * PWP; idx += 256) {
-      const int b = idx / (BR * PWP), q = idx - b * BR * PWP;
-      const int y = SP * y0 - ORG + q / PWP, x = SP * x0 - ORG + q % PWP;
-      float v = 0.f;
-      if (b0 + b < p.cb && y >= 0 && y < p.hb && x >= 0 && x < p.wb)
-        v = p.B[((long long)n * p.cb + b0 + b) * hwb + (long long)y * p.wb + x];
-      Bs[b * PB + q] = v;
-    }
-  };
-
-  const float* ga = As + (aq * 32 + l31) * PA + khalf * TW;
-  const float* ub = Bs + (bq * 32 + l31) * PB + SP * khalf * PWP;
-  const int t_begin = ks * p.tiles_per_split, t_end = min(p.ntiles, t_begin + p.tiles_per_split);
-  if (t_begin < t_end) issue(t_begin);
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    __syncthreads();                       // every wave is done reading the previous step
-    commit(tile);
-    __syncthreads();
-    __builtin_amdgcn_sched_barrier(0);
-    if (tile + 1 < t_end) issue(tile + 1);  // in flight during this step's MFMAs
-    // K-step j: A pixel (y0 + khalf, x0 + j); tap (ky, kx) reads patch row SP*khalf + ky, column SP*j + kx.
-    // The 3-column window slides by SP columns per step: column c lives in slot c % 3.
-    float win[3][3];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) win[ky][c] = ub[ky * PWP + c] * sb_lane;
-    float a_cur = ga[0] * sa_lane, a_nxt = 0.f;
-#pragma unroll
-    for (int j = 0; j < TW; ++j) {
-      __builtin_amdgcn_sched_barrier(0);
-      float nw[3][SP];
-      if (j + 1 < TW) {                    // operands of step j + 1 while step j is on the matrix pipe
-        a_nxt = ga[j + 1];
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-          for (int e = 0; e < SP; ++e) nw[ky][e] = ub[ky * PWP + SP * j + 3 + e];
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-          acc[ky * 3 + kx] =
-              __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur, win[ky][(SP * j + kx) % 3], acc[ky * 3 + kx], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (j + 1 < TW) {
-        a_cur = a_nxt * sa_lane;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-          for (int e = 0; e < SP; ++e) win[ky][(SP * j + e) % 3] = nw[ky][e] * sb_lane;   // columns SP*j .. leave, SP*j+3 .. enter
-      }
-    }
-  }
-  float* slab = p.partial + (long long)ks * 9 * p.ca * p.cb;
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int a = a0 + aq * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-      if (a < p.ca && my_b < p.cb) slab[((long long)t * p.ca + a) * p.cb + my_b] = acc[t][r];
-    }
-}
-
-// gw[o][i][t] = scale * sum_ks partial[ks][t][a][b];  transposed: (a, b) = (i, o), else (o, i)
-__global__ __launch_bounds__(256) void modconv_wgrad64_finish_f32(const float* __restrict__ partial, float* __restrict__ gw,
-                                                                  int cout, int cin, int ksplit, float scale, int transposed) {
-  const int total = cout * cin * 9;
-  for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
-    const int t = idx % 9, oi = idx / 9;
-    const int o = oi / cin, i = oi - o * cin;
-    const long long ab = transposed ? (long long)i * cout + o : (long long)o * cin + i;
-    float v = 0.f;
-    for (int ks = 0; ks < ksplit; ++ks) v += partial[((long long)ks * 9 + t) * cout * cin + ab];
-    gw[idx] = v * scale;
-  }
-}
-
-// mode 0: plain conv; 1: transposed stride-2 conv (x [h,w], go [2h+1,2w+1]); 2: stride-2 valid conv (x [h,w], go [(h-3)/2+1, ..])
-inline bool wgrad64_setup(WG64Params& q, const float* go, const float* demod, const float* x, const float* style,
-                          int batch, int cin, int cout, int h, int w, int mode) {
-  if (cin < 48 || cout < 48) return false;
-  q.batch = batch;
-  if (mode == 0) {
-    q.A = go; q.sa = demod; q.ca = cout; q.ha = h; q.wa = w;
-    q.B = x; q.sb = style; q.cb = cin; q.hb = h; q.wb = w;
-  } else if (mode == 1) {
-    q.A = x; q.sa = style; q.ca = cin; q.ha = h; q.wa = w;
-    q.B = go; q.sb = demod; q.cb = cout; q.hb = 2 * h + 1; q.wb = 2 * w + 1;
-  } else {
-    if (h < 3 || w < 3) return false;
-    q.A = go; q.sa = demod; q.ca = cout; q.ha = (h - 3) / 2 + 1; q.wa = (w - 3) / 2 + 1;
-    q.B = x; q.sb = style; q.cb = cin; q.hb = h; q.wb = w;
-  }
-  if (q.wa < 16) return false;
-  const int TW = (mode == 0 && q.wa >= 32) ? 32 : 16;
-  q.tiles_x = (q.wa + TW - 1) / TW;
-  q.tiles_y = (q.ha + 1) / 2;
-  q.ntiles = batch * q.tiles_x * q.tiles_y;
-  q.a_tiles = (q.ca + 63) / 64;
-  q.b_tiles = (q.cb + 63) / 64;
-  const int pairs = q.a_tiles * q.b_tiles;
-  int ks = (FMGAN_NUM_CU * 4 + pairs - 1) / pairs;      // ~2 rounds of 2 blocks per CU
-  const int max_ks = q.ntiles / 4 > 0 ? q.ntiles / 4 : 1; // at least 4 tile steps per block
-  if (ks > max_ks) ks = max_ks;
-  if (ks < 1) ks = 1;
-  q.tiles_per_split = (q.ntiles + ks - 1) / ks;
-  q.ksplit = (q.ntiles + q.tiles_per_split - 1) / q.tiles_per_split;
-  return true;
-}
-
-template <int TWL2, int SP>
-inline void wgrad64_launch(const WG64Params& q, long long nblk, hipStream_t s) {
-  constexpr int TW = 1 << TWL2;
-  constexpr int PB = ((SP + 3) * (SP * (TW - 1) + 3)) | 1;
-  const size_t lds = sizeof(float) * 64 * ((2 * TW + 1) + PB);
-  hipLaunchKernelGGL((modconv_wgrad64_f32<TWL2, SP>), dim3((unsigned)nblk), dim3(256), lds, s, q);
-}
-
-inline void wgrad_plan(WGParams& p) {
-  p.tw_log2 = p.w >= 32 ? 5 : 4;
-  const int TW = 1 << p.tw_log2;
-  p.th = 128 / TW;
-  p.tiles_x = (p.w + TW - 1) / TW;
-  p.tiles_y = (p.h + p.th - 1) / p.th;
-  p.ntiles = p.batch * p.tiles_x * p.tiles_y;
-  p.o_tiles = (p.cout + 31) / 32;
-  p.i_tiles = (p.cin + 31) / 32;
-  const int pairs = p.o_tiles * p.i_tiles;
-  int ks = (FMGAN_NUM_CU * 6 + pairs - 1) / pairs;     // ~3 rounds of 2 blocks per CU
-  if (ks > p.ntiles) ks = p.ntiles;
-  if (ks < 1) ks = 1;
-  p.tiles_per_split = (p.ntiles + ks - 1) / ks;
-  p.ksplit = (p.ntiles + p.tiles_per_split - 1) / p.tiles_per_split;
-}
-
-// ------------------------------------------------------------------ ToRGB (1x1, <= 4 output channels, HBM-bound)
-template <int VEC>
-__global__ __launch_bounds__(256) void torgb_f32(const float* __restrict__ in, const float* __restrict__ weight,
-                                                 const float* __restrict__ style, const float* __restrict__ bias,
-                                                 const float* __restrict__ skip, float* __restrict__ out, int cin,
-                                                 int cout, int hw, float scale) {
-  extern __shared__ float ws[];  // [cout][cin]  scale*W*style for this sample
-  const int b = blockIdx.y;
-  for (int idx = threadIdx.x; idx < cout * cin; idx += 256)
-    ws[idx] = scale * weight[idx] * style[(long long)b * cin + idx % cin];
-  __syncthreads();
-  const int n = hw / VEC;
-  const float* inb = in + (long long)b * cin * hw;
-  for (int pidx = blockIdx.x * 256 + threadIdx.x; pidx < n; pidx += gridDim.x * 256) {
-    float acc[4][VEC];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) acc[c][e] = 0.f;
-#pragma unroll 8
-    for (int i = 0; i < cin; ++i) {
-      float v[VEC];
-      if constexpr (VEC == 4) {
-        const f32x4 t = reinterpret_cast<const f32x4*>(inb + (long long)i * hw)[pidx];
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-      } else {
-        v[0] = inb[(long long)i * hw + pidx];
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (c < cout) {
-          const float wv = ws[c * cin + i];
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) acc[c][e] = fmaf(wv, v[e], acc[c][e]);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (c >= cout) continue;
-      const long long off = ((long long)b * cout + c) * hw + (long long)pidx * VEC;
-      const float bv = bias ? bias[c] : 0.f;
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        float r = __fadd_rn(acc[c][e], bv);
-        if (skip) r = __fadd_rn(r, skip[off + e]);
-        acc[c][e] = r;
-      }
-      if constexpr (VEC == 4) {
-        f32x4 t; t.x = acc[c][0]; t.y = acc[c][1]; t.z = acc[c][2]; t.w = acc[c][3];
-        *reinterpret_cast<f32x4*>(out + off) = t;
-      } else {
-        out[off] = acc[c][0];
-      }
-    }
-  }
-}
-
-// Small images (<= 128^2): too few pixels for one-pixel-group-per-thread to fill the chip and the 512-channel loop is a
-// long dependent chain.  Here a block owns 64 pixels; its four waves each reduce a quarter of the input channels and
-// the partial sums meet in LDS (112-184 us -> ~15 us per layer at B=8).
-__global__ __launch_bounds__(256) void torgb_small_f32(const float* __restrict__ in, const float* __restrict__ weight,
-                                                       const float* __restrict__ style, const float* __restrict__ bias,
-                                                       const float* __restrict__ skip, float* __restrict__ out, int cin,
-                                                       int cout, int hw, float scale) {
-  extern __shared__ float ws[];            // [cout][cin] modulated weights, then [4][4][64] partial sums
-  const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int idx = threadIdx.x; idx < cout * cin; idx += 256)
-    ws[idx] = scale * weight[idx] * style[(long long)b * cin + idx % cin];
-  __syncthreads();
-  const int pix = blockIdx.x * 64 + lane;
-  const int per = (cin + 3) / 4, i_lo = wave * per, i_hi = min(cin, i_lo + per);
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  if (pix < hw) {
-    const float* ip = in + ((long long)b * cin + i_lo) * hw + pix;
-#pragma unroll 8
-    for (int i = i_lo; i < i_hi; ++i, ip += hw) {
-      const float v = *ip;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (c < cout) acc[c] = fmaf(ws[c * cin + i], v, acc[c]);
-    }
-  }
-  __syncthreads();                          // everyone is done with ws
-  float* red = ws;                          // host guarantees room for 4*4*64 floats
-#pragma unroll
-  for (int c = 0; c < 4; ++c) red[(wave * 4 + c) * 64 + lane] = acc[c];
-  __syncthreads();
-  if (wave == 0 && pix < hw) {
-    for (int c = 0; c < cout; ++c) {
-      // same association as the single-pass kernel would give per quarter; quarters added in channel order
-      float r = red[(0 * 4 + c) * 64 + lane] + red[(1 * 4 + c) * 64 + lane];
-      r += red[(2 * 4 + c) * 64 + lane];
-      r += red[(3 * 4 + c) * 64 + lane];
-      const long long off = ((long long)b * cout + c) * hw + pix;
-      r = __fadd_rn(r, bias ? bias[c] : 0.f);
-      if (skip) r = __fadd_rn(r, skip[off]);
-      out[off] = r;
-    }
-  }
-}
-
 }  // namespace
-
-extern "C" int fmgan_modconv_demod_f32(const float* weight, const float* style, float* demod, int batch, int cout,
-                                       int cin, int ktaps, float scale, float eps, void* stream) {
-  if (batch < 0 || cout <= 0 || cin <= 0 || ktaps <= 0) return FMGAN_EINVAL;
-  if (batch == 0) return FMGAN_OK;
-  if (!weight || !style || !demod) return FMGAN_EINVAL;
-  hipLaunchKernelGGL(modconv_demod_f32<false>, dim3((cout + 3) / 4), dim3(256), 0, (hipStream_t)stream, weight, style,
-                     demod, batch, cout, cin, ktaps, scale, eps);
-  return fmgan_check_launch();
-}
-
-extern "C" int fmgan_modconv_wsq_f32(const float* weight, float* wsq, int cout, int cin, int ktaps, void* stream) {
-  if (cout <= 0 || cin <= 0 || ktaps <= 0) return FMGAN_EINVAL;
-  if (!weight || !wsq) return FMGAN_EINVAL;
-  const long long n = (long long)cout * cin;
-  long long blocks = (n + 255) / 256;
-  if (blocks > FMGAN_NUM_CU * 16) blocks = FMGAN_NUM_CU * 16;
-  hipLaunchKernelGGL(modconv_wsq_f32, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, weight, wsq, n, ktaps);
-  return fmgan_check_launch();
-}
-
-extern "C" int fmgan_modconv_demod_wsq_f32(const float* wsq, const float* style, float* demod, int batch, int cout,
-                                           int cin, float scale, float eps, void* stream) {
-  if (batch < 0 || cout <= 0 || cin <= 0) return FMGAN_EINVAL;
-  if (batch == 0) return FMGAN_OK;
-  if (!wsq || !style || !demod) return FMGAN_EINVAL;
-  hipLaunchKernelGGL(modconv_demod_f32<true>, dim3((cout + 3) / 4, batch < 64 ? batch : 64), dim3(256), 0, (hipStream_t)stream, wsq, style, demod,
-                     batch, cout, cin, 1, scale, eps);
-  return fmgan_check_launch();
-}
-
-extern "C" int fmgan_modconv_weight_prep_f32(const float* weight, float* wt, int cout, int cin, int ktaps, float scale,
-                                             int kind, void* stream) {
-  if (cout <= 0 || cin <= 0 || ktaps <= 0) return FMGAN_EINVAL;
-  if (kind < 0 || kind > 2) return FMGAN_EUNSUPPORTED;
-  if (!weight || !wt) return FMGAN_EINVAL;
-  const long long total = (long long)cout * cin * ktaps;
-  long long blocks = (total + 255) / 256;
-  if (blocks > FMGAN_NUM_CU * 16) blocks = FMGAN_NUM_CU * 16;
-  hipLaunchKernelGGL(modconv_weight_prep_f32, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, weight, wt,
-                     cout, cin, ktaps, scale, kind);
-  return fmgan_check_launch();
-}
 
 extern "C" long long fmgan_modconv2d_workspace_bytes(int batch, int cin, int cout, int h, int w, int mode) {
   if (batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || mode < 0 || mode > 2) return 0;
@@ -1926,22 +1358,12 @@ struct RgbArgs {
 bool rgb_fusable(int batch, int cin, int cout, int h, int w) {
   const int cfg = pick_cfg(0, cout, (long long)batch * h * w);
   int BM, BN;
-  cfg_dims(0, cfg, BM, BN);
+  model_tile_dims(0, cfg, BM, BN);
   (void)cin;
   MCParams::Seg sg{0, 0, h, w};
   plan_segment(sg, batch, BN);
   // one output-channel tile, tiles of a single sample; the fused launch runs without split-K
   return cout <= BM && sg.nb == 1;
-}
-
-__global__ __launch_bounds__(256) void torgb_weight_mod_f32(const float* __restrict__ W, const float* __restrict__ style,
-                                                            float* __restrict__ wmod, int batch, int cout, int rgb_c,
-                                                            float scale) {
-  const int n = batch * 3 * cout;
-  for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
-    const int o = idx % cout, c = (idx / cout) % 3, b = idx / (3 * cout);
-    wmod[idx] = c < rgb_c ? scale * W[c * cout + o] * style[(long long)b * cout + o] : 0.f;
-  }
 }
 
 int modconv2d_impl(const float* in, const float* wt, const float* style, const float* demod,
@@ -1986,7 +1408,7 @@ int modconv2d_impl(const float* in, const float* wt, const float* style, const f
   p.noise = noise; p.noise_weight = noise_weight; p.bias = bias;
   p.noise_batch = noise_batch; p.fuse_act = fuse_act; p.alpha = alpha; p.act_scale = act_scale;
   // index ranges the kernel relies on: pixel indices (y*ow + x, h*w) and per-chunk weight offsets are 32-bit ints,
-  // whole-tensor offsets are 64-bit; per-tile input offsets (nb*cin*h*w) are checked per segment in launch_cfg
+  // whole-tensor offsets are 64-bit; per-tile input offsets (nb*cin*h*w) are checked per segment in launch_tile
   if ((long long)batch * cout * p.oh * p.ow > (1LL << 40)) return FMGAN_EOVERFLOW;
   if ((long long)p.oh * p.ow >= (1LL << 31) || (long long)h * w >= (1LL << 31)) return FMGAN_EOVERFLOW;
   if (cin > (1 << 20) || cout > (1 << 20)) return FMGAN_EOVERFLOW;
@@ -2036,17 +1458,6 @@ extern "C" int fmgan_modconv2d_f32(const float* in, const float* wt, const float
                         nullptr);
 }
 
-extern "C" int fmgan_torgb_weight_mod_f32(const float* weight, const float* style, float* wmod, int batch, int cout,
-                                          int rgb_channels, float scale, void* stream) {
-  if (batch < 0 || cout <= 0 || rgb_channels < 1 || rgb_channels > 3) return FMGAN_EINVAL;
-  if (batch == 0) return FMGAN_OK;
-  if (!weight || !style || !wmod) return FMGAN_EINVAL;
-  const int n = batch * 3 * cout;
-  hipLaunchKernelGGL(torgb_weight_mod_f32, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, weight, style, wmod,
-                     batch, cout, rgb_channels, scale);
-  return fmgan_check_launch();
-}
-
 extern "C" int fmgan_modconv2d_rgb_fusable(int batch, int cin, int cout, int h, int w) {
   if (batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return 0;
   return rgb_fusable(batch, cin, cout, h, w) ? 1 : 0;
@@ -2061,207 +1472,4 @@ extern "C" int fmgan_modconv2d_rgb_f32(const float* in, const float* wt, const f
   const RgbArgs rgb{rgb_wmod, rgb_bias, rgb_skip, rgb_out, rgb_channels};
   return modconv2d_impl(in, wt, style, demod, out, batch, cin, cout, h, w, 0, noise, noise_weight, bias, noise_batch,
                         fuse_act, alpha, act_scale, 0, 0, nullptr, 0, stream, &rgb);
-}
-
-extern "C" long long fmgan_modconv_wgrad_mode_workspace_bytes(int batch, int cin, int cout, int h, int w, int mode) {
-  if (batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || mode < 0 || mode > 2) return 0;
-  WG64Params q{};
-  if (wgrad64_setup(q, nullptr, nullptr, nullptr, nullptr, batch, cin, cout, h, w, mode))
-    return (long long)q.ksplit * 9 * cout * cin * (long long)sizeof(float);
-  if (mode != 0 || w < 16) return 0;
-  WGParams p{};
-  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
-  wgrad_plan(p);
-  return (long long)p.ksplit * 9 * cout * cin * (long long)sizeof(float);
-}
-
-extern "C" long long fmgan_modconv_wgrad_workspace_bytes(int batch, int cin, int cout, int h, int w) {
-  return fmgan_modconv_wgrad_mode_workspace_bytes(batch, cin, cout, h, w, 0);
-}
-
-extern "C" int fmgan_modconv_wgrad_mode_f32(const float* go, const float* demod, const float* x, const float* style,
-                                            float* gw, int batch, int cin, int cout, int h, int w, int mode, float scale,
-                                            void* workspace, long long workspace_bytes, void* stream) {
-  if (batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return FMGAN_EINVAL;
-  if (mode < 0 || mode > 2) return FMGAN_EUNSUPPORTED;
-  if (!go || !x || !style || !gw || !workspace) return FMGAN_EINVAL;
-  // go is the largest tensor of the transposed conv: [batch, cout, 2h+1, 2w+1]
-  const long long big_hw = mode == 1 ? (long long)(2 * h + 1) * (2 * w + 1) : (long long)h * w;
-  if ((long long)batch * (cin > cout ? cin : cout) * big_hw >= (1LL << 40)) return FMGAN_EOVERFLOW;
-  if (big_hw >= (1LL << 31) || cin > (1 << 20) || cout > (1 << 20)) return FMGAN_EOVERFLOW;
-  hipStream_t s = (hipStream_t)stream;
-  WG64Params q{};
-  if (wgrad64_setup(q, go, demod, x, style, batch, cin, cout, h, w, mode)) {
-    q.partial = (float*)workspace;
-    if (workspace_bytes < (long long)q.ksplit * 9 * cout * cin * (long long)sizeof(float)) return FMGAN_EINVAL;
-    const long long nblk = (long long)q.a_tiles * q.b_tiles * q.ksplit;
-    if (nblk > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-    if (mode == 0) {
-      if (q.wa >= 32) wgrad64_launch<5, 1>(q, nblk, s); else wgrad64_launch<4, 1>(q, nblk, s);
-    } else {
-      wgrad64_launch<4, 2>(q, nblk, s);
-    }
-    int st = fmgan_check_launch();
-    if (st != FMGAN_OK) return st;
-    int fb = (cout * cin * 9 + 255) / 256;
-    if (fb > FMGAN_NUM_CU * 16) fb = FMGAN_NUM_CU * 16;
-    hipLaunchKernelGGL(modconv_wgrad64_finish_f32, dim3(fb), dim3(256), 0, s, (const float*)workspace, gw, cout, cin,
-                       q.ksplit, scale, mode == 1 ? 1 : 0);
-    return fmgan_check_launch();
-  }
-  if (mode != 0 || w < 16) return FMGAN_EUNSUPPORTED;   // narrow / tiny layers: the host keeps MIOpen's wgrad
-  WGParams p{};
-  p.go = go; p.d = demod; p.x = x; p.s = style; p.partial = (float*)workspace;
-  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
-  wgrad_plan(p);
-  if (workspace_bytes < (long long)p.ksplit * 9 * cout * cin * (long long)sizeof(float)) return FMGAN_EINVAL;
-  const int TW = 1 << p.tw_log2;
-  const int patch = (p.th + 2) * (TW + 2);
-  const int SB = patch + 1 + (patch & 1);
-  size_t lds = sizeof(float) * (32 * 129 + 32 * (size_t)SB);
-  if (lds < sizeof(float) * 4 * 32 * 33) lds = sizeof(float) * 4 * 32 * 33;
-  const long long blocks = (long long)p.o_tiles * p.i_tiles * p.ksplit;
-  if (blocks > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-  hipLaunchKernelGGL(modconv_wgrad_f32, dim3((unsigned)blocks), dim3(256), lds, s, p);
-  int st = fmgan_check_launch();
-  if (st != FMGAN_OK) return st;
-  int fb = (cout * cin * 9 + 255) / 256;
-  if (fb > FMGAN_NUM_CU * 16) fb = FMGAN_NUM_CU * 16;
-  hipLaunchKernelGGL(modconv_wgrad_finish_f32, dim3(fb), dim3(256), 0, s, (const float*)workspace, gw, cout, cin,
-                     p.ksplit, scale);
-  return fmgan_check_launch();
-}
-
-extern "C" int fmgan_modconv_wgrad_f32(const float* go, const float* demod, const float* x, const float* style,
-                                       float* gw, int batch, int cin, int cout, int h, int w, float scale,
-                                       void* workspace, long long workspace_bytes, void* stream) {
-  if (w > 0 && w < 16) return FMGAN_EUNSUPPORTED;           // tiny layers: negligible FLOPs, the host keeps MIOpen's wgrad
-  return fmgan_modconv_wgrad_mode_f32(go, demod, x, style, gw, batch, cin, cout, h, w, 0, scale, workspace,
-                                      workspace_bytes, stream);
-}
-
-extern "C" int fmgan_torgb_f32(const float* in, const float* weight, const float* style, const float* bias,
-                               const float* skip, float* out, int batch, int cin, int cout, int hw, float scale,
-                               void* stream) {
-  if (batch < 0 || cin <= 0 || cout <= 0 || cout > 4 || hw <= 0) return FMGAN_EINVAL;
-  if (batch == 0) return FMGAN_OK;
-  if (!in || !weight || !style || !out) return FMGAN_EINVAL;
-  if (batch > 65535) return FMGAN_EOVERFLOW;
-  size_t lds = sizeof(float) * (size_t)cout * cin;
-  if (lds > 64 * 1024) return FMGAN_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  if (hw <= 128 * 128) {
-    if (lds < sizeof(float) * 4 * 4 * 64) lds = sizeof(float) * 4 * 4 * 64;
-    hipLaunchKernelGGL(torgb_small_f32, dim3((hw + 63) / 64, batch), dim3(256), lds, s, in, weight, style, bias, skip, out,
-                       cin, cout, hw, scale);
-    return fmgan_check_launch();
-  }
-  const bool vec = (hw & 3) == 0 && ((((uintptr_t)in) | ((uintptr_t)out) | ((uintptr_t)skip)) & 15) == 0;
-  const int n = vec ? hw / 4 : hw;
-  int gx = (n + 255) / 256;
-  const int cap = (FMGAN_NUM_CU * 16 + batch - 1) / batch;
-  if (gx > cap) gx = cap;
-  if (gx < 1) gx = 1;
-  if (vec) hipLaunchKernelGGL(torgb_f32<4>, dim3(gx, batch), dim3(256), lds, s, in, weight, style, bias, skip, out, cin, cout, hw, scale);
-  else hipLaunchKernelGGL(torgb_f32<1>, dim3(gx, batch), dim3(256), lds, s, in, weight, style, bias, skip, out, cin, cout, hw, scale);
-  return fmgan_check_launch();
-}
-
-// ------------------------------------------------------------------ ToRGB backward (HBM-bound, one pass over x)
-// out[b,c,p] = sum_i (scale * W[c,i] * s[b,i]) * x[b,i,p]  (stylegan2.py:389-404 without demodulation).  Its backward
-// needs  gx[b,i,p] = sum_c (scale * W[c,i] * s[b,i]) * go[b,c,p]  and  M[b,c,i] = sum_p go[b,c,p] * x[b,i,p]  (from which
-// gW[c,i] = scale * sum_b s[b,i] M[b,c,i] and gs[b,i] = scale * sum_c W[c,i] M[b,c,i] are [B,3,Cin] algebra).  The autograd
-// composite reads x twice and go many times through a grouped 1x1 convolution and its non-reproducible weight
-// gradient; here a block owns 16 input channels and a pixel range of one sample, reads its x planes ONCE, writes gx, and
-// keeps the 3 x 16 partial sums of M in registers over the whole range — one block-wide reduction at the end, one
-// partial row per (pixel split) that the caller sums in a fixed order (bit-reproducible).
-constexpr int TB_CT = 16;
-__global__ __launch_bounds__(256) void torgb_bwd_f32(const float* __restrict__ x, const float* __restrict__ go,
-                                                     const float* __restrict__ weight, const float* __restrict__ style,
-                                                     float* __restrict__ gx, float* __restrict__ mpart, int batch, int cin,
-                                                     int cout, int hw4, int chunk, float scale) {
-  __shared__ float wm[4][TB_CT];
-  __shared__ float red[4][4 * TB_CT];
-  const int b = blockIdx.z, i0 = blockIdx.y * TB_CT, split = blockIdx.x;
-  const int tid = threadIdx.x;
-  if (tid < 4 * TB_CT) {
-    const int c = tid / TB_CT, j = tid % TB_CT;
-    wm[c][j] = (c < cout && i0 + j < cin) ? scale * weight[c * cin + i0 + j] * style[(long long)b * cin + i0 + j] : 0.f;
-  }
-  __syncthreads();
-  float acc[4][TB_CT];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int j = 0; j < TB_CT; ++j) acc[c][j] = 0.f;
-  const f32x4* go4 = reinterpret_cast<const f32x4*>(go) + (long long)b * cout * hw4;
-  const f32x4* x4 = reinterpret_cast<const f32x4*>(x) + ((long long)b * cin + i0) * hw4;
-  f32x4* gx4 = reinterpret_cast<f32x4*>(gx) + ((long long)b * cin + i0) * hw4;
-  const int p_end = min(hw4, (split + 1) * chunk);
-  const int nj = min(TB_CT, cin - i0);
-  for (int p = split * chunk + tid; p < p_end; p += 256) {
-    f32x4 g[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      g[c] = c < cout ? go4[(long long)c * hw4 + p] : z;
-    }
-#pragma unroll
-    for (int j = 0; j < TB_CT; ++j) {
-      if (j >= nj) break;
-      const f32x4 xv = x4[(long long)j * hw4 + p];
-      f32x4 r = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float w = wm[c][j];
-        r.x = fmaf(w, g[c].x, r.x); r.y = fmaf(w, g[c].y, r.y); r.z = fmaf(w, g[c].z, r.z); r.w = fmaf(w, g[c].w, r.w);
-        acc[c][j] = fmaf(g[c].x, xv.x, fmaf(g[c].y, xv.y, fmaf(g[c].z, xv.z, fmaf(g[c].w, xv.w, acc[c][j]))));
-      }
-      gx4[(long long)j * hw4 + p] = r;
-    }
-  }
-  // block reduction of the 4 x 16 partials: wave butterfly, then the four waves in order
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int j = 0; j < TB_CT; ++j) {
-      float v = acc[c][j];
-#pragma unroll
-      for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-      if ((tid & 63) == 0) red[tid >> 6][c * TB_CT + j] = v;
-    }
-  __syncthreads();
-  if (tid < 4 * TB_CT) {
-    const int c = tid / TB_CT, j = tid % TB_CT;
-    if (c < cout && i0 + j < cin)
-      mpart[(((long long)split * batch + b) * cout + c) * cin + i0 + j] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-  }
-}
-
-// pixel splits of the backward launch (= rows of the partial array [splits, batch, cout, cin]); 0: shape not served
-extern "C" int fmgan_torgb_backward_splits(int batch, int cin, int hw) {
-  if (batch <= 0 || cin <= 0 || hw <= 0 || (hw & 3)) return 0;
-  const int hw4 = hw >> 2;
-  const long long others = (long long)batch * ((cin + TB_CT - 1) / TB_CT);
-  long long s = (8LL * FMGAN_NUM_CU + others - 1) / others;      // ~8 blocks per CU in the grid
-  const long long smax = (hw4 + 511) / 512;                       // at least two float4 per lane and split
-  if (s > smax) s = smax;
-  if (s < 1) s = 1;
-  if (s > 1024) s = 1024;
-  return (int)s;
-}
-
-extern "C" int fmgan_torgb_backward_f32(const float* x, const float* grad_out, const float* weight, const float* style,
-                                        float* grad_x, float* m_partial, int batch, int cin, int cout, int hw, float scale,
-                                        void* stream) {
-  if (batch < 0 || cin <= 0 || cout <= 0 || cout > 4 || hw <= 0) return FMGAN_EINVAL;
-  if (batch == 0) return FMGAN_OK;
-  if (!x || !grad_out || !weight || !style || !grad_x || !m_partial) return FMGAN_EINVAL;
-  const int splits = fmgan_torgb_backward_splits(batch, cin, hw);
-  if (splits == 0 || ((((uintptr_t)x) | ((uintptr_t)grad_out) | ((uintptr_t)grad_x)) & 15) != 0) return FMGAN_EUNSUPPORTED;
-  if (batch > 65535) return FMGAN_EOVERFLOW;
-  const int hw4 = hw >> 2, chunk = (hw4 + splits - 1) / splits;
-  hipLaunchKernelGGL(torgb_bwd_f32, dim3(splits, (cin + TB_CT - 1) / TB_CT, batch), dim3(256), 0, (hipStream_t)stream, x,
-                     grad_out, weight, style, grad_x, m_partial, batch, cin, cout, hw4, chunk, scale);
-  return fmgan_check_launch();
 }

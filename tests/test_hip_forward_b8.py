@@ -1,6 +1,6 @@
 """The headline configuration — batch 8, Generator(1024, 512, 8) — held to references of its own.
 
-Kernel dispatch depends on the batch (stylegan2.winograd_pays, the tile table of csrc/modconv.hip, the placement
+Kernel dispatch depends on the batch (stylegan2.winograd_pays, the tile table of csrc/modconv_fwd.hip, the placement
 workspaces of op/placement.py, the fused ToRGB of the last resolution), and the other Generator tests run at B = 1 or 2.
 
 Part 1, per layer: every synthesis layer of the B = 8 forward, RUN AS A MODULE (StyledConv.forward / fused_with_rgb / ToRGB
@@ -94,7 +94,7 @@ def _windows(res):
     origins — the four corners, the last rows in the interior of the width and the last columns in the interior of the
     height, an interior window off every power-of-two grid, and one window centred on (res/2, res/2).  res/2 is a multiple
     of 128 here, so that window crosses in BOTH directions a boundary of every tiling in play: the plain conv's 128- and
-    256-position tiles (32 wide x 4 or 8 tall, csrc/modconv.hip plan_segment / pick_tw_log2), the transposed conv's tiles
+    256-position tiles (32 wide x 4 or 8 tall, csrc/modconv_fwd.hip plan_segment / pick_tw_log2), the transposed conv's tiles
     (32 x 4 positions of one output phase = 64 x 8 output pixels), the bf16x3 kernel's tiles and the fused blur's
     64-column wave strips."""
     if res <= 128:

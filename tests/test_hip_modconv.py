@@ -589,7 +589,7 @@ def test_modconv_random_shapes_vs_c_oracle():
 
 
 # ---------------------------------------------------------------------------------------- index-range guard boundary
-# Shapes just INSIDE the guards of fmgan_modconv2d_f32 (csrc/modconv.hip: 32-bit per-tile input offsets
+# Shapes just INSIDE the guards of fmgan_modconv2d_f32 (csrc/modconv_fwd.hip: 32-bit per-tile input offsets
 # nb*cin*h*w < 2^31 elements; buffer-load staging only for tensors shorter than the parked voffset 0xFFFFFFF0 bytes)
 # must compute correctly; shapes just outside return FMGAN_EOVERFLOW without launching (tests/test_abi_host.py).
 # The tensors are 4-9 GB, so the check is the convolution's locality: output windows (all four corners, the last
@@ -748,26 +748,37 @@ for (r, cin, cout, mode, b) in [(64, 128, 128, 0, 4), (32, 64, 64, 0, 8), (32, 3
     dm = _native.modconv_demod(w, s, 1.0 / (cin * 9) ** 0.5)
     y = _native.modconv2d(x, wt, s, dm, mode)
     out[f'{r}/{cin}/{cout}/{mode}/{b}'] = hashlib.sha256(y.cpu().numpy().tobytes()).hexdigest()
+print('LIB ' + os.path.realpath(_native.LIB_PATH))
 print('DIGESTS ' + json.dumps(out))
 '''
 
 
 def test_lean_k_loop_equals_general_k_loop_bitwise(tmp_path):
-    """csrc/modconv.hip, PIPE 1: the lean K loop (taken when every chunk is complete and DMA-servable) against the general
-    loop (FMGAN_MC_DEBUG=8 forces it; the library reads the switch once, hence two processes): same DMA pieces, same
-    MFMA order -> identical output bits on every tile family."""
+    """csrc/modconv_fwd.hip, PIPE 1: the lean K loop (taken when every chunk is complete and DMA-servable) against the
+    general loop: same DMA pieces, same MFMA order -> identical output bits on every tile family.  Only the experiments
+    build of the library reads FMGAN_MC_DEBUG (=8 forces the general loop; read once, hence two processes), so the general
+    loop runs on tools/exp/lib/libfmgan_hip_exp.so and the lean loop on the product library."""
     import json
     import subprocess
     import sys
     script = tmp_path / 'loop_worker.py'
     script.write_text(_LOOP_WORKER)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = []
-    for dbg in ('0', '8'):
+    exp = os.path.join(root, 'tools', 'exp', 'lib', 'libfmgan_hip_exp.so')
+    if not os.path.exists(exp):
+        subprocess.check_call(['make', '-C', os.path.join(root, '3d-fm-gan_amd', 'csrc'), '-j16', 'experiments'])
+    res, libs = [], []
+    for dbg, lib in (('0', None), ('8', exp)):
         env = dict(os.environ, FMGAN_MC_DEBUG=dbg)
+        env.pop('FMGAN_LIB', None)
+        if lib:
+            env['FMGAN_LIB'] = lib
         pr = subprocess.run([sys.executable, str(script), root], env=env, capture_output=True, text=True, timeout=600)
         line = [ln for ln in pr.stdout.splitlines() if ln.startswith('DIGESTS ')]
-        assert pr.returncode == 0 and line, pr.stdout[-1000:] + pr.stderr[-3000:]
+        used = [ln for ln in pr.stdout.splitlines() if ln.startswith('LIB ')]
+        assert pr.returncode == 0 and line and used, pr.stdout[-1000:] + pr.stderr[-3000:]
         res.append(json.loads(line[0][8:]))
+        libs.append(used[0][4:])
+    assert libs[0] != libs[1] and libs[1] == os.path.realpath(exp), libs
     assert res[0] == res[1]
     assert len(res[0]) == 8

@@ -52,12 +52,12 @@ def _one(kernels, needle):
 
 # (mangled-name fragment, max registers for the quoted blocks per CU = 512 // blocks, spills allowed)
 MODCONV = [
-    ('modconv_mfma_f32ILi0ELi4ELi2ELi1ELi4ELb0ELi2ELi4ELi1E', 256, False),   # 128 x 256 plain tile: 2 blocks per CU
-    ('modconv_mfma_f32ILi0ELi2ELi2ELi1ELi4ELb0ELi3ELi4ELi1E', 170, False),   # 64 x 256 plain tile: 3
-    ('modconv_mfma_f32ILi0ELi1ELi2ELi1ELi4ELb0ELi4ELi4ELi1E', 128, False),   # 32 x 256 plain tile, 4-channel chunks: 4
-    ('modconv_mfma_f32ILi0ELi1ELi2ELi1ELi4ELb1ELi4ELi4ELi1E', 128, True),    # the same with the ToRGB epilogue (epilogue-only spills)
-    ('modconv_mfma_f32ILi1ELi2ELi1ELi1ELi4ELb0ELi2ELi8ELi1E', 256, False),   # transposed 64-channel tile: 2
-    ('modconv_mfma_f32ILi1ELi1ELi1ELi1ELi4ELb0ELi4ELi8ELi1E', 128, True),    # transposed 32-channel tile: 4 (7 dwords in the epilogue)
+    ('modconv_mfma_f32INS_18Plain128x256DmaKc4ELb0E', 256, False),   # 128 x 256 plain tile: 2 blocks per CU
+    ('modconv_mfma_f32INS_17Plain64x256DmaKc4ELb0E', 170, False),   # 64 x 256 plain tile: 3
+    ('modconv_mfma_f32INS_21Plain32x256DmaKc4R128ELb0E', 128, False),   # 32 x 256 plain tile, 4-channel chunks: 4
+    ('modconv_mfma_f32INS_21Plain32x256DmaKc4R128ELb1E', 128, True),    # the same with the ToRGB epilogue (epilogue-only spills)
+    ('modconv_mfma_f32INS_19Transposed64x128DmaELb0E', 256, False),   # transposed 64-channel tile: 2
+    ('modconv_mfma_f32INS_23Transposed32x128DmaR128ELb0E', 128, True),    # transposed 32-channel tile: 4 (7 dwords in the epilogue)
 ]
 
 
