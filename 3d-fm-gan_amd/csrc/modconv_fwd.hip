@@ -1049,11 +1049,17 @@ inline long long plan_segment(MCParams::Seg& sg, int batch, int BN) {
 constexpr size_t MC_LDS_LIMIT = 64 * 1024;   // dynamic LDS a launch may ask for without a function attribute
 constexpr size_t MC_LDS_MAX = 160 * 1024;    // LDS of a CU
 
+// What a planning call (fmgan_modconv2d_select) gets back in place of a launch: the tile that would have run.
+struct MCPick {
+  int cfg; char variant; int bm, bn, ksplit;
+};
+
 // Returns FMGAN_OK, an error, or +1 when this variant cannot serve the shape (PIPE 1 with an LDS image over the limit):
 // the caller then launches the register-pipeline variant.
 // FUSES_RGB: the tile's kernel with the ToRGB epilogue is built too, for launches with p.rgb_out.
+// plan_only: every decision of the launch, no HIP call — returns what the launch would return just before it launches.
 template <class Tile, bool FUSES_RGB>
-int launch_tile(MCParams& p, hipStream_t s) {
+int launch_tile(MCParams& p, hipStream_t s, bool plan_only) {
   constexpr int MODE = Tile::MODE, MINB = Tile::MINB, KC = Tile::KC, PIPE = Tile::PIPE, BM = Tile::BM, BN = Tile::BN;
   static_assert(!FUSES_RGB || MODE == 0, "the RGB epilogue belongs to the plain conv");
   if constexpr (!FUSES_RGB) { if (p.rgb_out) return FMGAN_EUNSUPPORTED; }
@@ -1110,7 +1116,7 @@ int launch_tile(MCParams& p, hipStream_t s) {
     p.lds_style_floats = (nbmax == 1 && p.cin_per_split <= 512) ? p.cin_per_split : 0;
     lds = sizeof(float) * (2 * (size_t)p.lds_buf_floats + 2 * BM + p.lds_style_floats);
     if (lds > (MINB == 1 ? MC_LDS_MAX : MC_LDS_LIMIT)) return 1;
-    if (lds > MC_LDS_LIMIT) {
+    if (lds > MC_LDS_LIMIT && !plan_only) {
       // one block per CU may use more than the 64 KB a launch gets by default (160 KB per CU on gfx950)
       static bool raised = false;
       if (!raised) {
@@ -1126,10 +1132,16 @@ int launch_tile(MCParams& p, hipStream_t s) {
   if constexpr (FUSES_RGB) {
     if (p.rgb_out) {
       if (p.o_tiles != 1 || p.ksplit != 1) return FMGAN_EUNSUPPORTED;
+      // The RGB epilogue reads ONE sample's wmod per block.  rgb_fusable() vouches for that on the 128-position planning
+      // model; a 256-position tile packs two samples of a 4-row image (TW = 32; 8 rows at TW = 16, ...) into one tile
+      // where the 128-position tile holds one: such a launch goes to the register tile instead.
+      if (nbmax > 1) return PIPE == 1 ? 1 : FMGAN_EUNSUPPORTED;
+      if (plan_only) return FMGAN_OK;
       hipLaunchKernelGGL((modconv_mfma_f32<Tile, true>), dim3((unsigned)blocks, 1), dim3(256), lds, s, p);
       return fmgan_check_launch();
     }
   }
+  if (plan_only) return FMGAN_OK;
   hipLaunchKernelGGL((modconv_mfma_f32<Tile, false>), dim3((unsigned)blocks, p.ksplit), dim3(256), lds, s, p);
   return fmgan_check_launch();
 }
@@ -1156,7 +1168,7 @@ struct TileEntry {
   char variant;
   int BM, BN;              // output channels x positions of the launched block
   bool fuses_rgb;          // takes launches with the ToRGB epilogue (p.rgb_out)
-  int (*launch)(MCParams&, hipStream_t);
+  int (*launch)(MCParams&, hipStream_t, bool plan_only);
 };
 template <class Tile, bool FUSES_RGB = false>
 constexpr TileEntry tile_entry(int cfg, char variant) {
@@ -1266,7 +1278,8 @@ inline long long blocks_with(const MCParams& p, int BM, int BN) {
   return blocks * ((p.cout + BM - 1) / BM);
 }
 
-inline int launch_any(int mode, int cfg, MCParams& p, hipStream_t s) {
+// pick: null = launch; otherwise plan only (no HIP call) and report the tile the launch would have run
+inline int launch_any(int mode, int cfg, MCParams& p, hipStream_t s, MCPick* pick = nullptr) {
   char v = mc_variant(mode, cfg);
   // the large-tile variants need enough tiles to fill the chip twice over (2 blocks per CU); smaller launches keep
   // the 128-position tiles (and their split-K plan)
@@ -1284,10 +1297,13 @@ inline int launch_any(int mode, int cfg, MCParams& p, hipStream_t s) {
     if (small) v = 'B';
   }
   int st = 1;
-  if (v != 'A' && (e = find_tile(mode, cfg, v)) != nullptr) st = e->launch(p, s);
-  if (st != 1) return st;
-  e = find_tile(mode, cfg, 'A');                        // the register pipeline serves what the LDS-DMA tile could not
-  return e ? e->launch(p, s) : FMGAN_EUNSUPPORTED;
+  if (v != 'A' && (e = find_tile(mode, cfg, v)) != nullptr) st = e->launch(p, s, pick != nullptr);
+  if (st == 1) {
+    e = find_tile(mode, cfg, 'A');                      // the register pipeline serves what the LDS-DMA tile could not
+    st = e ? e->launch(p, s, pick != nullptr) : FMGAN_EUNSUPPORTED;
+  }
+  if (pick && st == FMGAN_OK) *pick = {cfg, e->variant, e->BM, e->BN, p.ksplit};
+  return st;
 }
 
 // Blocks of one launch (all segments), for a given tile configuration.
@@ -1370,7 +1386,8 @@ int modconv2d_impl(const float* in, const float* wt, const float* style, const f
                    float* out, int batch, int cin, int cout, int h, int w, int mode,
                    const float* noise, const float* noise_weight, const float* bias, int noise_batch,
                    int fuse_act, float alpha, float act_scale, long long out_plane_stride,
-                   int out_row_stride, void* workspace, long long workspace_bytes, void* stream, const RgbArgs* rgb) {
+                   int out_row_stride, void* workspace, long long workspace_bytes, void* stream, const RgbArgs* rgb,
+                   MCPick* pick = nullptr) {
   if (batch < 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return FMGAN_EINVAL;
   if (mode < 0 || mode > 2) return FMGAN_EUNSUPPORTED;
   if (mode != 0 && fuse_act) return FMGAN_EUNSUPPORTED;  // the blur sits between conv and activation
@@ -1380,8 +1397,10 @@ int modconv2d_impl(const float* in, const float* wt, const float* style, const f
     if (!rgb_fusable(batch, cin, cout, h, w)) return FMGAN_EUNSUPPORTED;
   }
   if (batch == 0) return FMGAN_OK;
-  if (!in || !wt || !style || (!out && !rgb)) return FMGAN_EINVAL;
-  if (rgb && (!rgb->wmod || !rgb->out)) return FMGAN_EINVAL;
+  if (!pick) {                                             // (a planning call has no tensors)
+    if (!in || !wt || !style || (!out && !rgb)) return FMGAN_EINVAL;
+    if (rgb && (!rgb->wmod || !rgb->out)) return FMGAN_EINVAL;
+  }
   if (fuse_act && noise && noise_batch != 1 && noise_batch != batch) return FMGAN_EINVAL;
   MCParams p{};
 #ifdef FMGAN_EXPERIMENTS
@@ -1435,8 +1454,8 @@ int modconv2d_impl(const float* in, const float* wt, const float* style, const f
     p.seg[0] = {0, 0, p.oh, p.ow};      // mode 0: oh = h; mode 2: the output grid
     p.nseg = 1;
   }
-  int st = launch_any(mode, cfg, p, s);
-  if (st != FMGAN_OK) return st;
+  int st = launch_any(mode, cfg, p, s, pick);
+  if (st != FMGAN_OK || pick) return st;
   if (p.ksplit > 1) {
     const long long total = (long long)batch * cout * p.oh * p.ow;
     long long blocks = (total + 255) / 256;
@@ -1472,4 +1491,38 @@ extern "C" int fmgan_modconv2d_rgb_f32(const float* in, const float* wt, const f
   const RgbArgs rgb{rgb_wmod, rgb_bias, rgb_skip, rgb_out, rgb_channels};
   return modconv2d_impl(in, wt, style, demod, out, batch, cin, cout, h, w, 0, noise, noise_weight, bias, noise_batch,
                         fuse_act, alpha, act_scale, 0, 0, nullptr, 0, stream, &rgb);
+}
+
+// The planning half of fmgan_modconv2d_f32 / fmgan_modconv2d_rgb_f32 alone: the same modconv2d_impl -> launch_any ->
+// launch_tile walk with plan_only set, so the rules are stated once.  The wide patch (and with it the LDS image a DMA tile
+// is judged by) depends on the input's alignment: the plan assumes a 16-byte-aligned input, the larger image — a tile that
+// takes the aligned tensor takes the misaligned one too.
+extern "C" int fmgan_modconv2d_select(int batch, int cin, int cout, int h, int w, int mode, int rgb, int has_workspace,
+                                      int* cfg, int* variant, int* bm, int* bn, int* ksplit) {
+  alignas(16) static float aligned[4];
+  MCPick pick{-1, 0, 0, 0, 0};
+  const RgbArgs ra{aligned, nullptr, nullptr, aligned, 3};
+  const int st = (rgb && mode != 0) ? FMGAN_EUNSUPPORTED :   // the fused entry point is the plain conv's
+                 modconv2d_impl(aligned, nullptr, nullptr, nullptr, aligned, batch, cin, cout, h, w, mode,
+                                nullptr, nullptr, nullptr, 1, rgb ? 1 : 0, 0.2f, 1.f, 0, 0,
+                                has_workspace && !rgb ? aligned : nullptr, has_workspace && !rgb ? (1LL << 62) : 0,
+                                nullptr, rgb ? &ra : nullptr, &pick);
+  if (cfg) *cfg = pick.cfg;
+  if (variant) *variant = pick.variant;
+  if (bm) *bm = pick.bm;
+  if (bn) *bn = pick.bn;
+  if (ksplit) *ksplit = pick.ksplit;
+  return st;
+}
+
+extern "C" int fmgan_modconv2d_tiles(int* out, int cap) {
+  int n = 0;
+  for (const TileEntry& e : MC_TILES) {
+    if (out && n < cap) {
+      int* o = out + 6 * n;
+      o[0] = e.mode; o[1] = e.cfg; o[2] = e.variant; o[3] = e.BM; o[4] = e.BN; o[5] = e.fuses_rgb ? 1 : 0;
+    }
+    ++n;
+  }
+  return n;
 }

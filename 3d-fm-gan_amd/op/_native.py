@@ -80,6 +80,8 @@ def lib():
     _sig(L.fmgan_modconv2d_bf16x3_supported, [i] * 6)
     _sig(L.fmgan_modconv2d_bf16x3, [vp] * 5 + [i] * 6 + [vp] * 3 + [i, i, f, f, ll, i, vp])
     _sig(L.fmgan_modconv2d_rgb_fusable, [i] * 5)
+    _sig(L.fmgan_modconv2d_select, [i] * 8 + [ctypes.POINTER(i)] * 5)
+    _sig(L.fmgan_modconv2d_tiles, [ctypes.POINTER(i), i])
     _sig(L.fmgan_torgb_weight_mod_f32, [vp] * 3 + [i] * 3 + [f, vp])
     _sig(L.fmgan_modconv2d_rgb_f32, [vp] * 5 + [i] * 5 + [vp] * 3 + [i, i, f, f] + [vp] * 4 + [i, vp])
     _sig(L.fmgan_modconv_wgrad_workspace_bytes, [i] * 5, ll)
@@ -654,6 +656,25 @@ def modconv2d(x, wt, style, demod, mode, noise=None, noise_weight=None, bias=Non
 
 def modconv2d_rgb_fusable(batch, cin, cout, h, w):
     return bool(lib().fmgan_modconv2d_rgb_fusable(int(batch), int(cin), int(cout), int(h), int(w)))
+
+
+def modconv2d_select(batch, cin, cout, h, w, mode, rgb=False, has_workspace=True):
+    """(cfg, variant letter, BM, BN, ksplit): the tile and split-K factor modconv2d (rgb: modconv2d_rgb) launches for this
+    shape — host logic, no device needed.  Raises as the launch would for arguments it refuses."""
+    v = [ctypes.c_int() for _ in range(5)]
+    check(lib().fmgan_modconv2d_select(int(batch), int(cin), int(cout), int(h), int(w), int(mode), int(bool(rgb)),
+                                       int(bool(has_workspace)), *[ctypes.byref(c) for c in v]), 'modconv2d_select')
+    cfg, variant, bm, bn, ks = (c.value for c in v)
+    return cfg, chr(variant) if variant else '', bm, bn, ks
+
+
+def modconv2d_tiles():
+    """Tiles of this build of the library: [(mode, cfg, variant letter, BM, BN, fuses_rgb), ...] in table order."""
+    n = lib().fmgan_modconv2d_tiles(None, 0)
+    buf = (ctypes.c_int * (6 * n))()
+    lib().fmgan_modconv2d_tiles(buf, n)
+    return [(buf[6 * k], buf[6 * k + 1], chr(buf[6 * k + 2]), buf[6 * k + 3], buf[6 * k + 4], bool(buf[6 * k + 5]))
+            for k in range(n)]
 
 
 def modconv2d_rgb(x, wt, style, demod, noise, noise_weight, bias, alpha, act_scale, rgb_weight, rgb_style, rgb_bias,

@@ -391,6 +391,25 @@ int fmgan_modconv2d_rgb_f32(const float *in, const float *wt, const float *style
                             const float *rgb_skip, float *rgb_out, int rgb_channels, void *stream);
 
 /*
+ * Which tile, which split (pure host logic, no HIP call — as fmgan_upfirdn2d_select): the plan of fmgan_modconv2d_f32
+ * (rgb == 0) or fmgan_modconv2d_rgb_f32 (rgb != 0; mode must be 0) for these arguments, made by the launch's own planning
+ * code with the launch left out.  has_workspace: the caller passes the fmgan_modconv2d_workspace_bytes() buffer (without
+ * it the launch runs unsplit).  The plan is that of a 16-byte-aligned input, whose halo patch is the wider one: a misaligned
+ * input takes the same tile, or the LDS-DMA tile where the aligned one's LDS image was too large and 'A' is reported.
+ *   *cfg     output-channel class of the shape: 0 = 128, 1 = 64, 2 = 32 channels per block
+ *   *variant the tile's letter in its (mode, cfg) row of the tile table: 'A' = register prefetch, 'B'..'E' = LDS-DMA
+ *            (after the fall-back to 'A' when the LDS-DMA tile declines the shape)
+ *   *bm, *bn output channels x positions of the launched block;  *ksplit blocks along the input channels (1 = no split)
+ * Any of the five may be NULL.  Returns the status the launch returns before it launches (FMGAN_OK: it would launch);
+ * on an error, and for batch == 0, *cfg is -1 and the others 0.
+ * fmgan_modconv2d_tiles: the tiles of this build, six ints each (mode, cfg, variant, BM, BN, fuses_rgb: takes launches
+ * of fmgan_modconv2d_rgb_f32); writes the first `cap` tiles to out (may be NULL) and returns the number of tiles.
+ */
+int fmgan_modconv2d_select(int batch, int cin, int cout, int h, int w, int mode, int rgb, int has_workspace,
+                           int *cfg, int *variant, int *bm, int *bn, int *ksplit);
+int fmgan_modconv2d_tiles(int *out, int cap);
+
+/*
  * Weight gradient of the plain (mode 0) modulated conv on the MFMA units:
  *   gw[o,i,ky,kx] = scale * sum_{b,y,x} (demod[b,o] * go[b,o,y,x]) * (style[b,i] * x[b,i,y+ky-1,x+kx-1])
  * (the conv part of d loss / d weight; the demodulation chain-rule term is [B,Cout]x[Cout,Cin] algebra on the host).

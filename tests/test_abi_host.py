@@ -381,3 +381,82 @@ def test_fused_blur_selection_declines_firs_wider_than_four_taps():
         _, off, ps, rs = _native.aligned_rows_shape(b, c, h, h, 2)
         assert L.fmgan_blur_noise_bias_act_select(None, None, None, b, c, h, h, ps, rs, 5, 5, 2, 1, 2, 1) == -2
         assert not _native.blur_noise_bias_act_serves(b, c, h, h, ps, rs, (5, 5), (2, 1))
+
+
+# ------------------------------------------------------------------------ fmgan_modconv2d_select / fmgan_modconv2d_tiles
+def test_modconv_select_and_tiles_are_host_logic():
+    """Which tile, which split: both answers come without a device, invalid arguments return the launch's status, the tile
+    table lists one tile per (mode, cfg, letter) with the channel extent of its class, and the split reported is the one
+    fmgan_modconv2d_workspace_bytes sizes the workspace for."""
+    from op import _native
+    L = _lib()
+    tiles = _native.modconv2d_tiles()
+    assert L.fmgan_modconv2d_tiles(None, 0) == len(tiles) == 16
+    assert len({t[:3] for t in tiles}) == len(tiles)
+    for mode, cfg, variant, bm, bn, rgb in tiles:
+        assert mode in (0, 1, 2) and bm == (128, 64, 32)[cfg] and bn in (128, 256) and variant in 'ABCDE'
+        assert not rgb or mode == 0                                   # the RGB epilogue belongs to the plain conv
+        assert (mode, cfg, 'A', bm, 128) in {t[:5] for t in tiles}   # every class has its register tile, the fall-back
+    few = (ctypes.c_int * 12)()
+    assert L.fmgan_modconv2d_tiles(few, 2) == 16 and tuple(few[:6]) == (0, 0, ord('C'), 128, 256, 0)
+
+    def status(*args):
+        return L.fmgan_modconv2d_select(*args, None, None, None, None, None)
+    assert status(1, 8, 8, 4, 4, 3, 0, 1) == -2                      # as fmgan_modconv2d_f32: unknown mode
+    assert status(1, 8, 8, 0, 4, 0, 0, 1) == -1
+    assert status(1, 0, 8, 4, 4, 0, 0, 1) == -1
+    assert status(1, 8, 8, 2, 2, 2, 0, 1) == -1                      # stride-2 conv of an image smaller than its window
+    assert status(1, 8, 8, 16384, 16384, 0, 0, 1) == -4              # 32-bit per-tile offsets
+    assert status(1, 256, 256, 128, 128, 0, 1, 1) == -2              # as fmgan_modconv2d_rgb_f32: not fusable
+    assert status(8, 32, 32, 64, 64, 1, 1, 1) == -2                  # the fused launch is the plain conv's
+    assert status(0, 8, 8, 4, 4, 0, 0, 1) == 0                       # empty batch: nothing to launch
+    with pytest.raises(RuntimeError):
+        _native.modconv2d_select(1, 8, 8, 4, 4, 3)
+    assert _native.modconv2d_select(0, 8, 8, 4, 4, 0) == (-1, '', 0, 0, 0)
+    by_key = {t[:3]: t for t in tiles}
+    for mode in (0, 1, 2):
+        for b, cin, cout, h, w in ((1, 512, 512, 5, 5), (8, 512, 512, 16, 16), (2, 64, 200, 33, 31), (4, 128, 64, 32, 32),
+                                   (8, 32, 32, 1024, 1024), (3, 20, 40, 257, 34), (2, 256, 64, 129, 131), (1, 8, 3, 7, 9)):
+            cfg, variant, bm, bn, ks = _native.modconv2d_select(b, cin, cout, h, w, mode)
+            assert by_key[(mode, cfg, variant)][3:5] == (bm, bn)
+            oh, ow = (2 * h + 1, 2 * w + 1) if mode == 1 else (((h - 3) // 2 + 1, (w - 3) // 2 + 1) if mode == 2 else (h, w))
+            need = L.fmgan_modconv2d_workspace_bytes(b, cin, cout, h, w, mode)
+            assert need == (ks * b * cout * oh * ow * 4 if ks > 1 else 0), (mode, b, cin, cout, h, w, ks, need)
+            assert _native.modconv2d_select(b, cin, cout, h, w, mode, has_workspace=False)[4] == 1   # no workspace: unsplit
+    assert any(_native.modconv2d_select(b, 512, 512, 8, 8, 0)[4] > 1 for b in (1, 8))
+
+
+def test_modconv_select_headline_forward_dispatch():
+    """The documented dispatch of the batch-8 1024^2 forward (csrc/modconv_fwd.hip, the comment block above MC_TILES and
+    launch_any; network widths 512 / 256 / 128 / 64 / 32 at 64^2 .. 1024^2), derived from those comments, not recorded:
+    Cout >= 96 -> the 128 x 256 tile 'C', Cout >= 48 -> 64 x 256 'C', below -> 32 x 256 'E', all unsplit; a fused-ToRGB
+    launch of the 128- and 64-channel classes never takes 'C' but the register tile 'A', the 32-channel class keeps 'E';
+    at batch 1 the 64^2 .. 256^2 layers have too few 256-position tiles to fill the chip twice and take 'B'."""
+    from op import _native
+    widths = {64: 512, 128: 256, 256: 128, 512: 64, 1024: 32}
+
+    def sel(b, r, rgb=False):
+        c = widths[r]
+        return _native.modconv2d_select(b, c, c, r, r, 0, rgb=rgb)
+    for r in (64, 128, 256):
+        assert sel(8, r) == (0, 'C', 128, 256, 1), r
+        assert sel(1, r)[:4] == (0, 'B', 128, 128), r
+    assert sel(8, 512) == (1, 'C', 64, 256, 1)
+    assert sel(8, 1024) == (2, 'E', 32, 256, 1) and sel(8, 1024, rgb=True) == (2, 'E', 32, 256, 1)
+    assert sel(8, 256, rgb=True) == (0, 'A', 128, 128, 1) and sel(8, 512, rgb=True) == (1, 'A', 64, 128, 1)
+    for r in (64, 128):                                             # two and more channel tiles: not fusable
+        assert not _native.modconv2d_rgb_fusable(8, widths[r], widths[r], r, r)
+        with pytest.raises(RuntimeError):
+            sel(8, r, rgb=True)
+
+
+def test_modconv_select_keeps_fused_torgb_on_single_sample_tiles():
+    """fmgan_modconv2d_rgb_fusable answers on the 128-position planning model; a 256-position tile packs two samples of a
+    4-row image (TW = 32: 8 rows per tile) or an 8-row, 16-wide image into one tile, and the RGB epilogue reads one sample's
+    weights per block: such a fused launch takes the register tile, the unfused one keeps 'E'."""
+    from op import _native
+    for shape in ((16, 8, 32, 4, 2048), (1024, 8, 32, 8, 16)):
+        assert _native.modconv2d_rgb_fusable(*shape)
+        assert _native.modconv2d_select(*shape, 0) == (2, 'E', 32, 256, 1)
+        assert _native.modconv2d_select(*shape, 0, rgb=True) == (2, 'A', 32, 128, 1)
+    assert _native.modconv2d_select(16, 8, 32, 8, 2048, 0, rgb=True) == (2, 'E', 32, 256, 1)     # 8 rows fill the tile

@@ -85,6 +85,11 @@ def test_modconv_kernel_vs_c_oracle(cfg, demod):
 def test_conv_with_torgb_in_epilogue_vs_c_oracle(cfg):
     """fmgan_modconv2d_rgb_f32: StyledConv (conv + noise + bias + lrelu) and the following ToRGB (+ bias + skip) in one
     kernel vs the two C-oracle steps; also against this repo's own two-kernel path."""
+    check_conv_with_torgb_in_epilogue(cfg)
+
+
+def check_conv_with_torgb_in_epilogue(cfg):
+    """Body of test_conv_with_torgb_in_epilogue_vs_c_oracle (shared with tests/test_hip_modconv_tiles.py)."""
     from op import _native
     from oracle import c_oracle
     b, cin, cout, h, w, keep = cfg
@@ -737,18 +742,27 @@ import torch
 from op import _native
 d = torch.device('cuda', 0)
 out = {}
-# (res, cin, cout, mode, batch): lean-loop shapes of every LDS-DMA tile, a ragged-channel shape and a tiny one (general loop both times)
-for (r, cin, cout, mode, b) in [(64, 128, 128, 0, 4), (32, 64, 64, 0, 8), (32, 32, 32, 0, 8), (32, 128, 64, 1, 4),
-                                (64, 64, 32, 1, 2), (33, 40, 72, 0, 3), (17, 24, 48, 1, 2), (8, 64, 64, 0, 2)]:
+sel = {}
+# (h, w, cin, cout, mode, batch): lean-loop shapes of every LDS-DMA tile (whole 4- and 8-channel chunks, whole channel tiles),
+# a ragged-channel shape and a tiny one (general loop both times)
+for (r, rw, cin, cout, mode, b) in [(64, 64, 128, 128, 0, 4), (32, 32, 64, 64, 0, 8), (32, 32, 32, 32, 0, 8), (32, 32, 128, 64, 1, 4),
+                                    (64, 64, 64, 32, 1, 2), (33, 33, 40, 72, 0, 3), (17, 17, 24, 48, 1, 2), (8, 8, 64, 64, 0, 2),
+                                    # the 256-position default tiles: plain C of the 128- and 64-channel classes, E
+                                    (512, 64, 16, 128, 0, 4), (512, 64, 16, 64, 0, 4), (257, 36, 16, 32, 0, 8),
+                                    # the transposed 64-channel DMA tile ((32, 32, 128, 64, 1, 4) above falls back to 'A':
+                                    # its thin segments' patches put the LDS image over the limit)
+                                    (33, 34, 32, 64, 1, 3)]:
     g = torch.Generator(device=d).manual_seed(r * 7 + mode)
-    x = torch.randn(b, cin, r, r, device=d, generator=g)
+    x = torch.randn(b, cin, r, rw, device=d, generator=g)
     w = torch.randn(cout, cin, 3, 3, device=d, generator=g)
     s = torch.randn(b, cin, device=d, generator=g) * 0.5 + 1
     wt = _native.modconv_weight_prep(w, 1.0 / (cin * 9) ** 0.5)
     dm = _native.modconv_demod(w, s, 1.0 / (cin * 9) ** 0.5)
     y = _native.modconv2d(x, wt, s, dm, mode)
-    out[f'{r}/{cin}/{cout}/{mode}/{b}'] = hashlib.sha256(y.cpu().numpy().tobytes()).hexdigest()
+    out[f'{r}x{rw}/{cin}/{cout}/{mode}/{b}'] = hashlib.sha256(y.cpu().numpy().tobytes()).hexdigest()
+    sel[f'{r}x{rw}/{cin}/{cout}/{mode}/{b}'] = [mode] + list(_native.modconv2d_select(b, cin, cout, r, rw, mode))
 print('LIB ' + os.path.realpath(_native.LIB_PATH))
+print('SELECT ' + json.dumps(sel))
 print('DIGESTS ' + json.dumps(out))
 '''
 
@@ -757,7 +771,10 @@ def test_lean_k_loop_equals_general_k_loop_bitwise(tmp_path):
     """csrc/modconv_fwd.hip, PIPE 1: the lean K loop (taken when every chunk is complete and DMA-servable) against the
     general loop: same DMA pieces, same MFMA order -> identical output bits on every tile family.  Only the experiments
     build of the library reads FMGAN_MC_DEBUG (=8 forces the general loop; read once, hence two processes), so the general
-    loop runs on tools/exp/lib/libfmgan_hip_exp.so and the lean loop on the product library."""
+    loop runs on tools/exp/lib/libfmgan_hip_exp.so and the lean loop on the product library.  The worker also reports
+    fmgan_modconv2d_select for every shape: both libraries must have run the same tiles, and the shapes must reach all eight
+    LDS-DMA tiles of the product table (plain C / B of the 128- and 64-channel classes, plain E / B of the 32-channel class,
+    transposed B and D) — each with a shape of whole chunks and whole channel tiles, the lean loop's."""
     import json
     import subprocess
     import sys
@@ -767,7 +784,7 @@ def test_lean_k_loop_equals_general_k_loop_bitwise(tmp_path):
     exp = os.path.join(root, 'tools', 'exp', 'lib', 'libfmgan_hip_exp.so')
     if not os.path.exists(exp):
         subprocess.check_call(['make', '-C', os.path.join(root, '3d-fm-gan_amd', 'csrc'), '-j16', 'experiments'])
-    res, libs = [], []
+    res, libs, sels = [], [], []
     for dbg, lib in (('0', None), ('8', exp)):
         env = dict(os.environ, FMGAN_MC_DEBUG=dbg)
         env.pop('FMGAN_LIB', None)
@@ -776,9 +793,18 @@ def test_lean_k_loop_equals_general_k_loop_bitwise(tmp_path):
         pr = subprocess.run([sys.executable, str(script), root], env=env, capture_output=True, text=True, timeout=600)
         line = [ln for ln in pr.stdout.splitlines() if ln.startswith('DIGESTS ')]
         used = [ln for ln in pr.stdout.splitlines() if ln.startswith('LIB ')]
-        assert pr.returncode == 0 and line and used, pr.stdout[-1000:] + pr.stderr[-3000:]
+        picked = [ln for ln in pr.stdout.splitlines() if ln.startswith('SELECT ')]
+        assert pr.returncode == 0 and line and used and picked, pr.stdout[-1000:] + pr.stderr[-3000:]
         res.append(json.loads(line[0][8:]))
         libs.append(used[0][4:])
+        sels.append(json.loads(picked[0][7:]))
     assert libs[0] != libs[1] and libs[1] == os.path.realpath(exp), libs
+    # both libraries ran the same tile on every shape, and the shapes reach all eight LDS-DMA tiles of the product table
+    assert sels[0] == sels[1], (sels[0], sels[1])
+    reached = {(m, cfg, v) for (m, cfg, v, _bm, _bn, _ks) in sels[0].values()}
+    dma = {(0, 0, 'C'), (0, 0, 'B'), (0, 1, 'C'), (0, 1, 'B'), (0, 2, 'E'), (0, 2, 'B'), (1, 1, 'B'), (1, 2, 'D')}
+    from op import _native
+    assert dma == {(m, cfg, v) for (m, cfg, v, _bm, _bn, _rgb) in _native.modconv2d_tiles() if v != 'A'}
+    assert dma <= reached, sorted(dma - reached)
     assert res[0] == res[1]
-    assert len(res[0]) == 8
+    assert len(res[0]) == 12 and len(sels[0]) == 12
