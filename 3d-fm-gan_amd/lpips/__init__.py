@@ -11,10 +11,23 @@ is available offline, and the reference's module itself is not imp
 skimage, IPython).  So this module is **load, not a parity row**: same layers, same tensor shapes, same arithmetic per
 layer, random initialisation unless `load_state_dict` is given real weights (state_dict names follow the reference:
 `net.slice1.0.weight` ... `lin4.model.1.weight`, `scaling_layer.shift/scale`).  It is frozen and in eval mode in the
-training step, so only data gradients flow through it.  Host PyTorch-ROCm (MIOpen convs); no custom kernel.
+training step, so only data gradients flow through it.
+
+The VGG trunk is host PyTorch-ROCm (MIOpen convs).  The distance behind each tap (normalise, difference, square, 1x1
+conv, spatial mean) runs on the kernel of op/lpips_distance.py (csrc/lpips_distance.hip) when the module is in eval mode
+(dropout inactive) and the features are float32, NHWC-dense CUDA tensors with autocast off; otherwise (CPU tensors,
+bf16 features of the autocast leg, NCHW features, training mode) it is the aten composite below, as before.  Switch:
+`lpips.FUSED` (environment FMGAN_LPIPS_FUSED, default 1).
 """
+import os
+
 import torch
 from torch import nn
+
+from op.lpips_distance import lpips_distance, lpips_distance_serves
+
+# Per-tap distance on the HIP kernel where it serves (DESIGN 3.4c); False keeps the aten composite everywhere.
+FUSED = os.environ.get('FMGAN_LPIPS_FUSED', '1') != '0'
 
 # VGG16 `features` indices -> (slice, [(index, cin, cout) convs]); a MaxPool2d(2) opens slices 2..5
 _VGG_SLICES = (
@@ -88,11 +101,19 @@ class PNetLin(nn.Module):
             setattr(self, f'lin{i}', NetLinLayer(c, use_dropout=use_dropout))
 
     def forward(self, in0, in1):
-        f0, f1 = self.net(self.scaling_layer(in0)), self.net(self.scaling_layer(in1))
+        # MIOpen's convolutions are not bit-reproducible from call to call (two trunk passes over the same values differ
+        # in the last bit at every tap), so the distance of an image to itself is exactly 0 only if its features are
+        # computed once.
+        f0 = self.net(self.scaling_layer(in0))
+        f1 = f0 if in1 is in0 else self.net(self.scaling_layer(in1))
         val = None
         for i in range(len(self.chns)):
-            diff = (normalize_tensor(f0[i]) - normalize_tensor(f1[i])) ** 2
-            r = getattr(self, f'lin{i}').model(diff).mean([2, 3], keepdim=True)
+            lin = getattr(self, f'lin{i}').model
+            if FUSED and not self.training and lpips_distance_serves(f0[i], f1[i], lin[-1].weight):
+                r = lpips_distance(f0[i], f1[i], lin[-1].weight)
+            else:
+                diff = (normalize_tensor(f0[i]) - normalize_tensor(f1[i])) ** 2
+                r = lin(diff).mean([2, 3], keepdim=True)
             val = r if val is None else val + r
         return val
 

@@ -61,6 +61,9 @@ def lib():
     _sig(L.fmgan_face_region_loss_f32, [vp] * 3 + [i, i, ll, vp])
     _sig(L.fmgan_face_region_backward_f32, [vp] * 4 + [i, i, ll, vp])
     _sig(L.fmgan_render_mask_f32, [vp] * 2 + [i, i, ll, vp])
+    _sig(L.fmgan_lpips_distance_blocks, [i] * 3)
+    _sig(L.fmgan_lpips_distance_f32, [vp] * 4 + [i, i, i, f, vp])
+    _sig(L.fmgan_lpips_distance_backward_f32, [vp] * 6 + [i, i, i, f, vp])
     _sig(L.fmgan_modconv_demod_f32, [vp] * 3 + [i] * 4 + [f, f, vp])
     _sig(L.fmgan_modconv_wsq_f32, [vp] * 2 + [i] * 3 + [vp])
     _sig(L.fmgan_modconv_demod_wsq_f32, [vp] * 3 + [i] * 3 + [f, f, vp])
@@ -412,6 +415,77 @@ def render_mask(r):
         check(lib().fmgan_render_mask_f32(fp(r), fp(mask), b, c, hw, stream), 'render_mask')
         _observer.end(tok)
     return mask
+
+
+def nhwc_dense(t):
+    """Is the [N, C, H, W] tensor stored as one dense [N, H, W, C] block (channels_last with nothing between pixels)?"""
+    return t.ndim == 4 and t.permute(0, 2, 3, 1).is_contiguous()
+
+
+def _lpips_distance_shape(f0, f1, w):
+    """(N, C, H*W) after the checks shared by the two LPIPS-distance entry points: shapes and layout first (ValueError),
+    then device and dtype (RuntimeError from fp(), no fallback)."""
+    if f0.ndim != 4 or tuple(f0.shape) != tuple(f1.shape) or w.numel() != f0.shape[1]:
+        raise ValueError(f'lpips_distance: features {tuple(f0.shape)} and {tuple(f1.shape)}, weight {tuple(w.shape)}: '
+                         f'expected two [N, C, H, W] tensors of one shape and C weights')
+    if not (nhwc_dense(f0) and nhwc_dense(f1)):
+        raise ValueError('lpips_distance: features must be NHWC-dense (channels_last storage); the kernel reads a '
+                         'pixel\'s channel vector as one contiguous run')
+    n, c, h, wd = f0.shape
+    return n, c, h * wd
+
+
+def lpips_distance(f0, f1, w, eps=1e-10):
+    """LPIPS distance of one tap: f0, f1 [N, C, H, W] f32, NHWC-dense; w the C weights of the 1x1 conv (any shape)
+    -> d [N] = mean_p sum_c w_c (u0 - u1)^2 with u = f / (sqrt(sum_c f^2) + eps).  Fixed-order per-block partials from
+    the kernel, summed here: bit-reproducible.  None when the kernel does not serve the shape (C not 64 / 128 / 256 /
+    512, pointers not 16-byte aligned): the caller then evaluates the composite."""
+    n, c, hw = _lpips_distance_shape(f0, f1, w)
+    p0, p1, pw = fp(f0), fp(f1), fp(w)
+    if n == 0:
+        return torch.zeros((0,), dtype=torch.float32, device=f0.device)
+    blocks = lib().fmgan_lpips_distance_blocks(n, c, hw)
+    if blocks <= 0:
+        return None
+    if not w.is_contiguous():
+        w = w.contiguous()
+        pw = fp(w)
+    with on_device(f0) as stream:
+        partial = torch.empty((n, blocks), dtype=torch.float32, device=f0.device)
+        tok = _observer.begin('lpips_distance', (n, c, hw, 0))
+        st = lib().fmgan_lpips_distance_f32(p0, p1, pw, fp(partial), n, c, hw, float(eps), stream)
+        _observer.end(tok)
+    if st == -2:
+        return None
+    check(st, 'lpips_distance')
+    return partial.sum(1) / hw
+
+
+def lpips_distance_backward(f0, f1, w, grad, need0, need1, eps=1e-10):
+    """Data gradients of lpips_distance: grad [N] is the upstream gradient of d ON THE DEVICE, read by the kernel (no
+    .item()).  Returns (grad_f0 or None, grad_f1 or None) as need0 / need1 ask, laid out like the features; None
+    (alone) when the kernel does not serve the shape."""
+    n, c, hw = _lpips_distance_shape(f0, f1, w)
+    if not (need0 or need1):
+        return None, None
+    gl = grad.reshape(-1)
+    if gl.numel() != n:
+        raise ValueError(f'lpips_distance_backward: grad must hold one element per sample ({n}), got {tuple(grad.shape)}')
+    gl = gl.to(device=f0.device, dtype=torch.float32).contiguous()
+    w = w.contiguous()
+    p0, p1, pw, pg = fp(f0), fp(f1), fp(w), fp(gl)
+    g0 = torch.empty_like(f0) if need0 else None        # preserve_format: NHWC-dense like f0
+    g1 = torch.empty_like(f1) if need1 else None
+    if n == 0:
+        return g0, g1
+    with on_device(f0) as stream:
+        tok = _observer.begin('lpips_distance', (n, c, hw, 1))
+        st = lib().fmgan_lpips_distance_backward_f32(p0, p1, pw, pg, fp(g0), fp(g1), n, c, hw, float(eps), stream)
+        _observer.end(tok)
+    if st == -2:
+        return None
+    check(st, 'lpips_distance_backward')
+    return g0, g1
 
 
 def modconv_demod(weight, style, scale, eps=1e-8, wsq=None):

@@ -206,6 +206,32 @@ int fmgan_face_region_backward_f32(const float *r, const float *g, const float *
 int fmgan_render_mask_f32(const float *r, float *mask, int batch, int channels, long long hw, void *stream);
 
 /*
+ * LPIPS distance of one VGG tap (lpips/__init__.py, PNetLin.forward: unit-normalise over channels, squared difference,
+ * 1x1 conv to one channel, spatial mean) and its data gradients.  f0, f1 [batch, hw, channels] f32 (NHWC storage of
+ * [batch, channels, H, W] features, hw = H*W), w [channels] the 1x1 weight:
+ *   r_k = sqrt(sum_c f_k^2),  n_k = r_k + eps,  u_k = f_k / n_k                      (per pixel)
+ *   fmgan_lpips_distance_f32          : partial[b, blk] = sum over block blk's pixels of sample b of
+ *                                       sum_c w_c (u0_c - u1_c)^2; partial [batch, fmgan_lpips_distance_blocks(...)],
+ *                                       fixed association (no atomics): the caller sums each row and divides by hw
+ *   fmgan_lpips_distance_backward_f32 : with q1_c = -2 w_c (u0_c - u1_c) grad[b]/hw and q0 = -q1,
+ *                                       grad_fk_c = (qk_c - fk_c * (sum_c' qk_c' fk_c') / (r_k n_k)) / n_k;
+ *                                       grad [batch] is read on the DEVICE (no host synchronisation); grad_f0 / grad_f1
+ *                                       like f0 / f1, either may be NULL (not wanted), not both.  A pixel whose f_k is
+ *                                       exactly zero gets NaN in grad_fk (0/0, as autograd's sqrt backward) and
+ *                                       touches no other pixel.
+ * Served: channels in {64, 128, 256, 512} and 16-byte aligned pointers; FMGAN_EUNSUPPORTED otherwise
+ * (fmgan_lpips_distance_blocks returns 0 for such a channel count): the caller then evaluates the composite.
+ * batch == 0 returns FMGAN_OK before anything else; batch > 65535 or hw * channels >= 2^30 (a sample's element offsets
+ * are 32-bit) returns FMGAN_EOVERFLOW, and fmgan_lpips_distance_blocks 0.
+ */
+int fmgan_lpips_distance_blocks(int batch, int channels, int hw);
+int fmgan_lpips_distance_f32(const float *f0, const float *f1, const float *w, float *partial, int batch, int channels,
+                             int hw, float eps, void *stream);
+int fmgan_lpips_distance_backward_f32(const float *f0, const float *f1, const float *w, const float *grad,
+                                      float *grad_f0, float *grad_f1, int batch, int channels, int hw, float eps,
+                                      void *stream);
+
+/*
  * Demodulation coefficients of ModulatedConv2d (stylegan2.py:258-262):
  *   demod[b,o] = rsqrt( sum_{i,k} (scale * weight[o,i,k] * style[b,i])^2 + eps )
  *   weight [cout, cin, ktaps] f32 (the [1,cout,cin,k,k] parameter), style [batch, cin] f32,

@@ -76,7 +76,8 @@ def main():
         res[k] = {'first_call_s': round(first, 2), 'ms': round(1e3 * ts[len(ts) // 2], 2)}
         print(f'[{name} B={batch}] {k}: first call {first:.1f} s, then {res[k]["ms"]:.1f} ms', file=sys.stderr, flush=True)
     if only:
-        print(json.dumps({'workload': name, 'batch': batch, 'phases': res}))
+        print(json.dumps({'workload': name, 'batch': batch, 'phases': res,
+                          'peak_hbm_gb': round(torch.cuda.max_memory_allocated() / 1e9, 1)}))
         return
     amort = res['D']['ms'] + res['R1']['ms'] / a.d_reg_every + res['G']['ms'] + res['PPL']['ms'] / a.g_reg_every + res['EMA']['ms']
     torch.cuda.synchronize()
