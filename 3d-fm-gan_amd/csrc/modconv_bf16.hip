@@ -94,13 +94,24 @@ __device__ __forceinline__ void dma16_to_lds(RSRC rsrc, void* lds, unsigned voff
 #endif
 }
 
+// The halo patch and the LDS bytes of one tile (32*RM channels x 4*RNP rows x 32 columns), as its kernel and its launch
+// read them.  PIECES: bf16 pieces per fp32 operand, 1 (bf16: two weight images, one patch) or 3 (split operands: one
+// weight image and one patch per piece); every patch is double-buffered.
+template <int PIECES, int MODE, int RM, int RNP>
+struct BFTile {
+  static constexpr int BM = 32 * RM, TH = 4 * RNP, TW = 32;
+  static constexpr int SP = MODE == 2 ? 2 : 1;          // input step per position
+  static constexpr int PH = MODE == 1 ? TH + 1 : SP * (TH - 1) + 3;
+  static constexpr int PWP = MODE == 1 ? TW + 1 : SP * (TW - 1) + 3;
+  static constexpr size_t LDS = (size_t)((PIECES == 1 ? 2 : 3) * 9 * 2 * BM + PIECES * 2 * PH * PWP) * 16;
+};
+
 template <int MODE, int RM, int RNP>
 __global__ __launch_bounds__(256, 2) void modconv_mfma_bf16(const BFParams p) {
-  constexpr int BM = 32 * RM, TH = 4 * RNP, TW = 32;
-  constexpr int SP = MODE == 2 ? 2 : 1;                 // input step per position
+  using Tile = BFTile<1, MODE, RM, RNP>;
+  constexpr int BM = Tile::BM, TH = Tile::TH, TW = Tile::TW, SP = Tile::SP;
   constexpr int ORG = MODE == 2 ? 0 : 1;                // patch origin = SP * first position - ORG
-  constexpr int PH = MODE == 1 ? TH + 1 : SP * (TH - 1) + 3;
-  constexpr int PWP = MODE == 1 ? TW + 1 : SP * (TW - 1) + 3;
+  constexpr int PH = Tile::PH, PWP = Tile::PWP;
   constexpr int PLANE = PH * PWP;
   constexpr int NPH = MODE == 1 ? 4 : 1;
   constexpr int NU = (PLANE + 255) / 256;               // patch positions per thread
@@ -360,27 +371,6 @@ __global__ __launch_bounds__(256, 2) void modconv_mfma_bf16(const BFParams p) {
   }
 }
 
-template <int MODE, int RM, int RNP>
-int launch_bf16(BFParams& p, hipStream_t s) {
-  constexpr int BM = 32 * RM, TH = 4 * RNP;
-  constexpr int SP = MODE == 2 ? 2 : 1;
-  constexpr int PH = MODE == 1 ? TH + 1 : SP * (TH - 1) + 3;
-  constexpr int PWP = MODE == 1 ? 33 : SP * 31 + 3;
-  constexpr size_t lds = (size_t)(2 * 9 * 2 * BM + 2 * PH * PWP) * 16;     // two weight images + the patch
-  p.tiles_x = (p.gw + 31) / 32;
-  p.tiles_y = (p.gh + TH - 1) / TH;
-  p.o_tiles = (p.cout + BM - 1) / BM;
-  const long long blocks = (long long)p.o_tiles * p.tiles_x * p.tiles_y * p.batch;
-  if (blocks > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-  static bool attr = false;     // > 48 KB of dynamic LDS needs the opt-in once per instantiation (idempotent)
-  if (lds > 48 * 1024 && !attr) {
-    (void)hipFuncSetAttribute((const void*)modconv_mfma_bf16<MODE, RM, RNP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  hipLaunchKernelGGL((modconv_mfma_bf16<MODE, RM, RNP>), dim3((unsigned)blocks), dim3(256), lds, s, p);
-  return fmgan_check_launch();
-}
-
 // ------------------------------------------------------------------ fp32 on the bf16 matrix pipe: split operands
 // v_mfma_f32_32x32x16_bf16 does 16x the MACs per cycle of v_mfma_f32_32x32x2_f32.  An fp32 value splits exactly into three
 // bf16 pieces, x = hi + mid + lo (8 + 8 + 8 mantissa bits: hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid), every
@@ -429,9 +419,8 @@ __global__ __launch_bounds__(256) void modconv_weight_to_bf16x3(const float* __r
 template <int MODE, int RNP>
 __global__ __launch_bounds__(256, 2) void modconv_mfma_bf16x3(const BFParams p) {
   static_assert(MODE == 0 || MODE == 1, "forward modes only");
-  constexpr int BM = 32, TH = 4 * RNP, TW = 32;
-  constexpr int PH = MODE == 1 ? TH + 1 : TH + 2;
-  constexpr int PWP = MODE == 1 ? TW + 1 : TW + 2;
+  using Tile = BFTile<3, MODE, 1, RNP>;
+  constexpr int BM = Tile::BM, TH = Tile::TH, TW = Tile::TW, PH = Tile::PH, PWP = Tile::PWP;
   constexpr int PLANE = PH * PWP;
   constexpr int NPH = MODE == 1 ? 4 : 1;
   constexpr int NU = (PLANE + 255) / 256;
@@ -697,22 +686,72 @@ __global__ __launch_bounds__(256, 2) void modconv_mfma_bf16x3(const BFParams p) 
   }
 }
 
-template <int MODE, int RNP>
-int launch_bf16x3(BFParams& p, hipStream_t s) {
-  constexpr int TH = 4 * RNP;
-  constexpr int PH = MODE == 1 ? TH + 1 : TH + 2, PWP = MODE == 1 ? 33 : 34;
-  constexpr size_t lds = (size_t)(3 * 9 * 2 * 32 + 3 * 2 * PH * PWP) * 16;
-  p.tiles_x = (p.gw + 31) / 32;
-  p.tiles_y = (p.gh + TH - 1) / TH;
-  p.o_tiles = (p.cout + 31) / 32;
+// One launch for every tile of both contractions: the block grid, the LDS opt-in and the kernel, all from the tile.
+template <int PIECES, int MODE, int RM, int RNP>
+int launch_tile(BFParams& p, hipStream_t s) {
+  using Tile = BFTile<PIECES, MODE, RM, RNP>;
+  void (*kernel)(const BFParams);
+  if constexpr (PIECES == 3) kernel = modconv_mfma_bf16x3<MODE, RNP>;
+  else kernel = modconv_mfma_bf16<MODE, RM, RNP>;
+  p.tiles_x = (p.gw + Tile::TW - 1) / Tile::TW;
+  p.tiles_y = (p.gh + Tile::TH - 1) / Tile::TH;
+  p.o_tiles = (p.cout + Tile::BM - 1) / Tile::BM;
   const long long blocks = (long long)p.o_tiles * p.tiles_x * p.tiles_y * p.batch;
   if (blocks > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-  static bool attr = false;
-  if (lds > 48 * 1024 && !attr) {
-    (void)hipFuncSetAttribute((const void*)modconv_mfma_bf16x3<MODE, RNP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  static bool attr = false;     // > 48 KB of dynamic LDS needs the opt-in once per instantiation (idempotent)
+  if (Tile::LDS > 48 * 1024 && !attr) {
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Tile::LDS);
     attr = true;
   }
-  hipLaunchKernelGGL((modconv_mfma_bf16x3<MODE, RNP>), dim3((unsigned)blocks), dim3(256), lds, s, p);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), Tile::LDS, s, p);
+  return fmgan_check_launch();
+}
+
+// The host side of fmgan_modconv2d_bf16 (pieces == 1) and fmgan_modconv2d_bf16x3 (pieces == 3, forward modes 0 / 1).
+int modconv2d_bf(int pieces, const float* in, const void* wt, const float* style, const float* demod, float* out, int batch,
+                 int cin, int cout, int h, int w, int mode, const float* noise, const float* noise_weight,
+                 const float* bias, int noise_batch, int fuse_act, float alpha, float act_scale,
+                 long long out_plane_stride, int out_row_stride, hipStream_t s) {
+  if (batch < 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return FMGAN_EINVAL;
+  if (mode < 0 || mode > (pieces == 3 ? 1 : 2)) return FMGAN_EUNSUPPORTED;
+  if (mode != 0 && fuse_act) return FMGAN_EUNSUPPORTED;
+  if (batch == 0) return FMGAN_OK;
+  if (!(pieces == 3 ? fmgan_modconv2d_bf16x3_supported : fmgan_modconv2d_bf16_supported)(batch, cin, cout, h, w, mode))
+    return FMGAN_EUNSUPPORTED;
+  if (!in || !wt || !style || !out) return FMGAN_EINVAL;
+  if (fuse_act && noise && noise_batch != 1 && noise_batch != batch) return FMGAN_EINVAL;
+  BFParams p{};
+  p.in = in; p.wt = (const unsigned short*)wt; p.style = style; p.demod = demod; p.out = out;
+  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
+  if (mode == 1) { p.oh = 2 * h + 1; p.ow = 2 * w + 1; p.gh = h + 1; p.gw = w + 1; }   // quads (m <= h, n <= w)
+  else if (mode == 2) { p.oh = (h - 3) / 2 + 1; p.ow = (w - 3) / 2 + 1; p.gh = p.oh; p.gw = p.ow; }
+  else { p.oh = h; p.ow = w; p.gh = h; p.gw = w; }
+  if (out_row_stride == 0) out_row_stride = p.ow;
+  if (out_plane_stride == 0) out_plane_stride = (long long)p.oh * out_row_stride;
+  if (out_row_stride < p.ow || out_plane_stride < (long long)p.oh * out_row_stride) return FMGAN_EINVAL;
+  if ((long long)batch * cout * out_plane_stride > (1LL << 40)) return FMGAN_EOVERFLOW;
+  p.out_plane_stride = out_plane_stride; p.out_row_stride = out_row_stride;
+  p.mp = (cout + 31) / 32 * 32;
+  p.noise = noise; p.noise_weight = noise_weight; p.bias = bias; p.noise_batch = noise_batch; p.fuse_act = fuse_act;
+  p.alpha = alpha; p.act_scale = act_scale;
+  if (pieces == 3) return mode == 0 ? launch_tile<3, 0, 1, 2>(p, s) : launch_tile<3, 1, 1, 1>(p, s);
+  // (a 128-channel tile needs 2 x 37 KB of weight images: one block per CU; 64 channels x 256 positions fits three)
+  if (mode == 0) return cout >= 64 ? launch_tile<1, 0, 2, 2>(p, s) : launch_tile<1, 0, 1, 4>(p, s);
+  if (mode == 2) return cout >= 64 ? launch_tile<1, 2, 2, 2>(p, s) : launch_tile<1, 2, 1, 2>(p, s);
+  return cout >= 64 ? launch_tile<1, 1, 2, 1>(p, s) : launch_tile<1, 1, 1, 2>(p, s);
+}
+
+// fmgan_modconv_weight_to_bf16 (pieces == 1) and fmgan_modconv_weight_to_bf16x3 (pieces == 3): one thread per bf16 pair
+int weight_to_bf(int pieces, const float* wt, void* dst, int cin, int cout, int ktaps, hipStream_t s) {
+  if (cout <= 0 || cin <= 0 || ktaps <= 0) return FMGAN_EINVAL;
+  if (!wt || !dst) return FMGAN_EINVAL;
+  const long long pairs = fmgan_modconv_weight_bf16_bytes(cin, cout, ktaps) / 4;
+  long long blocks = (pairs + 255) / 256;
+  const long long cap = (long long)FMGAN_NUM_CU * 16;
+  if (blocks > cap) blocks = cap;
+  const dim3 g((unsigned)blocks), b(256);
+  if (pieces == 3) hipLaunchKernelGGL(modconv_weight_to_bf16x3, g, b, 0, s, wt, (unsigned*)dst, cin, cout, ktaps);
+  else hipLaunchKernelGGL(modconv_weight_to_bf16, g, b, 0, s, wt, (unsigned short*)dst, cin, cout, ktaps);
   return fmgan_check_launch();
 }
 
@@ -724,15 +763,7 @@ extern "C" long long fmgan_modconv_weight_bf16_bytes(int cin, int cout, int ktap
 }
 
 extern "C" int fmgan_modconv_weight_to_bf16(const float* wt, void* wt_bf16, int cin, int cout, int ktaps, void* stream) {
-  if (cout <= 0 || cin <= 0 || ktaps <= 0) return FMGAN_EINVAL;
-  if (!wt || !wt_bf16) return FMGAN_EINVAL;
-  const long long pairs = fmgan_modconv_weight_bf16_bytes(cin, cout, ktaps) / 4;
-  long long blocks = (pairs + 255) / 256;
-  const long long cap = (long long)FMGAN_NUM_CU * 16;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(modconv_weight_to_bf16, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, wt,
-                     (unsigned short*)wt_bf16, cin, cout, ktaps);
-  return fmgan_check_launch();
+  return weight_to_bf(1, wt, wt_bf16, cin, cout, ktaps, (hipStream_t)stream);
 }
 
 // 1 when fmgan_modconv2d_bf16 serves the shape (host logic only)
@@ -753,41 +784,8 @@ extern "C" int fmgan_modconv2d_bf16(const float* in, const void* wt_bf16, const 
                                     const float* noise_weight, const float* bias, int noise_batch, int fuse_act,
                                     float alpha, float act_scale, long long out_plane_stride, int out_row_stride,
                                     void* stream) {
-  if (batch < 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return FMGAN_EINVAL;
-  if (mode < 0 || mode > 2) return FMGAN_EUNSUPPORTED;
-  if (mode != 0 && fuse_act) return FMGAN_EUNSUPPORTED;
-  if (batch == 0) return FMGAN_OK;
-  if (!fmgan_modconv2d_bf16_supported(batch, cin, cout, h, w, mode)) return FMGAN_EUNSUPPORTED;
-  if (!in || !wt_bf16 || !style || !out) return FMGAN_EINVAL;
-  if (fuse_act && noise && noise_batch != 1 && noise_batch != batch) return FMGAN_EINVAL;
-  BFParams p{};
-  p.in = in; p.wt = (const unsigned short*)wt_bf16; p.style = style; p.demod = demod; p.out = out;
-  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
-  if (mode == 1) { p.oh = 2 * h + 1; p.ow = 2 * w + 1; p.gh = h + 1; p.gw = w + 1; }   // quads (m <= h, n <= w)
-  else if (mode == 2) { p.oh = (h - 3) / 2 + 1; p.ow = (w - 3) / 2 + 1; p.gh = p.oh; p.gw = p.ow; }
-  else { p.oh = h; p.ow = w; p.gh = h; p.gw = w; }
-  if (out_row_stride == 0) out_row_stride = p.ow;
-  if (out_plane_stride == 0) out_plane_stride = (long long)p.oh * out_row_stride;
-  if (out_row_stride < p.ow || out_plane_stride < (long long)p.oh * out_row_stride) return FMGAN_EINVAL;
-  if ((long long)batch * cout * out_plane_stride > (1LL << 40)) return FMGAN_EOVERFLOW;
-  p.out_plane_stride = out_plane_stride; p.out_row_stride = out_row_stride;
-  p.mp = (cout + 31) / 32 * 32;
-  p.noise = noise; p.noise_weight = noise_weight; p.bias = bias; p.noise_batch = noise_batch; p.fuse_act = fuse_act;
-  p.alpha = alpha; p.act_scale = act_scale;
-  hipStream_t s = (hipStream_t)stream;
-  int st;
-  if (mode == 0) {
-    // (a 128-channel tile needs 2 x 37 KB of weight images: one block per CU; 64 channels x 256 positions fits three)
-    if (cout >= 64) st = launch_bf16<0, 2, 2>(p, s);
-    else st = launch_bf16<0, 1, 4>(p, s);
-  } else if (mode == 2) {
-    if (cout >= 64) st = launch_bf16<2, 2, 2>(p, s);
-    else st = launch_bf16<2, 1, 2>(p, s);
-  } else {
-    if (cout >= 64) st = launch_bf16<1, 2, 1>(p, s);
-    else st = launch_bf16<1, 1, 2>(p, s);
-  }
-  return st;
+  return modconv2d_bf(1, in, wt_bf16, style, demod, out, batch, cin, cout, h, w, mode, noise, noise_weight, bias,
+                      noise_batch, fuse_act, alpha, act_scale, out_plane_stride, out_row_stride, (hipStream_t)stream);
 }
 
 // ---- split-operand fp32 ("bf16x3"): see the kernel's comment.  Forward modes 0 / 1.
@@ -797,15 +795,7 @@ extern "C" long long fmgan_modconv_weight_bf16x3_bytes(int cin, int cout, int kt
 }
 
 extern "C" int fmgan_modconv_weight_to_bf16x3(const float* wt, void* wt_split, int cin, int cout, int ktaps, void* stream) {
-  if (cout <= 0 || cin <= 0 || ktaps <= 0) return FMGAN_EINVAL;
-  if (!wt || !wt_split) return FMGAN_EINVAL;
-  const long long pairs = fmgan_modconv_weight_bf16_bytes(cin, cout, ktaps) / 4;
-  long long blocks = (pairs + 255) / 256;
-  const long long cap = (long long)FMGAN_NUM_CU * 16;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(modconv_weight_to_bf16x3, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, wt,
-                     (unsigned*)wt_split, cin, cout, ktaps);
-  return fmgan_check_launch();
+  return weight_to_bf(3, wt, wt_split, cin, cout, ktaps, (hipStream_t)stream);
 }
 
 extern "C" int fmgan_modconv2d_bf16x3_supported(int batch, int cin, int cout, int h, int w, int mode) {
@@ -819,26 +809,6 @@ extern "C" int fmgan_modconv2d_bf16x3(const float* in, const void* wt_split, con
                                       const float* noise_weight, const float* bias, int noise_batch, int fuse_act,
                                       float alpha, float act_scale, long long out_plane_stride, int out_row_stride,
                                       void* stream) {
-  if (batch < 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return FMGAN_EINVAL;
-  if (mode != 0 && mode != 1) return FMGAN_EUNSUPPORTED;
-  if (mode != 0 && fuse_act) return FMGAN_EUNSUPPORTED;
-  if (batch == 0) return FMGAN_OK;
-  if (!fmgan_modconv2d_bf16x3_supported(batch, cin, cout, h, w, mode)) return FMGAN_EUNSUPPORTED;
-  if (!in || !wt_split || !style || !out) return FMGAN_EINVAL;
-  if (fuse_act && noise && noise_batch != 1 && noise_batch != batch) return FMGAN_EINVAL;
-  BFParams p{};
-  p.in = in; p.wt = (const unsigned short*)wt_split; p.style = style; p.demod = demod; p.out = out;
-  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
-  if (mode == 1) { p.oh = 2 * h + 1; p.ow = 2 * w + 1; p.gh = h + 1; p.gw = w + 1; }
-  else { p.oh = h; p.ow = w; p.gh = h; p.gw = w; }
-  if (out_row_stride == 0) out_row_stride = p.ow;
-  if (out_plane_stride == 0) out_plane_stride = (long long)p.oh * out_row_stride;
-  if (out_row_stride < p.ow || out_plane_stride < (long long)p.oh * out_row_stride) return FMGAN_EINVAL;
-  if ((long long)batch * cout * out_plane_stride > (1LL << 40)) return FMGAN_EOVERFLOW;
-  p.out_plane_stride = out_plane_stride; p.out_row_stride = out_row_stride;
-  p.mp = (cout + 31) / 32 * 32;
-  p.noise = noise; p.noise_weight = noise_weight; p.bias = bias; p.noise_batch = noise_batch; p.fuse_act = fuse_act;
-  p.alpha = alpha; p.act_scale = act_scale;
-  hipStream_t s = (hipStream_t)stream;
-  return mode == 0 ? launch_bf16x3<0, 2>(p, s) : launch_bf16x3<1, 1>(p, s);
+  return modconv2d_bf(3, in, wt_split, style, demod, out, batch, cin, cout, h, w, mode, noise, noise_weight, bias,
+                      noise_batch, fuse_act, alpha, act_scale, out_plane_stride, out_row_stride, (hipStream_t)stream);
 }

@@ -654,110 +654,52 @@ __global__ __launch_bounds__(256) void ufd_up2_f32(const float* __restrict__ in,
   }
 }
 
-template <typename T>
-int launch_generic(const void* in, const void* kern, void* out, const UfdParams& p, hipStream_t s) {
-  const long long total = (long long)p.major * p.out_h * p.out_w * p.minor;
-  if (total == 0) return FMGAN_OK;
-  long long blocks = (total + 255) / 256;
-  const long long cap = (long long)FMGAN_NUM_CU * 32;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(ufd_generic<T>, dim3((unsigned)blocks), dim3(256), 0, s, (const T*)in, (const T*)kern, (T*)out, p, total);
-  return fmgan_check_launch();
-}
+// ---------------------------------------------------------------- host: one plan per call
+// Every entry point below is plan_ufd, and launch_ufd where something runs.  The plan is made once from the arguments the
+// entry point got and holds every decision: launch_ufd copies it into the kernel's parameter struct, a select returns it.
+struct UfdEpilogue {
+  const float* noise; const float* noise_weight; const float* bias;
+  int channels, noise_batch; float alpha, act_scale;
+};
+
+struct UfdArgs {
+  int dtype, major, in_h, in_w, minor;
+  long long in_plane_stride; int in_row_stride;
+  int kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, force_path;
+  const void* in; const void* kern; void* out;   // a query may leave them absent
+  const UfdEpilogue* ep;   // the fused blur: planes are batch x ep->channels and `major` is not read
+  int batch;
+  bool query;              // nothing will be launched
+};
+
+struct UfdPlan {
+  UfdParams p;             // the shape, out_h / out_w included
+  int kernel;              // the header's numbering: 0 generic, 1 row-march, 5 LDS-DMA ring, 2 plane-tile, 3 up2
+  bool empty;              // major == 0: the launch is a no-op
+  unsigned blocks; size_t lds;
+  long long total;         // path 0: output elements
+  int vec, strips, th, tiles_y; long long total_waves; bool nt;   // paths 1 and 1b
+  int pb, bw, bh;          // path 2: planes per block; path 3: 4x2 blocks per row / column
+};
 
 bool rowmarch_ok(int dtype, const UfdParams& p) {
   return dtype == FMGAN_F32 && p.minor == 1 && p.up_x == 1 && p.up_y == 1 && p.down_x == 1 && p.down_y == 1 &&
          p.kh <= 4 && p.kw <= 4 && p.out_w >= 64 && p.out_h >= 4;
 }
 
-struct UfdEpilogue {
-  const float* noise; const float* noise_weight; const float* bias;
-  int channels, noise_batch; float alpha, act_scale;
-};
-
 // Path 1b serves the aligned-row layout only: position 0 of every row (= logical column -pad_x0) on a 16-byte
 // boundary, row / plane pitch multiples of 4 floats, rows of the output 16-byte aligned, a noise plane when fused.
+// It is chosen by address: a query that gives no addresses is answered with path 1.
 // force_path 4 keeps path 1, 5 insists on path 1b (A/B tests and measurements; no environment switch in the library).
-bool dmaring_ok(const void* in, const void* out, const UfdParams& p, const UfdEpilogue* ep) {
-  const uintptr_t in0 = (uintptr_t)in - 4u * (unsigned)p.pad_x0;
-  if (p.pad_x0 < 0 || p.pad_x0 > 3 || (in0 & 15) || ((uintptr_t)out & 15)) return false;
+bool dmaring_ok(const UfdArgs& a, const UfdParams& p) {
+  if (!a.in || !a.out) return false;
+  const uintptr_t in0 = (uintptr_t)a.in - 4u * (unsigned)p.pad_x0;
+  if (p.pad_x0 < 0 || p.pad_x0 > 3 || (in0 & 15) || ((uintptr_t)a.out & 15)) return false;
   if ((p.in_row_stride & 3) || (p.in_plane_stride & 3) || (p.out_w & 3) || p.out_w < 256 || p.out_h < 8) return false;
   if (p.in_row_stride < p.in_w + p.pad_x0) return false;                       // the shifted row must fit its pitch
   if ((long long)p.in_h * p.in_row_stride * 4 > 0x7fffffffLL) return false;    // num_records / soffset are 32-bit
-  if (ep && (!ep->noise || ((uintptr_t)ep->noise & 15))) return false;
+  if (a.ep && (!a.ep->noise || ((uintptr_t)a.ep->noise & 15))) return false;
   return true;
-}
-
-int launch_dmaring(const void* in, const void* kern, void* out, const UfdParams& p, hipStream_t s,
-                   const UfdEpilogue* ep) {
-  DRParams r{};
-  r.in0 = (const float*)in - p.pad_x0; r.out = (float*)out; r.kern = (const float*)kern;
-  if (ep) {
-    r.noise = ep->noise; r.noise_weight = ep->noise_weight; r.bias = ep->bias;
-    r.channels = ep->channels; r.noise_batch = ep->noise_batch; r.alpha = ep->alpha; r.act_scale = ep->act_scale;
-  }
-  r.planes = p.major; r.in_h = p.in_h; r.in_w = p.in_w; r.out_h = p.out_h; r.out_w = p.out_w;
-  r.rs = p.in_row_stride; r.ps = p.in_plane_stride; r.pad_x0 = p.pad_x0; r.pad_y0 = p.pad_y0; r.kh = p.kh; r.kw = p.kw;
-  r.strips = (p.out_w + 255) / 256;
-  // Largest row tile (halo re-read = 3/TH) that divides the height and still leaves >= 32 waves per CU in the grid.
-  const long long want = (long long)FMGAN_NUM_CU * 32;
-  int th = 64;
-  while (th > 8 && ((p.out_h % th) != 0 || (long long)p.major * r.strips * (p.out_h / th) < want)) th >>= 1;
-  r.th = th;
-  r.tiles_y = (p.out_h + th - 1) / th;
-  r.total_waves = (long long)p.major * r.strips * r.tiles_y;
-  const long long blocks = (r.total_waves + 3) / 4;
-  if (blocks > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-  const dim3 g((unsigned)blocks), b(256);
-  const size_t lds = 4 * 4 * 320 * sizeof(float);   // 4 waves x 4 slots x (256 + 64) floats
-  // Block order and cache policy: hardware order, cached loads.  Blocks are dealt round-robin over the 8 XCDs, so with
-  // tiles numbered (strip, row tile, plane) an XCD sees the SAME few (strip, row tile) positions of every plane: its
-  // share of the noise plane is a few hundred KB that stays in its L2 for all planes, where the XCD-contiguous order of
-  // path 1 re-fetches it per plane (FETCH_SIZE of the fused headline blur, standalone: 1.68x the input with
-  // XCD-contiguous order, 1.51x with nt loads on top, 1.12x in hardware order; plain blur 1.08x either way — the
-  // <.., NT, XCD> instantiations those numbers came from are no longer built).
-  if (ep) hipLaunchKernelGGL((ufd_dmaring_f32<true, false, false>), g, b, lds, s, r);
-  else hipLaunchKernelGGL((ufd_dmaring_f32<false, false, false>), g, b, lds, s, r);
-  return fmgan_check_launch();
-}
-
-// variant: -1 / 1 pick between path 1 and 1b, 4 = path 1 (register row-march), 5 = path 1b (LDS-DMA ring) or refuse
-int launch_rowmarch(const void* in, const void* kern, void* out, const UfdParams& p, hipStream_t s,
-                    const UfdEpilogue* ep = nullptr, int variant = -1) {
-  if (variant == 5 && !dmaring_ok(in, out, p, ep)) return FMGAN_EUNSUPPORTED;
-  if (variant != 4 && dmaring_ok(in, out, p, ep)) return launch_dmaring(in, kern, out, p, s, ep);
-  RMParams r{};
-  if (ep) {
-    r.fuse = 1; r.noise = ep->noise; r.noise_weight = ep->noise_weight; r.bias = ep->bias;
-    r.channels = ep->channels; r.noise_batch = ep->noise_batch; r.alpha = ep->alpha; r.act_scale = ep->act_scale;
-  }
-  r.planes = p.major; r.in_h = p.in_h; r.in_w = p.in_w; r.out_h = p.out_h; r.out_w = p.out_w;
-  r.pad_x0 = p.pad_x0; r.pad_y0 = p.pad_y0; r.kh = p.kh; r.kw = p.kw;
-  r.in_plane_stride = p.in_plane_stride; r.in_row_stride = p.in_row_stride;
-  const int vec = p.out_w >= 192 ? 4 : (p.out_w >= 96 ? 2 : 1);
-  r.strips = (p.out_w + 64 * vec - 1) / (64 * vec);
-  // Largest row tile that still leaves >= 32 waves per CU in the grid (halo re-read = 3/TH).
-  const long long want = (long long)FMGAN_NUM_CU * 32;
-  int th = 64;
-  while (th > 4) {
-    const long long waves = (long long)p.major * r.strips * ((p.out_h + th - 1) / th);
-    if (waves >= want) break;
-    th >>= 1;
-  }
-  // outputs far larger than the 256 MiB Infinity Cache cannot be re-read from it by the consumer: store them
-  // non-temporal (measured +3 % on the 1 GB headline call); small layers keep the default policy.
-  const bool env_nt = (long long)p.major * p.out_h * p.out_w * 4 >= (512LL << 20);
-  r.th = th;
-  r.tiles_y = (p.out_h + th - 1) / th;
-  r.total_waves = (long long)p.major * r.strips * r.tiles_y;
-  const long long blocks = (r.total_waves + 3) / 4;
-  if (blocks > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-  const dim3 g((unsigned)blocks), b(256);
-  if (vec == 4 && env_nt) hipLaunchKernelGGL((ufd_rowmarch_f32<4, true>), g, b, 0, s, (const float*)in, (const float*)kern, (float*)out, r);
-  else if (vec == 4) hipLaunchKernelGGL(ufd_rowmarch_f32<4>, g, b, 0, s, (const float*)in, (const float*)kern, (float*)out, r);
-  else if (vec == 2) hipLaunchKernelGGL(ufd_rowmarch_f32<2>, g, b, 0, s, (const float*)in, (const float*)kern, (float*)out, r);
-  else hipLaunchKernelGGL(ufd_rowmarch_f32<1>, g, b, 0, s, (const float*)in, (const float*)kern, (float*)out, r);
-  return fmgan_check_launch();
 }
 
 bool planetile_ok(int dtype, const UfdParams& p) {
@@ -766,65 +708,190 @@ bool planetile_ok(int dtype, const UfdParams& p) {
          (long long)p.in_h * p.in_row_stride <= 0x7fffffffLL;
 }
 
-int launch_planetile(const void* in, const void* kern, void* out, const UfdParams& p, hipStream_t s,
-                     const UfdEpilogue* ep = nullptr) {
-  PTParams t{p.major, p.in_h, p.in_w, p.out_h, p.out_w, p.pad_x0, p.pad_y0, p.kh, p.kw, 1};
-  t.in_plane_stride = p.in_plane_stride; t.in_row_stride = p.in_row_stride;
-  if (ep) {
-    t.noise = ep->noise; t.noise_weight = ep->noise_weight; t.bias = ep->bias; t.channels = ep->channels;
-    t.noise_batch = ep->noise_batch; t.alpha = ep->alpha; t.act_scale = ep->act_scale;
-  }
-  const int in_sz = p.in_h * p.in_w;
-  int pb = 8192 / in_sz;                      // ~32 KB of LDS per block
-  if (pb < 1) pb = 1;
-  if (pb > 64) pb = 64;
-  // keep at least ~2 blocks per CU when the layer is small
-  while (pb > 1 && (p.major + pb - 1) / pb < 2 * FMGAN_NUM_CU) pb >>= 1;
-  t.pb = pb;
-  const unsigned blocks = (unsigned)((p.major + pb - 1) / pb);
-  if (ep) hipLaunchKernelGGL(ufd_planetile_f32<true>, dim3(blocks), dim3(256), sizeof(float) * (size_t)pb * in_sz, s,
-                             (const float*)in, (const float*)kern, (float*)out, t);
-  else hipLaunchKernelGGL(ufd_planetile_f32<false>, dim3(blocks), dim3(256), sizeof(float) * (size_t)pb * in_sz, s,
-                          (const float*)in, (const float*)kern, (float*)out, t);
-  return fmgan_check_launch();
-}
-
 bool up2_ok(int dtype, const UfdParams& p) {
   return dtype == FMGAN_F32 && p.minor == 1 && p.up_x == 2 && p.up_y == 2 && p.down_x == 1 && p.down_y == 1 &&
          p.kh <= 4 && p.kw <= 4 && p.in_row_stride == p.in_w && p.in_plane_stride == (long long)p.in_h * p.in_w;
 }
 
-int launch_up2(const void* in, const void* kern, void* out, const UfdParams& p, hipStream_t s) {
-  U2Params t{p.major, p.in_h, p.in_w, p.out_h, p.out_w, p.pad_x0, p.pad_y0, p.kh, p.kw, (p.out_w + 3) / 4,
-             (p.out_h + 1) / 2};
-  const long long total = (long long)p.major * t.bw * t.bh;
-  long long blocks = (total + 255) / 256;
+// Checks in the order the launches have always reported them; no allocation, no HIP call, no environment read.
+int plan_ufd(const UfdArgs& a, UfdPlan& pl) {
+  pl = UfdPlan{};
+  const bool fused = a.ep != nullptr;
+  long long major = a.major;
+  if (fused) {
+    if (a.force_path != -1 && a.force_path != 1 && a.force_path != 4 && a.force_path != 5) return FMGAN_EUNSUPPORTED;
+    // an empty batch is a no-op to launch, but a query has no kernel to name for it
+    if (a.batch < 0 || (a.query && a.batch == 0) || a.ep->channels <= 0) return FMGAN_EINVAL;
+    major = (long long)a.batch * a.ep->channels;
+    if (major > 0x7fffffffLL) return FMGAN_EOVERFLOW;
+  }
+  if (a.dtype != FMGAN_F32 && a.dtype != FMGAN_F64 && a.dtype != FMGAN_F16) return FMGAN_EUNSUPPORTED;
+  if (major < 0 || a.in_h <= 0 || a.in_w <= 0 || a.minor <= 0 || a.kh <= 0 || a.kw <= 0) return FMGAN_EINVAL;
+  if (a.up_x <= 0 || a.up_y <= 0 || a.down_x <= 0 || a.down_y <= 0) return FMGAN_EINVAL;
+  if (a.in_row_stride < a.in_w * a.minor ||
+      a.in_plane_stride < (long long)(a.in_h - 1) * a.in_row_stride + (long long)a.in_w * a.minor)
+    return FMGAN_EINVAL;
+  if (fused && a.ep->noise && a.ep->noise_batch != 1 && a.ep->noise_batch != a.batch) return FMGAN_EINVAL;
+  UfdParams& p = pl.p;
+  p = UfdParams{(int)major, a.in_h, a.in_w, a.minor, a.kh, a.kw, a.up_x, a.up_y, a.down_x, a.down_y, a.pad_x0, a.pad_y0,
+                0, 0, a.in_plane_stride, a.in_row_stride};
+  fmgan_upfirdn2d_out_size(a.in_h, a.in_w, a.kh, a.kw, a.up_x, a.up_y, a.down_x, a.down_y, a.pad_x0, a.pad_x1, a.pad_y0,
+                           a.pad_y1, &p.out_h, &p.out_w);
+  if (p.out_h <= 0 || p.out_w <= 0) return FMGAN_EINVAL;
+  if (!a.query && major == 0) { pl.empty = true; return FMGAN_OK; }
+  if (!a.query && (!a.in || !a.kern || !a.out)) return FMGAN_EINVAL;
+  if ((long long)a.in_h * a.in_row_stride > 0x7fffffffLL) return FMGAN_EOVERFLOW;
+  if (!fused && (long long)p.out_h * p.out_w * a.minor > 0x7fffffffLL) return FMGAN_EOVERFLOW;
+  // Which kernel.  The fused blur has three (row-march, ring, plane-tile) and takes -1 and 1 alike as "automatic":
+  // the plane-tile kernel serves the small planes of the 4^2..32^2 upsampling layers in the aligned-row layout.
+  const bool rm = rowmarch_ok(a.dtype, p);
+  int path = a.force_path;
+  if (fused) {
+    if (rm) path = path > 1 ? path : 1;
+    else if (path > 1 || !planetile_ok(a.dtype, p)) return FMGAN_EUNSUPPORTED;
+    else path = 2;
+  } else if (path < 0) {
+    path = rm ? 1 : planetile_ok(a.dtype, p) ? 2 : up2_ok(a.dtype, p) ? 3 : 0;
+  }
   const long long cap = (long long)FMGAN_NUM_CU * 32;
-  if (blocks > cap) blocks = cap;
-  const int par = (p.pad_y0 & 1) * 2 + (p.pad_x0 & 1);
-  const dim3 g((unsigned)blocks), b(256);
-  switch (par) {
-    case 0: hipLaunchKernelGGL((ufd_up2_f32<0, 0>), g, b, 0, s, (const float*)in, (const float*)kern, (float*)out, t); break;
-    case 1: hipLaunchKernelGGL((ufd_up2_f32<0, 1>), g, b, 0, s, (const float*)in, (const float*)kern, (float*)out, t); break;
-    case 2: hipLaunchKernelGGL((ufd_up2_f32<1, 0>), g, b, 0, s, (const float*)in, (const float*)kern, (float*)out, t); break;
-    default: hipLaunchKernelGGL((ufd_up2_f32<1, 1>), g, b, 0, s, (const float*)in, (const float*)kern, (float*)out, t); break;
+  switch (path) {
+    case 0:     // generic: pl.kernel stays 0
+      pl.total = major * p.out_h * p.out_w * p.minor;
+      pl.blocks = (unsigned)std::min(cap, (pl.total + 255) / 256);
+      return FMGAN_OK;
+    case 1:     // path 1b where its rules hold, else path 1
+    case 4:     // path 1 (register row-march)
+    case 5: {   // path 1b (LDS-DMA ring) or refuse
+      if (!rm) return FMGAN_EUNSUPPORTED;
+      const bool ring = path != 4 && dmaring_ok(a, p);
+      if (path == 5 && !ring) return FMGAN_EUNSUPPORTED;
+      pl.kernel = ring ? 5 : 1;
+      pl.vec = p.out_w >= 192 ? 4 : (p.out_w >= 96 ? 2 : 1);
+      pl.strips = (p.out_w + 64 * pl.vec - 1) / (64 * pl.vec);
+      // Largest row tile (halo re-read = 3/TH) that still leaves >= 32 waves per CU in the grid; the ring's tile
+      // also divides the height and has at least 8 rows.
+      pl.th = 64;
+      while (pl.th > (ring ? 8 : 4) &&
+             ((ring && (p.out_h % pl.th) != 0) || major * pl.strips * ((p.out_h + pl.th - 1) / pl.th) < cap))
+        pl.th >>= 1;
+      pl.tiles_y = (p.out_h + pl.th - 1) / pl.th;
+      pl.total_waves = major * pl.strips * pl.tiles_y;
+      if ((pl.total_waves + 3) / 4 > 0x7fffffffLL) return FMGAN_EOVERFLOW;
+      pl.blocks = (unsigned)((pl.total_waves + 3) / 4);
+      if (ring) pl.lds = 4 * 4 * 320 * sizeof(float);   // 4 waves x 4 slots x (256 + 64) floats
+      // outputs far larger than the 256 MiB Infinity Cache cannot be re-read from it by the consumer: store them
+      // non-temporal (measured +3 % on the 1 GB headline call); small layers keep the default policy.
+      else pl.nt = pl.vec == 4 && major * p.out_h * p.out_w * 4 >= (512LL << 20);
+      return FMGAN_OK;
+    }
+    case 2: {
+      if (!planetile_ok(a.dtype, p)) return FMGAN_EUNSUPPORTED;
+      pl.kernel = 2;
+      const int in_sz = p.in_h * p.in_w;
+      int pb = std::min(std::max(8192 / in_sz, 1), 64);   // ~32 KB of LDS per block
+      while (pb > 1 && (p.major + pb - 1) / pb < 2 * FMGAN_NUM_CU) pb >>= 1;   // >= ~2 blocks per CU on a small layer
+      pl.pb = pb;
+      pl.blocks = (unsigned)((p.major + pb - 1) / pb);
+      pl.lds = sizeof(float) * (size_t)pb * in_sz;
+      return FMGAN_OK;
+    }
+    case 3:
+      if (!up2_ok(a.dtype, p)) return FMGAN_EUNSUPPORTED;
+      pl.kernel = 3;
+      pl.bw = (p.out_w + 3) / 4;
+      pl.bh = (p.out_h + 1) / 2;
+      pl.blocks = (unsigned)std::min(cap, (major * pl.bw * pl.bh + 255) / 256);
+      return FMGAN_OK;
+    default: return FMGAN_EUNSUPPORTED;
+  }
+}
+
+// The optional StyledConv epilogue, as RMParams, DRParams and PTParams hold it.
+template <typename P>
+void set_epilogue(P& r, const UfdEpilogue* ep) {
+  if (!ep) return;
+  r.noise = ep->noise; r.noise_weight = ep->noise_weight; r.bias = ep->bias;
+  r.channels = ep->channels; r.noise_batch = ep->noise_batch; r.alpha = ep->alpha; r.act_scale = ep->act_scale;
+}
+
+template <typename T>
+void launch_generic(const UfdPlan& pl, const UfdArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(ufd_generic<T>, dim3(pl.blocks), dim3(256), 0, s, (const T*)a.in, (const T*)a.kern, (T*)a.out, pl.p,
+                     pl.total);
+}
+
+// Fills the parameter struct of the plan's kernel from the plan and launches it; nothing is decided here.
+int launch_ufd(const UfdPlan& pl, const UfdArgs& a, hipStream_t s) {
+  const UfdParams& p = pl.p;
+  const float* in = (const float*)a.in; const float* kern = (const float*)a.kern; float* out = (float*)a.out;
+  const dim3 g(pl.blocks), b(256);
+  switch (pl.kernel) {
+    case 0:
+      if (a.dtype == FMGAN_F32) launch_generic<float>(pl, a, s);
+      else if (a.dtype == FMGAN_F64) launch_generic<double>(pl, a, s);
+      else launch_generic<__half>(pl, a, s);
+      break;
+    case 1: {
+      RMParams r{};
+      r.fuse = a.ep != nullptr;
+      set_epilogue(r, a.ep);
+      r.planes = p.major; r.in_h = p.in_h; r.in_w = p.in_w; r.out_h = p.out_h; r.out_w = p.out_w;
+      r.pad_x0 = p.pad_x0; r.pad_y0 = p.pad_y0; r.kh = p.kh; r.kw = p.kw;
+      r.in_plane_stride = p.in_plane_stride; r.in_row_stride = p.in_row_stride;
+      r.th = pl.th; r.strips = pl.strips; r.tiles_y = pl.tiles_y; r.total_waves = pl.total_waves;
+      if (pl.nt) hipLaunchKernelGGL((ufd_rowmarch_f32<4, true>), g, b, 0, s, in, kern, out, r);
+      else if (pl.vec == 4) hipLaunchKernelGGL(ufd_rowmarch_f32<4>, g, b, 0, s, in, kern, out, r);
+      else if (pl.vec == 2) hipLaunchKernelGGL(ufd_rowmarch_f32<2>, g, b, 0, s, in, kern, out, r);
+      else hipLaunchKernelGGL(ufd_rowmarch_f32<1>, g, b, 0, s, in, kern, out, r);
+    } break;
+    case 5: {
+      DRParams r{};
+      r.in0 = in - p.pad_x0; r.out = out; r.kern = kern;
+      set_epilogue(r, a.ep);
+      r.planes = p.major; r.in_h = p.in_h; r.in_w = p.in_w; r.out_h = p.out_h; r.out_w = p.out_w;
+      r.rs = p.in_row_stride; r.ps = p.in_plane_stride; r.pad_x0 = p.pad_x0; r.pad_y0 = p.pad_y0; r.kh = p.kh; r.kw = p.kw;
+      r.th = pl.th; r.strips = pl.strips; r.tiles_y = pl.tiles_y; r.total_waves = pl.total_waves;
+      // Block order and cache policy: hardware order, cached loads.  Blocks are dealt round-robin over the 8 XCDs, so with
+      // tiles numbered (strip, row tile, plane) an XCD sees the SAME few (strip, row tile) positions of every plane: its
+      // share of the noise plane is a few hundred KB that stays in its L2 for all planes, where the XCD-contiguous order
+      // of path 1 re-fetches it per plane (FETCH_SIZE of the fused headline blur, standalone: 1.68x the input with
+      // XCD-contiguous order, 1.51x with nt loads on top, 1.12x in hardware order; plain blur 1.08x either way — the
+      // <.., NT, XCD> instantiations those numbers came from are no longer built).
+      if (a.ep) hipLaunchKernelGGL((ufd_dmaring_f32<true, false, false>), g, b, pl.lds, s, r);
+      else hipLaunchKernelGGL((ufd_dmaring_f32<false, false, false>), g, b, pl.lds, s, r);
+    } break;
+    case 2: {
+      PTParams t{p.major, p.in_h, p.in_w, p.out_h, p.out_w, p.pad_x0, p.pad_y0, p.kh, p.kw, pl.pb};
+      t.in_plane_stride = p.in_plane_stride; t.in_row_stride = p.in_row_stride;
+      set_epilogue(t, a.ep);
+      if (a.ep) hipLaunchKernelGGL(ufd_planetile_f32<true>, g, b, pl.lds, s, in, kern, out, t);
+      else hipLaunchKernelGGL(ufd_planetile_f32<false>, g, b, pl.lds, s, in, kern, out, t);
+    } break;
+    default: {   // 3; one instantiation per parity of the padding
+      U2Params t{p.major, p.in_h, p.in_w, p.out_h, p.out_w, p.pad_x0, p.pad_y0, p.kh, p.kw, pl.bw, pl.bh};
+      switch ((p.pad_y0 & 1) * 2 + (p.pad_x0 & 1)) {
+        case 0: hipLaunchKernelGGL((ufd_up2_f32<0, 0>), g, b, 0, s, in, kern, out, t); break;
+        case 1: hipLaunchKernelGGL((ufd_up2_f32<0, 1>), g, b, 0, s, in, kern, out, t); break;
+        case 2: hipLaunchKernelGGL((ufd_up2_f32<1, 0>), g, b, 0, s, in, kern, out, t); break;
+        default: hipLaunchKernelGGL((ufd_up2_f32<1, 1>), g, b, 0, s, in, kern, out, t); break;
+      }
+    }
   }
   return fmgan_check_launch();
 }
 
-int pick_path(int dtype, const UfdParams& p) {
-  if (rowmarch_ok(dtype, p)) return 1;
-  if (planetile_ok(dtype, p)) return 2;
-  if (up2_ok(dtype, p)) return 3;
-  return 0;
+int run_ufd(const UfdArgs& a, void* stream) {
+  UfdPlan pl;
+  const int st = plan_ufd(a, pl);
+  return st != FMGAN_OK || pl.empty ? st : launch_ufd(pl, a, (hipStream_t)stream);
 }
 
-int validate(int dtype, int major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x,
-             int down_y) {
-  if (dtype != FMGAN_F32 && dtype != FMGAN_F64 && dtype != FMGAN_F16) return FMGAN_EUNSUPPORTED;
-  if (major < 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 || kw <= 0) return FMGAN_EINVAL;
-  if (up_x <= 0 || up_y <= 0 || down_x <= 0 || down_y <= 0) return FMGAN_EINVAL;
-  return FMGAN_OK;
+// What a select function answers: the kernel that the launch with these arguments runs, else the launch's status.
+int query_ufd(UfdArgs a) {
+  a.query = true;
+  UfdPlan pl;
+  const int st = plan_ufd(a, pl);
+  return st != FMGAN_OK ? st : pl.kernel;
 }
 
 }  // namespace
@@ -842,55 +909,17 @@ extern "C" int fmgan_upfirdn2d_out_size(int in_h, int in_w, int kernel_h, int ke
 extern "C" int fmgan_upfirdn2d_select(int dtype, int major, int in_h, int in_w, int minor, int kernel_h, int kernel_w,
                                       int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0,
                                       int pad_y1) {
-  int st = validate(dtype, major, in_h, in_w, minor, kernel_h, kernel_w, up_x, up_y, down_x, down_y);
-  if (st != FMGAN_OK) return st;
-  UfdParams p{major, in_h, in_w, minor, kernel_h, kernel_w, up_x, up_y, down_x, down_y, pad_x0, pad_y0, 0, 0,
-              (long long)in_h * in_w * minor, in_w * minor};
-  fmgan_upfirdn2d_out_size(in_h, in_w, kernel_h, kernel_w, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1,
-                           &p.out_h, &p.out_w);
-  if (p.out_h <= 0 || p.out_w <= 0) return FMGAN_EINVAL;
-  return pick_path(dtype, p);
+  return query_ufd({dtype, major, in_h, in_w, minor, (long long)in_h * in_w * minor, in_w * minor, kernel_h, kernel_w,
+                    up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, -1});
 }
 
 extern "C" int fmgan_upfirdn2d_strided(int dtype, const void* input, const void* kernel, void* out, int major,
                                        int in_h, int in_w, int minor, long long in_plane_stride, int in_row_stride,
                                        int kernel_h, int kernel_w, int up_x, int up_y, int down_x, int down_y,
                                        int pad_x0, int pad_x1, int pad_y0, int pad_y1, int force_path, void* stream) {
-  int st = validate(dtype, major, in_h, in_w, minor, kernel_h, kernel_w, up_x, up_y, down_x, down_y);
-  if (st != FMGAN_OK) return st;
-  if (in_row_stride < in_w * minor || in_plane_stride < (long long)(in_h - 1) * in_row_stride + (long long)in_w * minor)
-    return FMGAN_EINVAL;
-  UfdParams p{major, in_h, in_w, minor, kernel_h, kernel_w, up_x, up_y, down_x, down_y, pad_x0, pad_y0, 0, 0,
-              in_plane_stride, in_row_stride};
-  fmgan_upfirdn2d_out_size(in_h, in_w, kernel_h, kernel_w, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1,
-                           &p.out_h, &p.out_w);
-  if (p.out_h <= 0 || p.out_w <= 0) return FMGAN_EINVAL;
-  if (major == 0) return FMGAN_OK;
-  if (!input || !kernel || !out) return FMGAN_EINVAL;
-  if ((long long)in_h * in_row_stride > 0x7fffffffLL || (long long)p.out_h * p.out_w * minor > 0x7fffffffLL)
-    return FMGAN_EOVERFLOW;
-  hipStream_t s = (hipStream_t)stream;
-  int path = force_path;
-  if (path < 0) path = pick_path(dtype, p);
-  switch (path) {
-    case 0:
-      if (dtype == FMGAN_F32) return launch_generic<float>(input, kernel, out, p, s);
-      if (dtype == FMGAN_F64) return launch_generic<double>(input, kernel, out, p, s);
-      return launch_generic<__half>(input, kernel, out, p, s);
-    case 1:
-    case 4:
-    case 5:
-      if (!rowmarch_ok(dtype, p)) return FMGAN_EUNSUPPORTED;
-      return launch_rowmarch(input, kernel, out, p, s, nullptr, path);
-    case 2:
-      if (!planetile_ok(dtype, p)) return FMGAN_EUNSUPPORTED;
-      return launch_planetile(input, kernel, out, p, s);
-    case 3:
-      if (!up2_ok(dtype, p)) return FMGAN_EUNSUPPORTED;
-      return launch_up2(input, kernel, out, p, s);
-    default:
-      return FMGAN_EUNSUPPORTED;
-  }
+  return run_ufd({dtype, major, in_h, in_w, minor, in_plane_stride, in_row_stride, kernel_h, kernel_w, up_x, up_y,
+                  down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, force_path, input, kernel, out},
+                 stream);
 }
 
 extern "C" int fmgan_blur_noise_bias_act_path_f32(const float* input, const float* kernel, float* out, int batch,
@@ -899,49 +928,19 @@ extern "C" int fmgan_blur_noise_bias_act_path_f32(const float* input, const floa
                                                   int pad_y0, int pad_y1, const float* noise, const float* noise_weight,
                                                   const float* bias, int noise_batch, float alpha, float act_scale,
                                                   int force_path, void* stream) {
-  if (force_path != -1 && force_path != 1 && force_path != 4 && force_path != 5) return FMGAN_EUNSUPPORTED;
-  if (batch < 0 || channels <= 0) return FMGAN_EINVAL;
-  const long long major = (long long)batch * channels;
-  if (major > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-  int st = validate(FMGAN_F32, (int)major, in_h, in_w, 1, kernel_h, kernel_w, 1, 1, 1, 1);
-  if (st != FMGAN_OK) return st;
-  if (in_row_stride < in_w || in_plane_stride < (long long)(in_h - 1) * in_row_stride + in_w) return FMGAN_EINVAL;
-  if (noise && noise_batch != 1 && noise_batch != batch) return FMGAN_EINVAL;
-  UfdParams p{(int)major, in_h, in_w, 1, kernel_h, kernel_w, 1, 1, 1, 1, pad_x0, pad_y0, 0, 0, in_plane_stride,
-              in_row_stride};
-  fmgan_upfirdn2d_out_size(in_h, in_w, kernel_h, kernel_w, 1, 1, 1, 1, pad_x0, pad_x1, pad_y0, pad_y1, &p.out_h, &p.out_w);
-  if (p.out_h <= 0 || p.out_w <= 0) return FMGAN_EINVAL;
-  if (major == 0) return FMGAN_OK;
-  if (!input || !kernel || !out) return FMGAN_EINVAL;
-  if ((long long)in_h * in_row_stride > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-  UfdEpilogue ep{noise, noise_weight, bias, channels, noise_batch, alpha, act_scale};
-  if (!rowmarch_ok(FMGAN_F32, p)) {
-    // small planes (the 4^2..32^2 upsampling layers): the plane-tile kernel reads the aligned-row layout and applies
-    // the epilogue in its store
-    if (force_path > 1 || !planetile_ok(FMGAN_F32, p)) return FMGAN_EUNSUPPORTED;
-    return launch_planetile(input, kernel, out, p, (hipStream_t)stream, &ep);
-  }
-  return launch_rowmarch(input, kernel, out, p, (hipStream_t)stream, &ep, force_path);
+  const UfdEpilogue ep{noise, noise_weight, bias, channels, noise_batch, alpha, act_scale};
+  return run_ufd({FMGAN_F32, 0, in_h, in_w, 1, in_plane_stride, in_row_stride, kernel_h, kernel_w, 1, 1, 1, 1, pad_x0,
+                  pad_x1, pad_y0, pad_y1, force_path, input, kernel, out, &ep, batch},
+                 stream);
 }
 
-// Which kernel fmgan_blur_noise_bias_act_f32 would run for these arguments (host logic, nothing is launched):
-// 5 = LDS-DMA ring (path 1b), 1 = register row-march (path 1), 2 = plane-tile, FMGAN_EUNSUPPORTED = none.
 extern "C" int fmgan_blur_noise_bias_act_select(const float* input, const float* out, const float* noise, int batch,
                                                 int channels, int in_h, int in_w, long long in_plane_stride,
                                                 int in_row_stride, int kernel_h, int kernel_w, int pad_x0, int pad_x1,
                                                 int pad_y0, int pad_y1) {
-  if (batch <= 0 || channels <= 0) return FMGAN_EINVAL;
-  const long long major = (long long)batch * channels;
-  if (major > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-  int st = validate(FMGAN_F32, (int)major, in_h, in_w, 1, kernel_h, kernel_w, 1, 1, 1, 1);
-  if (st != FMGAN_OK) return st;
-  UfdParams p{(int)major, in_h, in_w, 1, kernel_h, kernel_w, 1, 1, 1, 1, pad_x0, pad_y0, 0, 0, in_plane_stride,
-              in_row_stride};
-  fmgan_upfirdn2d_out_size(in_h, in_w, kernel_h, kernel_w, 1, 1, 1, 1, pad_x0, pad_x1, pad_y0, pad_y1, &p.out_h, &p.out_w);
-  if (p.out_h <= 0 || p.out_w <= 0) return FMGAN_EINVAL;
-  UfdEpilogue ep{noise, nullptr, nullptr, channels, 1, 0.f, 1.f};
-  if (rowmarch_ok(FMGAN_F32, p)) return dmaring_ok(input, out, p, &ep) ? 5 : 1;
-  return planetile_ok(FMGAN_F32, p) ? 2 : FMGAN_EUNSUPPORTED;
+  const UfdEpilogue ep{noise, nullptr, nullptr, channels, 1, 0.f, 1.f};
+  return query_ufd({FMGAN_F32, 0, in_h, in_w, 1, in_plane_stride, in_row_stride, kernel_h, kernel_w, 1, 1, 1, 1, pad_x0,
+                    pad_x1, pad_y0, pad_y1, -1, input, nullptr, (void*)out, &ep, batch});
 }
 
 extern "C" int fmgan_blur_noise_bias_act_f32(const float* input, const float* kernel, float* out, int batch,

@@ -553,10 +553,9 @@ def aligned_rows_buffer(b, c, oh, ow, pad0, device):
     and every wave-wide 1 KiB row load covers exactly 8 cache lines.  Measured on the 1024^2 blur (MI355X):
     contiguous 2W+1 rows 512-527 us, 16-byte-aligned rows 498 us, line-aligned rows 438-450 us (= copy speed).
     Returns (storage, data_ptr of logical element (0,0,0,0), plane stride, row stride) — strides in elements."""
-    off = pad0 % 4
-    rs = (ow + off + 31) // 32 * 32
-    buf = torch.empty((b * c, oh, rs), dtype=torch.float32, device=device)
-    return buf, buf.data_ptr() + 4 * off, oh * rs, rs
+    shape, off, ps, rs = aligned_rows_shape(b, c, oh, ow, pad0)
+    buf = torch.empty(shape, dtype=torch.float32, device=device)
+    return buf, buf.data_ptr() + 4 * off, ps, rs
 
 
 # Contraction of modconv2d: 'f32' (default, the parity path: v_mfma_f32_32x32x2_f32), 'bf16' (bf16 MFMA operands, fp32
@@ -695,35 +694,22 @@ def modconv2d(x, wt, style, demod, mode, noise=None, noise_weight=None, bias=Non
         out = None
         out_ptr, ops, ors = strided_out
     nz = noise.contiguous() if noise is not None else None
-    prec = precision or _mc_precision
-    if prec == 'bf16x3' and lib().fmgan_modconv2d_bf16x3_supported(b, cin, cout, h, w, mode):
-        wts = modconv_weight_to_bf16x3(wt)
-        with on_device(x) as stream:
-            tok = _observer.begin('modconv2d_bf16x3', (b, cin, cout, h, w, mode))
-            check(lib().fmgan_modconv2d_bf16x3(fp(x), ptr(wts), fp(style), fp(demod), out_ptr, b, cin, cout, h, w, mode,
-                                               fp(nz), fp(noise_weight), fp(bias), 1 if nz is None else nz.shape[0],
-                                               int(bool(fuse_act)), float(alpha), float(act_scale), ops, ors, stream),
-                  'modconv2d_bf16x3')
-            _observer.end(tok)
-        return out
-    if prec == 'bf16' and lib().fmgan_modconv2d_bf16_supported(b, cin, cout, h, w, mode):
-        wtb = modconv_weight_to_bf16(wt)
-        with on_device(x) as stream:
-            tok = _observer.begin('modconv2d_bf16', (b, cin, cout, h, w, mode))
-            check(lib().fmgan_modconv2d_bf16(fp(x), ptr(wtb), fp(style), fp(demod), out_ptr, b, cin, cout, h, w, mode,
-                                             fp(nz), fp(noise_weight), fp(bias), 1 if nz is None else nz.shape[0],
-                                             int(bool(fuse_act)), float(alpha), float(act_scale), ops, ors, stream),
-                  'modconv2d_bf16')
-            _observer.end(tok)
-        return out
-    ws_bytes = lib().fmgan_modconv2d_workspace_bytes(b, cin, cout, h, w, mode)
-    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
+    prec, L = precision or _mc_precision, lib()
+    # one launch for the three contractions: the name (also the observer's), the per-call weight image, the extra arguments
+    if prec == 'bf16x3' and L.fmgan_modconv2d_bf16x3_supported(b, cin, cout, h, w, mode):
+        name, wtb, extra = 'modconv2d_bf16x3', modconv_weight_to_bf16x3(wt), ()
+    elif prec == 'bf16' and L.fmgan_modconv2d_bf16_supported(b, cin, cout, h, w, mode):
+        name, wtb, extra = 'modconv2d_bf16', modconv_weight_to_bf16(wt), ()
+    else:
+        ws_bytes = L.fmgan_modconv2d_workspace_bytes(b, cin, cout, h, w, mode)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
+        name, wtb, extra = 'modconv2d', None, (fp(ws), ws_bytes)
+    launch = getattr(L, 'fmgan_' + name + ('_f32' if wtb is None else ''))
     with on_device(x) as stream:
-        tok = _observer.begin('modconv2d', (b, cin, cout, h, w, mode))
-        check(lib().fmgan_modconv2d_f32(fp(x), fp(wt), fp(style), fp(demod), out_ptr, b, cin, cout, h, w, mode,
-                                        fp(nz), fp(noise_weight), fp(bias), 1 if nz is None else nz.shape[0],
-                                        int(bool(fuse_act)), float(alpha), float(act_scale), ops, ors, fp(ws), ws_bytes,
-                                        stream), 'modconv2d')
+        tok = _observer.begin(name, (b, cin, cout, h, w, mode))
+        check(launch(fp(x), fp(wt) if wtb is None else ptr(wtb), fp(style), fp(demod), out_ptr, b, cin, cout, h, w, mode,
+                     fp(nz), fp(noise_weight), fp(bias), 1 if nz is None else nz.shape[0], int(bool(fuse_act)),
+                     float(alpha), float(act_scale), ops, ors, *extra, stream), name)
         _observer.end(tok)
     return out
 

@@ -75,18 +75,23 @@ def _kernel_conv(u, w4, mode, kind):
     return _native.modconv2d(u, wt, _ones(u.shape[0], u.shape[1], u.device), None, mode)
 
 
+def _miopen_wgrad(u, g, mode, k=3):
+    """G_m(u, g) -> [cout, cin, k, k] on MIOpen's fp32 wgrad: where this repo's kernel is off or declines the shape."""
+    cout, cin = g.shape[1], u.shape[1]
+    if mode == 0:
+        return torch.nn.grad.conv2d_weight(u, (cout, cin, k, k), g, padding=k // 2)
+    if mode == 1:   # y = conv_transpose2d(u, W^T, stride 2): adjoint of conv2d(., W^T, stride 2)
+        return torch.nn.grad.conv2d_weight(g, (cin, cout, k, k), u, stride=2).transpose(0, 1)
+    return torch.nn.grad.conv2d_weight(u, (cout, cin, k, k), g, stride=2)
+
+
 def _wgrad(u, g, mode):
     """G_m(u, g) -> [cout, cin, 3, 3].  mode 0 on this repo's MFMA wgrad kernel when enabled, else MIOpen's fp32 wgrad."""
-    cout, cin = g.shape[1], u.shape[1]
     if (HIP_WGRAD >= 2 or (HIP_WGRAD == 1 and mode == 0)) and u.dtype == torch.float32:
-        gw = _native.modconv_wgrad(g, None, u, _ones(u.shape[0], cin, u.device), 1.0, fast_only=True, mode=mode)
+        gw = _native.modconv_wgrad(g, None, u, _ones(u.shape[0], u.shape[1], u.device), 1.0, fast_only=True, mode=mode)
         if gw is not None:
             return gw
-    if mode == 0:
-        return torch.nn.grad.conv2d_weight(u, (cout, cin, 3, 3), g, padding=1)
-    if mode == 1:   # y = conv_transpose2d(u, W^T, stride 2): adjoint of conv2d(., W^T, stride 2)
-        return torch.nn.grad.conv2d_weight(g, (cin, cout, 3, 3), u, stride=2).transpose(0, 1)
-    return torch.nn.grad.conv2d_weight(u, (cout, cin, 3, 3), g, stride=2)
+    return _miopen_wgrad(u, g, mode)
 
 
 _ADJ = {0: (0, 1), 1: (2, 2), 2: (1, 2)}      # mode -> (kernel mode, weight layout kind) of D_m
@@ -241,12 +246,7 @@ class ModulatedConv2dFunction(Function):
             gw = _native.modconv_wgrad(go, d, x, s, scale, fast_only=True, mode=mode) if hip_w else None
             if gw is None:
                 gz = go * d[:, :, None, None] if demodulate else go
-                u = x * s[:, :, None, None]
-                if mode == 0:
-                    gw = torch.nn.grad.conv2d_weight(u, (cout, cin, k, k), gz, padding=k // 2)
-                else:   # y = conv_transpose2d(u, W^T, stride 2) is the adjoint of conv2d(., W^T, stride 2)
-                    gw = torch.nn.grad.conv2d_weight(gz, (cin, cout, k, k), u, stride=2).transpose(0, 1)
-                gw = gw * scale
+                gw = _miopen_wgrad(x * s[:, :, None, None], gz, mode, k) * scale
             if gq is not None:
                 gw = gw + (2.0 * scale * scale) * w4 * (gq.t() @ s.square())[:, :, None, None]
             gw = gw.reshape(weight.shape)

@@ -53,9 +53,13 @@ extern "C" {
 int         fmgan_abi_version(void);
 const char *fmgan_status_string(int status);
 
-/* Which upfirdn2d kernel `fmgan_upfirdn2d` would pick for these arguments:
+/* Which upfirdn2d kernel `fmgan_upfirdn2d` runs for these arguments:
  * 0 generic, 1 row-march (up=down=1, wide rows), 2 LDS plane-tile (up=down=1,
- * small planes), 3 up=2 polyphase.  Pure host logic, no GPU needed.
+ * small planes), 3 up=2 polyphase.  Pure host logic, no GPU needed: the launch's
+ * own plan with the launch left out.  A kernel id is returned exactly when the
+ * launch with these arguments (and valid pointers) runs that kernel; arguments
+ * the launch refuses return the launch's status (< 0).  The query has no
+ * addresses, so 1 stands for both row-march variants (path 1 and 1b).
  * `force_path` in fmgan_upfirdn2d uses the same numbering (-1 = automatic). */
 int fmgan_upfirdn2d_select(int dtype, int major, int in_h, int in_w, int minor,
                            int kernel_h, int kernel_w, int up_x, int up_y,
@@ -119,8 +123,11 @@ int fmgan_blur_noise_bias_act_f32(const float *input, const float *kernel, float
                                   const float *noise, const float *noise_weight, const float *bias,
                                   int noise_batch, float alpha, float act_scale, void *stream);
 /* Which kernel serves a fused-blur call with these arguments (host logic, nothing is launched): 5 = LDS-DMA ring
- * (path 1b), 1 = register row-march (path 1), 2 = plane-tile, FMGAN_EUNSUPPORTED = none.  bench.py names the kernel of
- * its roofline object from this. */
+ * (path 1b), 1 = register row-march (path 1), 2 = plane-tile.  It is the launch's own plan with the launch left out: a
+ * positive id is returned exactly when fmgan_blur_noise_bias_act_f32 with these arguments runs that kernel; otherwise the
+ * launch's status (FMGAN_EUNSUPPORTED: no kernel serves the shape; FMGAN_EINVAL / FMGAN_EOVERFLOW as the launch, and
+ * FMGAN_EINVAL for batch <= 0, where the launch of an empty batch is a no-op).  Path 1b is chosen by address: called
+ * without addresses the answer is 1 or 2, never 5.  bench.py names the kernel of its roofline object from this. */
 int fmgan_blur_noise_bias_act_select(const float *input, const float *out, const float *noise,
                                      int batch, int channels, int in_h, int in_w,
                                      long long in_plane_stride, int in_row_stride,

@@ -383,6 +383,55 @@ def test_fused_blur_selection_declines_firs_wider_than_four_taps():
         assert not _native.blur_noise_bias_act_serves(b, c, h, h, ps, rs, (5, 5), (2, 1))
 
 
+def test_upfirdn2d_selects_return_the_launch_status():
+    """Both select functions are the launch's own plan with the launch left out: arguments the launch refuses get the
+    launch's status, not a kernel id.  Every call here is refused before any HIP call (the pointers are placeholders)."""
+    L = _lib()
+    fake = ctypes.c_void_p(0x1000)
+    EINVAL, EOVER = -1, -4
+
+    def fused(b, c, h, w, ps, rs):
+        sel = L.fmgan_blur_noise_bias_act_select(None, None, None, b, c, h, w, ps, rs, 4, 4, 1, 1, 1, 1)
+        run = L.fmgan_blur_noise_bias_act_path_f32(fake, fake, fake, b, c, h, w, ps, rs, 4, 4, 1, 1, 1, 1, None, None, None, 1,
+                                                   0.2, 1.4, -1, None)
+        return sel, run
+    assert fused(1, 4, 129, 129, 129 * 129, 100) == (EINVAL, EINVAL)             # row stride below in_w
+    assert fused(1, 4, 129, 129, 10, 129) == (EINVAL, EINVAL)                    # plane stride below one plane
+    assert fused(1, 1, 70000, 129, 70000 * 32768, 32768) == (EOVER, EOVER)       # plane above 2^31 elements
+    big = (0, 1, 70000, 40000, 1, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1)                  # f32 [1, 70000, 40000, 1]
+    assert L.fmgan_upfirdn2d_select(*big) == EOVER
+    assert L.fmgan_upfirdn2d(0, fake, fake, fake, *big[1:], -1, None) == EOVER
+    # what the selects answered before for arguments the launch accepts, they still answer
+    assert L.fmgan_upfirdn2d_select(0, 256, 1025, 1025, 1, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1) == 1
+    assert L.fmgan_upfirdn2d_select(0, 1024, 9, 9, 1, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1) != 1
+    assert L.fmgan_upfirdn2d_select(1, 256, 1025, 1025, 1, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1) == 0
+    assert L.fmgan_upfirdn2d_select(0, 1, 0, 8, 1, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1) == -1
+    assert L.fmgan_upfirdn2d_select(7, 1, 8, 8, 1, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1) == -2
+    from op import _native
+    for b, c, h in ((8, 512, 17), (8, 256, 129), (8, 32, 1025)):
+        _, off, ps, rs = _native.aligned_rows_shape(b, c, h, h, 1)
+        assert L.fmgan_blur_noise_bias_act_select(None, None, None, b, c, h, h, ps, rs, 4, 4, 1, 1, 1, 1) == (2 if h < 64 else 1)
+        _, off, ps, rs = _native.aligned_rows_shape(b, c, h, h, 2)
+        assert L.fmgan_blur_noise_bias_act_select(None, None, None, b, c, h, h, ps, rs, 5, 5, 2, 1, 2, 1) == -2
+    assert L.fmgan_blur_noise_bias_act_select(None, None, None, 0, 4, 129, 129, 129 * 129, 129, 4, 4, 1, 1, 1, 1) == EINVAL
+
+
+def test_bf16_launches_ask_supported():
+    """fmgan_modconv2d_bf16(_x3)_supported is the one statement of which shapes the bf16 contractions serve, and the
+    launch asks it: for every refused shape, and for mode 2 on the split-operand entry, `_supported` is 0 and the launch
+    (placeholder pointers, nothing reaches HIP) returns FMGAN_EUNSUPPORTED."""
+    L = _lib()
+    fake = ctypes.c_void_p(0x1000)
+    refused = ((2, 12, 32, 64, 64, 0), (2, 32, 48, 64, 64, 0), (2, 32, 32, 16, 16, 0), (2, 512, 512, 4, 4, 1),
+               (1, 32, 32, 40, 40, 2))
+    for name, cfgs in (('bf16', refused), ('bf16x3', refused + ((2, 32, 32, 65, 65, 2),))):
+        supported, launch = getattr(L, f'fmgan_modconv2d_{name}_supported'), getattr(L, f'fmgan_modconv2d_{name}')
+        for cfg in cfgs:
+            assert supported(*cfg) == 0, (name, cfg)
+            assert launch(fake, fake, fake, None, fake, *cfg, None, None, None, 1, 0, 0.2, 1.4, 0, 0, None) == -2, (name, cfg)
+    assert L.fmgan_modconv2d_bf16_supported(2, 32, 32, 65, 65, 2) == 1          # mode 2 is the bf16 entry's alone
+
+
 # ------------------------------------------------------------------------ fmgan_modconv2d_select / fmgan_modconv2d_tiles
 def test_modconv_select_and_tiles_are_host_logic():
     """Which tile, which split: both answers come without a device, invalid arguments return the launch's status, the tile

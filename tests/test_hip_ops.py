@@ -215,6 +215,50 @@ def test_dma_ring_blur_equals_register_row_march(cfg):
     np.testing.assert_allclose(res['1'][0][:1].cpu().numpy().reshape(ref.shape), ref, **OP_TOL)
 
 
+@pytest.mark.parametrize('in_h,in_w,taps,shift,want', [
+    (9, 257, 4, 0, 5),      # out 8 x 256, aligned rows and pointers, a noise plane: the LDS-DMA ring
+    (9, 257, 4, 1, 1),      # the same planes one float further on: the ring's alignment rule fails, register row-march
+    (9, 65, 4, 0, 1),       # out 8 x 64: the narrowest row-march plane, too narrow for the ring
+    (9, 63, 4, 0, 2),       # out 8 x 62, 567 input elements: plane-tile
+    (300, 50, 4, 0, -2),    # plane above 12288 elements with rows below 64: no fused kernel
+    (9, 257, 5, 0, -2),     # a 5 x 5 FIR: no fused kernel
+], ids=['ring', 'ring_misaligned', 'rowmarch', 'planetile', 'tall_narrow', 'fir5'])
+def test_fused_blur_select_names_the_kernel_that_runs(in_h, in_w, taps, shift, want):
+    """fmgan_blur_noise_bias_act_select is the launch's own plan: at the smallest shape that reaches each answer it names
+    the kernel that then runs (5 exactly when insisting on path 1b is served, -2 exactly when the automatic launch
+    declines), and what runs equals the two-pass form (generic path 0, then fmgan_noise_bias_act) bit for bit."""
+    from op import _native
+    b, c, pad = 1, 2, (1, 1)
+    k = cases.make_fir(('rand', taps, taps, 23)).to(dev())
+    oh, ow = in_h + 2 - taps + 1, in_w + 2 - taps + 1
+    x = synth.tensor(f'sel/{in_h}x{in_w}/x', (b * c, in_h, in_w)).to(dev())
+    nz = synth.tensor(f'sel/{in_h}x{in_w}/n', (1, 1, oh, ow)).to(dev())
+    nw = torch.tensor([0.29], device=dev())
+    bias = synth.tensor(f'sel/{in_h}x{in_w}/b', (c,)).to(dev())
+    buf, p0, ps, rs = _native.aligned_rows_buffer(b, c, in_h, in_w, pad[0], dev())
+    buf.fill_(float('nan'))
+    off = pad[0] % 4 + shift
+    assert off + in_w <= rs
+    buf[:, :, off:off + in_w] = x
+    p0 += 4 * shift
+    out = torch.empty((b, c, oh, ow), dtype=torch.float32, device=dev())
+    sel = _native.lib().fmgan_blur_noise_bias_act_select(p0, out.data_ptr(), nz.data_ptr(), b, c, in_h, in_w, ps, rs,
+                                                         taps, taps, 1, 1, 1, 1)
+    assert sel == want
+    args = (p0, dev(), b, c, in_h, in_w, ps, rs, k, pad, nz, nw, bias, 0.2, 2 ** 0.5)
+    ring = _native.blur_noise_bias_act(*args, force_path=5, out=out)
+    assert (sel == 5) == (ring is not None)
+    y2 = _native.upfirdn2d_strided(p0, dev(), b * c, in_h, in_w, ps, rs, k, 1, 1, 1, 1, force_path=0).view(b, c, oh, ow)
+    ref = _native.noise_bias_act(y2, nz, nw, bias, 0.2, 2 ** 0.5)
+    if ring is not None:
+        assert torch.equal(ring, ref)
+        out.fill_(float('nan'))
+    auto = _native.blur_noise_bias_act(*args, out=out)
+    assert (sel == -2) == (auto is None)
+    if auto is not None:
+        assert torch.equal(auto, ref)
+
+
 def test_modconv_strided_output_matches_contiguous():
     from op import _native
     for (b, cin, cout, h, w) in ((2, 8, 40, 16, 16), (1, 16, 130, 9, 7), (9, 12, 20, 4, 4)):
