@@ -1,4 +1,5 @@
 """IR / IR-SE building blocks of the pSp W+ encoder (reference: psp_encoder_model/encoders/helpers.py)."""
+import os
 from collections import namedtuple
 
 import torch
@@ -131,3 +132,118 @@ class bottleneck_IR_SE(Module):
 
     def forward(self, x):
         return self.res_layer(x) + self.shortcut_layer(x)
+
+
+# ----------------------------------------------------------------------------- inference body on the fused glue kernels
+# Inference on the GPU (no_grad, fp32, channels_last): everything between a unit's MIOpen convolutions except the PReLU
+# between its two 3x3 convolutions runs on four HIP kernels (csrc/encoder_glue.hip) — per unit PReLU, se_pool, se_gate and
+# ir_tail instead of 11-12 aten / MIOpen launches, and one bn_prelu after the input convolution.  Every BatchNorm is
+# evaluated in-kernel from the module's live vectors on every launch; modules, state_dict names and the training path
+# are untouched.  FMGAN_NO_ENCODER_FUSE=1 (or ENCODER_FUSE = False) keeps the module path.
+ENCODER_FUSE = os.environ.get('FMGAN_NO_ENCODER_FUSE', '0') != '1'
+
+
+class _NotServed(Exception):
+    """A glue kernel declined a shape: the caller runs the modules instead."""
+
+
+def _served(res):
+    if res is None:
+        raise _NotServed
+    return res
+
+
+def _bn(m):
+    return m.running_mean, m.running_var, m.weight, m.bias, m.eps
+
+
+def _bn_fusable(m, c):
+    return (isinstance(m, BatchNorm2d) and not m.training and m.running_mean is not None and m.weight is not None
+            and m.num_features == c and m.weight.dtype == torch.float32 and m.running_mean.dtype == torch.float32)
+
+
+def _width_fusable(c):
+    return c % 4 == 0 and c <= 1024
+
+
+def _unit_fusable(unit):
+    if not isinstance(unit, (bottleneck_IR, bottleneck_IR_SE)):
+        return False
+    res, sc = unit.res_layer, unit.shortcut_layer
+    cin, depth = res[1].in_channels, res[3].out_channels
+    if not (_width_fusable(cin) and _width_fusable(depth) and _bn_fusable(res[0], cin) and _bn_fusable(res[4], depth)
+            and res[2].weight.numel() == depth):
+        return False
+    if len(res) == 6 and res[5].fc1.out_channels > 256:
+        return False
+    if isinstance(sc, MaxPool2d):
+        return sc.kernel_size == 1 and sc.padding == 0 and sc.dilation == 1 and isinstance(sc.stride, int)
+    return _bn_fusable(sc[1], depth)
+
+
+def _input_fusable(x):
+    return (ENCODER_FUSE and not torch.is_grad_enabled() and not torch.is_autocast_enabled() and x.is_cuda
+            and x.dtype == torch.float32 and x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous())
+
+
+def _fused_unit(unit, x, xn, bn_next, sub=None):
+    """One unit on the glue kernels.  x: the unit's input, xn = BN_in(x), sub: x already subsampled by the unit's
+    MaxPool2d(1, stride) shortcut (x may then be None).  Returns (out, bn_next(out) or None)."""
+    from op import _native
+    res, sc = unit.res_layer, unit.shortcut_layer
+    r = res[3](res[2](res[1](xn)))
+    gate = None
+    if len(res) == 6:
+        se = res[5]
+        partial = _served(_native.se_pool(r))
+        gate = _served(_native.se_gate(partial, r.shape[2] * r.shape[3], _bn(res[4]), se.fc1.weight, se.fc2.weight))
+    if not isinstance(sc, MaxPool2d):
+        return _served(_native.ir_tail(r, _bn(res[4]), gate, sc[0](x), 1, _bn(sc[1]), bn_next))
+    if sub is not None:
+        return _served(_native.ir_tail(r, _bn(res[4]), gate, sub, 1, None, bn_next))
+    return _served(_native.ir_tail(r, _bn(res[4]), gate, x, sc.stride, None, bn_next))
+
+
+def _fused_units(body, x, xn, sub, taps):
+    feats = {}
+    for i, unit in enumerate(body):
+        bn_next = _bn(body[i + 1].res_layer[0]) if i + 1 < len(body) else None
+        x, xn = _fused_unit(unit, x, xn, bn_next, sub)
+        sub = None
+        if i in taps:
+            feats[i] = x
+    return x, feats
+
+
+def fused_units(body, x, taps=()):
+    """The units of `body` (a Sequential of bottleneck_IR / bottleneck_IR_SE) on the glue kernels: (output, {tap index:
+    that unit's output}), or None when the fused path does not apply (training, autograd, CPU, NCHW, autocast, a width the
+    kernels do not serve): the caller then runs the modules.  The first unit's BN_in runs as a module here."""
+    if not (_input_fusable(x) and len(body) > 0 and all(_unit_fusable(u) for u in body)):
+        return None
+    try:
+        return _fused_units(body, x, body[0].res_layer[0](x), None, taps)
+    except _NotServed:
+        return None
+
+
+def fused_body(input_layer, body, x, taps=()):
+    """input_layer (conv, BatchNorm2d, PReLU) and the units of `body` on the glue kernels; as fused_units.  The input
+    layer's bn_prelu also writes the first unit's BN_in and, when that unit's shortcut is MaxPool2d(1, stride), its
+    subsampled shortcut — the full-size activation itself is then never written."""
+    from op import _native
+    if not (_input_fusable(x) and len(body) > 0 and all(_unit_fusable(u) for u in body) and len(input_layer) == 3):
+        return None
+    conv, bn, act = input_layer
+    c = conv.out_channels
+    if not (isinstance(conv, Conv2d) and _width_fusable(c) and _bn_fusable(bn, c) and isinstance(act, nn.PReLU)
+            and act.weight.numel() == c and body[0].res_layer[1].in_channels == c):
+        return None
+    pool = body[0].shortcut_layer
+    stride = pool.stride if isinstance(pool, MaxPool2d) else 0
+    try:
+        y, yn, sub = _served(_native.bn_prelu(conv(x), _bn(bn), act.weight, want_y=stride == 0,
+                                              bn_next=_bn(body[0].res_layer[0]), sub_stride=stride))
+        return _fused_units(body, y, yn, sub, taps)
+    except _NotServed:
+        return None

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 from torch import nn
 from torch.nn import BatchNorm2d, Conv2d, Module, Sequential
 
+from . import helpers
 from .helpers import PReLU, bottleneck_IR, bottleneck_IR_SE, get_blocks
 from stylegan2 import EqualLinear
 from op import fused_leaky_relu
@@ -195,13 +196,18 @@ class GradualStyleEncoder(Module):
         if self.channels_last and x.is_cuda:
             self._to_channels_last()
             x = x.contiguous(memory_format=torch.channels_last)
-        x = self.input_layer(x)
         t1, t2, t3 = _TAPS[self.num_layers]
-        feats = {}
-        for i, unit in enumerate(self.body):
-            x = unit(x)
-            if i in (t1, t2, t3):
-                feats[i] = x
+        # inference: BN / SE / shortcut / add of the units on the fused glue kernels (helpers.fused_body); None: not applicable
+        fused = helpers.fused_body(self.input_layer, self.body, x, (t1, t2, t3))
+        if fused is not None:
+            x, feats = fused
+        else:
+            x = self.input_layer(x)
+            feats = {}
+            for i, unit in enumerate(self.body):
+                x = unit(x)
+                if i in (t1, t2, t3):
+                    feats[i] = x
         c1, c2, c3 = feats[t1], feats[t2], feats[t3]
         if GROUP_HEADS and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled():
             flat = self._flatten_heads()

@@ -213,6 +213,45 @@ int fmgan_face_region_backward_f32(const float *r, const float *g, const float *
 int fmgan_render_mask_f32(const float *r, float *mask, int batch, int channels, long long hw, void *stream);
 
 /*
+ * Inference glue of the pSp encoder's IR / IR-SE units (psp_encoder_model/encoders/helpers.py): what runs between the
+ * MIOpen convolutions of a unit.  All tensors f32 in NHWC storage ([batch, h, w, channels]); a BatchNorm2d in eval mode is
+ * given as its four [channels] vectors and eps and is evaluated in-kernel on every launch as
+ *   bn(v) = (v - mean[c]) * (gamma[c] * (1 / sqrt(var[c] + eps))) + beta[c]
+ *   fmgan_bn_prelu_f32 : t = prelu(bn(x), slope[c]);  y = t (y may be NULL);  y_next = bn_next(t) (NULL: not wanted, the
+ *                        next_* vectors are then ignored);  y_sub [batch, (h-1)/s+1, (w-1)/s+1, channels] = t[:, ::s, ::s]
+ *                        with s = sub_stride >= 1 (NULL: not wanted).  At least one output.
+ *   fmgan_se_pool_f32  : partial[b, k, c] = sum over the rows of chunk k, in pixel order, of r[b, :, :, c];
+ *                        partial [batch, fmgan_se_pool_chunks(batch, channels, h, w), channels]
+ *   fmgan_se_gate_f32  : pooled = bn(sum_k partial[b, k, :] / hw) (chunks in order; the mean of the affine map is the affine
+ *                        map of the mean);  gate[b, :] = sigmoid(fc2 . relu(fc1 . pooled)),  fc1 [mid, channels],
+ *                        fc2 [channels, mid];  gate [batch, channels]
+ *   fmgan_ir_tail_f32  : out = bn(r) * gate[b, c] + shortcut (gate NULL: no SE gate);  out_next = bn_next(out) (NULL: not
+ *                        wanted).  With the sc_* vectors given, shortcut [batch, h, w, channels] is the 1x1 shortcut
+ *                        convolution's output and bn_sc is applied to it (sc_h = h, sc_w = w, sc_stride = 1); with all
+ *                        four NULL it is the unit's input [batch, sc_h, sc_w, channels] read in place at (s*y, s*x),
+ *                        s = sc_stride, (sc_h-1)/s+1 = h and (sc_w-1)/s+1 = w  (MaxPool2d(1, s)).
+ * No atomics, fixed summation order: bit-reproducible.  Served: channels % 4 == 0, channels <= 1024 (se_gate: mid <= 256)
+ * and 16-byte aligned pointers; FMGAN_EUNSUPPORTED otherwise (fmgan_se_pool_chunks returns 0): the caller then runs the
+ * modules.  batch == 0 returns FMGAN_OK before anything else; FMGAN_EOVERFLOW when batch > 65535 or a row index / an
+ * offset inside a row does not fit 32 bits (tensor offsets are 64-bit).
+ */
+int fmgan_bn_prelu_f32(const float *x, const float *mean, const float *var, const float *gamma, const float *beta,
+                       float eps, const float *slope, float *y, const float *next_mean, const float *next_var,
+                       const float *next_gamma, const float *next_beta, float next_eps, float *y_next, float *y_sub,
+                       int batch, int channels, int h, int w, int sub_stride, void *stream);
+int fmgan_se_pool_chunks(int batch, int channels, int h, int w);
+int fmgan_se_pool_f32(const float *r, float *partial, int batch, int channels, int h, int w, void *stream);
+int fmgan_se_gate_f32(const float *partial, int chunks, long long hw, const float *mean, const float *var,
+                      const float *gamma, const float *beta, float eps, const float *fc1, const float *fc2, float *gate,
+                      int batch, int channels, int mid, void *stream);
+int fmgan_ir_tail_f32(const float *r, const float *mean, const float *var, const float *gamma, const float *beta,
+                      float eps, const float *gate, const float *shortcut, int sc_h, int sc_w, int sc_stride,
+                      const float *sc_mean, const float *sc_var, const float *sc_gamma, const float *sc_beta, float sc_eps,
+                      float *out, const float *next_mean, const float *next_var, const float *next_gamma,
+                      const float *next_beta, float next_eps, float *out_next, int batch, int channels, int h, int w,
+                      void *stream);
+
+/*
  * LPIPS distance of one VGG tap (lpips/__init__.py, PNetLin.forward: unit-normalise over channels, squared difference,
  * 1x1 conv to one channel, spatial mean) and its data gradients.  f0, f1 [batch, hw, channels] f32 (NHWC storage of
  * [batch, channels, H, W] features, hw = H*W), w [channels] the 1x1 weight:
