@@ -416,6 +416,30 @@ def test_upfirdn2d_selects_return_the_launch_status():
     assert L.fmgan_blur_noise_bias_act_select(None, None, None, 0, 4, 129, 129, 129 * 129, 129, 4, 4, 1, 1, 1, 1) == EINVAL
 
 
+def test_upfirdn2d_kernel_case_tables_reach_their_kernels():
+    """tests/ufd_cases.py, every row: fmgan_upfirdn2d_select names the kernel the row was written for (1 where the row says
+    5: the ring is chosen by address, which this select does not get) and the output has the size the table states.  The
+    GPU tests assert the same before they run; here a change of the plan's rules fails without a GPU.  (Without a device
+    the plan assumes 256 CUs, the count the two scaled rows were written for.)"""
+    import ufd_cases
+    from op import _native
+    L = _lib()
+    assert len(set(ufd_cases.ALL_ROWS)) == len(ufd_cases.ALL_ROWS) == len(ufd_cases.OUT_SIZE)
+    assert ufd_cases.rowmarch_tall_major(256) == ufd_cases.ROWMARCH_TALL[1]
+    assert ufd_cases.up2_trip_major(256) == ufd_cases.UP2_TRIP[1]
+    reached = set()
+    for row in ufd_cases.ALL_ROWS:
+        kernel, major, in_h, in_w, kh, kw, up, px0, px1, py0, py1 = row
+        sel = L.fmgan_upfirdn2d_select(0, major, in_h, in_w, 1, kh, kw, up, up, 1, 1, px0, px1, py0, py1)
+        assert sel == (1 if kernel == 5 else kernel), f'{ufd_cases.row_id(row)}: select says {sel}'
+        assert _native.upfirdn2d_out_size(in_h, in_w, kh, kw, up, up, 1, 1, px0, px1, py0, py1) == ufd_cases.OUT_SIZE[row], row
+        reached.add(kernel)
+    assert reached == {0, 1, 5, 2, 3}
+    assert all(r in ufd_cases.ALL_ROWS for r in ufd_cases.FUSED)
+    # each parity instantiation of the up2 kernel has a directed row
+    assert {(r[9] & 1, r[7] & 1) for r in ufd_cases.UP2} == {(0, 1), (1, 0), (1, 1)}
+
+
 def test_bf16_launches_ask_supported():
     """fmgan_modconv2d_bf16(_x3)_supported is the one statement of which shapes the bf16 contractions serve, and the
     launch asks it: for every refused shape, and for mode 2 on the split-operand entry, `_supported` is 0 and the launch

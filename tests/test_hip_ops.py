@@ -519,7 +519,11 @@ def test_empty_batches_are_no_ops():
 
 def test_upfirdn2d_random_arguments_vs_c_oracle():
     """Seeded sweep over the whole argument space of the native entry point (asymmetric up/down/pads incl. negative
-    (cropping) pads, 1..5-tap kernels, minor > 1, f32 and f64): every dispatch path vs the C oracle."""
+    (cropping) pads, 1..5-tap kernels, minor > 1, f32 and f64) vs the C oracle.  This is a test of the GENERIC kernel: up
+    and down are drawn from 1..3 per axis, and the fast kernels need up == down == 1 or up == 2, down == 1 on both axes,
+    minor 1, f32 and at most 4 taps.  Replayed through fmgan_upfirdn2d_select, 59 of the 60 draws run the generic kernel,
+    one ((6, 9, 217), 2 x 4 taps, pads (1, 4, -2, 1)) the up=2 polyphase kernel, none the row-march or the plane-tile
+    kernel.  The fast kernels have their own sweeps and directed cases in tests/test_hip_upfirdn2d_kernels.py."""
     from op import _native
     from oracle import c_oracle
     rng = np.random.default_rng(2024)
