@@ -2,12 +2,17 @@
 
 Kept for the callers (train_3_encoder.py:460,507,574; Evaluation/visual_eval.py:116,180,296; quant_eval.py:93,162):
 Forward_Inference_3_Encoder, Build_Generator_From_Dict, Get_Network_Shape, Get_Conv_Kernel_Key.
+Re-animation (one photo, a sequence of renders: the reference's GIF driver, Evaluation/visual_eval.py:147-186, which
+re-runs all three encoders per frame): Encode_Photo once, then Forward_Inference_Reanimate / Reanimate_From_Codes per
+chunk of frames.
 Image/PIL helpers of the reference file (torchvision-based) are not on the path and not provided.
 """
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
+from op import _native
 from stylegan2 import Generator
 from Util.streams import side_streams, run_on, overlap_ok
 
@@ -124,3 +129,72 @@ def Forward_Inference_3_Encoder(p_input, r_input, E_Tsr, E_W, E_W_Plus, g_ema, t
         else:
             g_output = torch.tanh(g_output)
     return g_output
+
+
+class PhotoCode(NamedTuple):
+    """What the photo contributes to every frame: W+ [P,n_styles,512] and, for tsr_encode='Photo Image', the 4x4 input
+    tensor [P,512,4,4] (None for 'Render Image': the tensor then comes from each render)."""
+    w_plus: torch.Tensor
+    tensor: Optional[torch.Tensor]
+
+
+def Encode_Photo(p_input, E_Tsr, E_W_Plus, tsr_encode='Photo Image'):
+    """The photo side of Forward_Inference_3_Encoder, once: E_W_Plus (106 GFLOP per image) and, for 'Photo Image',
+    E_Tsr on the ResNet side stream beside it.  Inference only (no_grad)."""
+    if tsr_encode not in MODULATION_ENCODING:
+        raise ValueError(f'tsr_encode must be one of {MODULATION_ENCODING}')
+    _native.require_gpu(p_input, 'p_input')
+    with torch.no_grad():
+        if tsr_encode != 'Photo Image':
+            return PhotoCode(E_W_Plus(p_input), None)
+        if overlap_ok(p_input):
+            join, tensor = run_on(side_streams(p_input.device, RESNET_STREAMS, 'resnets')[0], E_Tsr, p_input)
+            w_plus = E_W_Plus(p_input)
+            join()
+        else:
+            tensor, w_plus = E_Tsr(p_input), E_W_Plus(p_input)
+    return PhotoCode(w_plus, tensor)
+
+
+def Reanimate_From_Codes(photo_code, encoded_W, encoded_tensor, g_ema, sliced_layer=None, use_tanh=False, noise=None,
+                         randomize_noise=True):
+    """Frames [T,3,S,S] from stored codes: W [T,512] of the renders, the photo's PhotoCode (P = 1: shared by all
+    frames, or P = T) and the input tensor [T,512,4,4] (None: the photo's, expanded over the frames).  Element for
+    element the arithmetic of Forward_Inference_3_Encoder after its encoders: latent[:, i] = W * W+[:, i] where sliced,
+    W elsewhere; image = g_ema(latent, tensor).  The generator is called bare (wrappers' `.module`), with the noise
+    arguments given here."""
+    frames = encoded_W.shape[0]
+    tensor = photo_code.tensor if encoded_tensor is None else encoded_tensor
+    if tensor is None:
+        raise ValueError('no input tensor: the photo was encoded for \'Render Image\' and no encoded_tensor was given')
+    if tensor.shape[0] != frames:
+        if tensor.shape[0] != 1:
+            raise ValueError(f'input tensor of {tensor.shape[0]} samples for {frames} frames')
+        tensor = tensor.expand(frames, -1, -1, -1)
+    with torch.no_grad():
+        g_output = _unwrapped(g_ema)(noise_z=None, use_external_input_tensor=True,
+                                     external_input_tensor=tensor.contiguous(), noise=noise,
+                                     randomize_noise=randomize_noise,
+                                     comod=(encoded_W, photo_code.w_plus, sliced_layer))
+        return torch.tanh(g_output) if use_tanh else g_output
+
+
+def Forward_Inference_Reanimate(photo_code, r_input, E_Tsr, E_W, g_ema, tsr_encode='Photo Image', sliced_layer=None,
+                                use_tanh=False, noise=None, randomize_noise=True):
+    """Render frames [T,3,256,256] + the photo's code -> images [T,3,S,S]: Forward_Inference_3_Encoder with the photo
+    repeated T times, minus the photo-side encoders (40-55 % of a frame's arithmetic)."""
+    if tsr_encode not in MODULATION_ENCODING:
+        raise ValueError(f'tsr_encode must be one of {MODULATION_ENCODING}')
+    _native.require_gpu(r_input, 'r_input')
+    render_tsr = tsr_encode != 'Photo Image'
+    with torch.no_grad():
+        if overlap_ok(r_input):
+            rs = side_streams(r_input.device, RESNET_STREAMS, 'resnets')
+            join_t, encoded_tensor = run_on(rs[0], E_Tsr, r_input) if render_tsr else ((lambda: None), None)
+            join_w, encoded_W = run_on(rs[-1], E_W, r_input)
+            join_t(); join_w()
+        else:
+            encoded_tensor = E_Tsr(r_input) if render_tsr else None
+            encoded_W = E_W(r_input)
+    return Reanimate_From_Codes(photo_code, encoded_W, encoded_tensor, g_ema, sliced_layer, use_tanh, noise,
+                                randomize_noise)

@@ -8,7 +8,7 @@
 //
 // One wave per (output feature n, sample b): lane l holds w[n, l + 64 j]; fixed summation order (lane-strided partial
 // sums, then a butterfly) — bit-reproducible, independent of the batch size.
-#include "common.h"
+#include "modulation_waves.h"
 
 namespace {
 
@@ -21,10 +21,7 @@ __global__ __launch_bounds__(256) void equal_linear_f32(const float* __restrict_
   const float* wn = w + (long long)n * k_in;
   for (int b = blockIdx.y; b < batch; b += gridDim.y) {
     const float* xb = x + (long long)b * k_in;
-    float acc = 0.f;
-    for (int k = lane; k < k_in; k += 64) acc = fmaf(wn[k], xb[k], acc);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    const float acc = equal_linear_wave<false>(wn, xb, nullptr, k_in, lane);
     if (lane == 0) out[(long long)b * n_out + n] = bias ? acc + bias[n] : acc;
   }
 }

@@ -1,7 +1,7 @@
 // ModulatedConv2d helpers for gfx950 (MI355X): demodulation, the cached per-(o,i) weight squares and the weight
 // layouts the MFMA kernels read (modconv_fwd.hip, modconv_wgrad.hip).
 // Demodulation: one wave per output channel, sum over Cin by wave-shuffle butterfly.
-#include "common.h"
+#include "modulation_waves.h"
 
 namespace {
 
@@ -17,47 +17,14 @@ __global__ __launch_bounds__(256) void modconv_demod_f32(const float* __restrict
   const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (o >= cout) return;  // wave-uniform
   const float* wo = W + (long long)o * cin * (PRE ? 1 : ktaps);
-  constexpr int MAXJ = 8;
-  const bool cached = cin <= 64 * MAXJ;
-  float wsq[MAXJ];
-  if (cached) {
-#pragma unroll
-    for (int j = 0; j < MAXJ; ++j) {
-      const int i = lane + 64 * j;
-      float q = 0.f;
-      if (i < cin) {
-        if constexpr (PRE) q = wo[i];
-        else
-          for (int t = 0; t < ktaps; ++t) { const float w = wo[i * ktaps + t]; q = fmaf(w, w, q); }
-      }
-      wsq[j] = q;
-    }
-  }
+  float wsq[DEMOD_MAXJ];
+  if (demod_cached(cin)) demod_load_wsq<PRE>(wo, cin, ktaps, lane, wsq);
   // PRE (inference): one wave per (output channel, sample) — the grid's y extent covers the batch, so the samples' style
   // loads are independent waves instead of `batch` dependent round trips inside one wave.  The raw-weight form keeps one
   // wave per channel (it squares nine taps per weight; repeating that per sample would cost more than it hides).
   for (int b = blockIdx.y; b < batch; b += gridDim.y) {
-    const float* sb = style + (long long)b * cin;
-    float acc = 0.f;
-    if (cached) {
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) {
-        const int i = lane + 64 * j;
-        if (i < cin) { const float m = sb[i]; acc = fmaf(wsq[j], m * m, acc); }
-      }
-    } else {
-      for (int i = lane; i < cin; i += 64) {
-        float q = 0.f;
-        if constexpr (PRE) q = wo[i];
-        else
-          for (int t = 0; t < ktaps; ++t) { const float w = wo[i * ktaps + t]; q = fmaf(w, w, q); }
-        const float m = sb[i];
-        acc = fmaf(q, m * m, acc);
-      }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) demod[(long long)b * cout + o] = 1.0f / sqrtf(scale * scale * acc + eps);
+    const float d = demod_wave<PRE>(wo, wsq, style + (long long)b * cin, cin, ktaps, scale, eps, lane);
+    if (lane == 0) demod[(long long)b * cout + o] = d;
   }
 }
 

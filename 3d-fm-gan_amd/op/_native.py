@@ -108,6 +108,9 @@ def lib():
     _sig(L.fmgan_refresh_entry_bytes, [])
     _sig(L.fmgan_weight_refresh_blocks, [i, i, i, i, ll], ll)
     _sig(L.fmgan_weight_refresh_f32, [vp, i, ll, vp])
+    _sig(L.fmgan_style_bank_entry_bytes, [])
+    _sig(L.fmgan_style_bank_f32, [vp, i, vp, vp, i, i, i, vp, vp])
+    _sig(L.fmgan_demod_bank_f32, [vp, i, vp, i, vp, vp])
     if L.fmgan_abi_version() != 1:
         raise RuntimeError('libfmgan_hip.so ABI version mismatch')
     _lib = L
@@ -645,6 +648,23 @@ def equal_linear(x, weight, bias=None):
     with on_device(x) as stream:
         check(lib().fmgan_equal_linear_f32(fp(x), fp(weight), fp(bias), fp(out), b, n, k, stream), 'equal_linear')
     return out
+
+
+def style_bank(table, n_entries, w, wplus, styles_out):
+    """Every table entry's style in one launch (op/style_bank.py builds the table): w [T,D], wplus [P,n_styles,D] with
+    P in {1, T}, styles_out flat f32 of T * sum(cin) elements."""
+    if w.dim() != 2 or wplus.dim() != 3 or wplus.shape[2] != w.shape[1] or not (w.is_contiguous() and wplus.is_contiguous()):
+        raise RuntimeError(f'style_bank: W {tuple(w.shape)} / W+ {tuple(wplus.shape)} must be contiguous [T,D] / [P,n,D]')
+    with on_device(w) as stream:
+        check(lib().fmgan_style_bank_f32(fp(table.view(torch.float32)), n_entries, fp(w), fp(wplus), wplus.shape[0],
+                                         w.shape[0], w.shape[1], fp(styles_out), stream), 'style_bank')
+
+
+def demod_bank(table, n_entries, styles, batch, demod_out):
+    """Every demodulated table entry's coefficients in one launch, from the flat styles of style_bank()."""
+    with on_device(styles) as stream:
+        check(lib().fmgan_demod_bank_f32(fp(table.view(torch.float32)), n_entries, fp(styles), batch, fp(demod_out), stream),
+              'demod_bank')
 
 
 def modconv_wsq(weight):

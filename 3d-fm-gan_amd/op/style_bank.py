@@ -1,0 +1,135 @@
+"""Styles and demodulation coefficients of a whole Generator in two launches (csrc/style_bank.hip).
+
+With co-modulation inputs that are complete before the synthesis network starts (re-animation: W+ of the photo is
+cached, W of the render frames is known) no layer's style depends on an activation, so the per-layer
+`fmgan_equal_linear_f32` / `fmgan_modconv_demod_wsq_f32` launches and the `W * W+[:, i]` multiplies leave the critical
+path: a device-side table with one entry per modulated conv (conv1, to_rgb1, every convs[i], every to_rgbs[i]) points
+at the layer's refreshed `weight*scale` / `bias*lr_mul` / `sum_tap W^2` buffers (op/live_weights.py) and at its slot
+in two flat output buffers.  The table holds raw pointers of the LiveWeights buffers, so it is rebuilt whenever
+LiveWeights rebuilds (recognised by the identity of its device table, which every rebuild replaces), a deep copy starts
+without one, and it is valid only inside the Generator's inference forward, after the weight refresh.
+"""
+import numpy as np
+import torch
+
+from . import _native
+from .live_weights import live
+
+_ENTRY = np.dtype([('ws', '<u8'), ('bs', '<u8'), ('wsq', '<u8'), ('style_off', '<i8'), ('demod_off', '<i8'),
+                   ('col', '<i4'), ('sliced', '<i4'), ('n_styles', '<i4'), ('cin', '<i4'), ('cout', '<i4'),
+                   ('demodulate', '<i4'), ('scale', '<f4'), ('eps', '<f4')])
+
+
+def _check_layout():
+    if _native.lib().fmgan_style_bank_entry_bytes() != _ENTRY.itemsize:
+        raise RuntimeError('fmgan_style_bank_entry layout mismatch between libfmgan_hip.so and op/style_bank.py')
+
+
+class Table:
+    """Device table + slot layout for a list of layers, each a dict(ws, bs, wsq, col, sliced, cout, scale, eps,
+    demodulate) of f32 GPU tensors (bs / wsq may be None) and scalars; cin is ws.shape[0]."""
+
+    def __init__(self, layers, n_styles):
+        _check_layout()
+        rows, self.style_slots, self.demod_slots = [], [], []
+        s_off = d_off = 0
+        for l in layers:
+            cin, cout = int(l['ws'].shape[0]), int(l['cout'])
+            demod = bool(l['demodulate']) and l['wsq'] is not None
+            if l['sliced'] and not 0 <= int(l['col']) < n_styles:
+                raise RuntimeError(f"style_bank: sliced column {l['col']} outside W+'s {n_styles} columns")
+            if l['ws'].dim() != 2 or l['ws'].shape[1] != layers[0]['ws'].shape[1] or not l['ws'].is_contiguous() or (l['wsq'] is not None and (
+                    tuple(l['wsq'].shape) != (cout, cin) or not l['wsq'].is_contiguous())) or (
+                    l['bs'] is not None and l['bs'].numel() != cin):
+                raise RuntimeError('style_bank: ws [cin,D], bs [cin], wsq [cout,cin], contiguous')
+            rows.append((_native.fp(l['ws']), _native.fp(l['bs']) or 0, _native.fp(l['wsq']) or 0, s_off, d_off,
+                         int(l['col']), int(bool(l['sliced'])), int(n_styles), cin, cout, int(demod), l['scale'], l['eps']))
+            self.style_slots.append((s_off, cin))
+            self.demod_slots.append((d_off, cout) if demod else None)
+            s_off += cin
+            d_off += cout if demod else 0
+        self.n, self.n_styles = len(rows), int(n_styles)
+        self.style_floats, self.demod_floats = s_off, d_off
+        self.style_dim = int(layers[0]['ws'].shape[1])
+        self.device = layers[0]['ws'].device
+        self.dev = torch.from_numpy(np.array(rows, dtype=_ENTRY).view(np.uint8).copy()).to(self.device)
+
+    def buffers(self, batch):
+        """(flat styles, flat demod) for `batch` samples (demod holds one spare float when nothing is demodulated)."""
+        return (torch.empty(batch * self.style_floats, dtype=torch.float32, device=self.device),
+                torch.empty(max(1, batch * self.demod_floats), dtype=torch.float32, device=self.device))
+
+    def run(self, w, wplus, styles, demod):
+        """The two launches on the current stream."""
+        if (wplus.dim() != 3 or wplus.shape[1] != self.n_styles or w.shape[1] != self.style_dim
+                or styles.numel() < w.shape[0] * self.style_floats or demod.numel() < w.shape[0] * self.demod_floats):
+            raise RuntimeError('style_bank: buffers, style_dim or W+ columns do not match the table')
+        _native.style_bank(self.dev, self.n, w, wplus, styles)
+        if self.demod_floats:
+            _native.demod_bank(self.dev, self.n, styles, w.shape[0], demod)
+
+    def views(self, batch, styles, demod):
+        """Per-layer ([batch,cin] style, [batch,cout] demod or None): views into the flat buffers."""
+        out = []
+        for (so, cin), ds in zip(self.style_slots, self.demod_slots):
+            s = styles[batch * so:batch * (so + cin)].view(batch, cin)
+            d = None if ds is None else demod[batch * ds[0]:batch * (ds[0] + ds[1])].view(batch, ds[1])
+            out.append((s, d))
+        return out
+
+
+class StyleBank:
+    """The bank of one Generator: tables per (sliced columns, n_styles), output buffers per batch size."""
+
+    def __init__(self, generator):
+        self.root = generator
+        self._source = None     # the LiveWeights device table our pointers were taken under (kept alive: identity is the key)
+        self._tables = {}
+        self._buffers = {}
+
+    def __deepcopy__(self, memo):
+        import copy
+        new = StyleBank.__new__(StyleBank)
+        memo[id(self)] = new
+        new.__init__(copy.deepcopy(self.root, memo))
+        return new
+
+    def layers(self):
+        """(ModulatedConv2d, latent column) of every modulated conv, in forward order."""
+        g = self.root
+        out = [(g.conv1.conv, 0), (g.to_rgb1.conv, 1)]
+        for blk, to_rgb in enumerate(g.to_rgbs):
+            i = 1 + 2 * blk
+            out += [(g.convs[2 * blk].conv, i), (g.convs[2 * blk + 1].conv, i + 1), (to_rgb.conv, i + 2)]
+        return out
+
+    def _table(self, sliced, n_styles):
+        lw = self.root._live_weights
+        if lw is None or not lw.active:
+            raise RuntimeError('StyleBank is valid only inside its Generator\'s inference forward (after the weight refresh)')
+        if lw._table is not self._source:   # LiveWeights rebuilt its buffers: every pointer of every table is stale.  Its
+            # pointer key would miss a rebuild A -> B -> A between two of our forwards; a rebuild always makes a new table.
+            self._source, self._tables, self._buffers = lw._table, {}, {}
+        tk = (sliced, n_styles)
+        if tk not in self._tables:
+            rows = []
+            for conv, col in self.layers():
+                ws, bs = live(conv.modulation)
+                lv = live(conv) if conv.kernel_size == 3 else None
+                rows.append(dict(ws=ws, bs=bs, wsq=lv[1] if lv else None, col=col, sliced=col in sliced,
+                                 cout=conv.out_channel, scale=conv.scale, eps=conv.eps, demodulate=conv.demodulate))
+                if conv.demodulate and lv is None:
+                    raise RuntimeError('style_bank: a demodulated layer without refreshed weight squares')
+            self._tables[tk] = Table(rows, n_styles)
+        return self._tables[tk]
+
+    def run(self, w, wplus, sliced):
+        """{ModulatedConv2d: (style [T,cin], demod [T,cout] or None)} for W [T,D], W+ [P,n_styles,D], P in {1,T}, and
+        the set of co-modulated columns."""
+        table = self._table(frozenset(sliced), int(wplus.shape[1]))
+        batch = int(w.shape[0])
+        if batch not in self._buffers:
+            self._buffers[batch] = table.buffers(batch)
+        styles, demod = self._buffers[batch]
+        table.run(w, wplus, styles, demod)
+        return {conv: v for (conv, _), v in zip(self.layers(), table.views(batch, styles, demod))}

@@ -9,6 +9,7 @@ tests/golden/*_manifest.json), but the hot ops are hand-written gfx950 kernels r
   ToRGB (1x1 + bias + skip add)         -> one HBM pass                         (reference: stylegan2.py:389-404)
 Host code stays PyTorch-ROCm.  There is no CPU path: CPU tensors raise RuntimeError in `op`.
 """
+import functools
 import math
 import os
 import random
@@ -21,6 +22,7 @@ from op import FusedLeakyReLU, fused_leaky_relu, upfirdn2d
 from op import _native, conv_grad, modconv, placement
 from op._native import amp_fwd as _amp_fwd, amp_bwd as _amp_bwd
 from op.live_weights import LiveWeights, live
+from op.style_bank import StyleBank
 from Util.streams import side_streams, run_on, overlap_ok
 
 _SQRT2 = math.sqrt(2.0)
@@ -308,6 +310,8 @@ def winograd_pays(batch, cin, cout, h, w):
         return False
     return cin >= 256 and cout >= 256 and 16 <= h <= 128 and 16 <= w <= 128 and batch * (h // 2) * (w // 2) >= 512
 FUSE_RGB = os.environ.get('FMGAN_NO_RGB_FUSE', '0') != '1'   # ToRGB in the preceding conv's epilogue (inference)
+# Generator(comod=...): all styles + demodulation coefficients in two launches (op/style_bank.py) instead of per layer
+STYLE_BANK = os.environ.get('FMGAN_NO_STYLE_BANK', '0') != '1'
 
 
 class StyledConv(nn.Module):
@@ -326,12 +330,21 @@ class StyledConv(nn.Module):
         self.noise = NoiseInjection()
         self.activate = FusedLeakyReLU(out_channel)
 
-    def _fused(self, input, style, noise):
-        conv, act = self.conv, self.activate
+    def _modulation(self, style, pre):
+        """(style vector, demodulation coefficients or None): `pre` if the enclosing Generator's style bank already
+        computed them for this forward, else this layer's own two launches."""
+        if pre is not None:
+            return pre
+        conv = self.conv
         s = conv.styles(style)
         lv = live(conv)     # (wt, wsq) refreshed by the enclosing network's forward, if any
         demod = (_native.modconv_demod(conv.weight, s, conv.scale, conv.eps, lv[1] if lv else None)
                  if conv.demodulate else None)
+        return s, demod
+
+    def _fused(self, input, style, noise, pre=None):
+        conv, act = self.conv, self.activate
+        s, demod = self._modulation(style, pre)
         b, _, h, w = input.shape
         oh, ow = (2 * h, 2 * w) if conv.upsample else (h, w)
         if noise is None:
@@ -399,24 +412,29 @@ class StyledConv(nn.Module):
         b, _, h, w = x_shape
         return _native.modconv2d_rgb_fusable(b, conv.in_channel, conv.out_channel, h, w)
 
-    def fused_with_rgb(self, input, style, noise, to_rgb, rgb_latent, skip_up, keep_out):
-        """StyledConv + ToRGB in one kernel (inference): returns (activation or None, rgb)."""
+    def fused_with_rgb(self, input, style, noise, to_rgb, rgb_latent, skip_up, keep_out, pre=None, rgb_pre=None):
+        """StyledConv + ToRGB in one kernel (inference): returns (activation or None, rgb).  pre / rgb_pre: this layer's
+        (style, demod) and the ToRGB's (style, None) from the style bank (then `style` / `rgb_latent` are None)."""
         if torch.is_autocast_enabled():
+            f = (lambda t: None if t is None else t.float())    # the bank's results are fp32 already; they carry no latent
             with torch.autocast('cuda', enabled=False):
-                return self.fused_with_rgb(input.float(), style.float(), None if noise is None else noise.float(), to_rgb,
-                                           rgb_latent.float(), None if skip_up is None else skip_up.float(), keep_out)
+                return self.fused_with_rgb(input.float(), f(style), f(noise), to_rgb, f(rgb_latent), f(skip_up), keep_out,
+                                           pre=pre, rgb_pre=rgb_pre)
         conv, act = self.conv, self.activate
-        s = conv.styles(style)
-        lv = live(conv)     # (wt, wsq) refreshed by the enclosing network's forward, if any
-        demod = (_native.modconv_demod(conv.weight, s, conv.scale, conv.eps, lv[1] if lv else None)
-                 if conv.demodulate else None)
+        s, demod = self._modulation(style, pre)
+        rgb_s = to_rgb.conv.styles(rgb_latent) if rgb_pre is None else rgb_pre[0]
         if noise is None:
             noise = input.new_empty(input.shape[0], 1, input.shape[2], input.shape[3]).normal_()
         return _native.modconv2d_rgb(input, conv.mfma_weight(), s, demod, noise, self.noise.weight, act.bias,
-                                     act.negative_slope, act.scale, to_rgb.conv.weight, to_rgb.conv.styles(rgb_latent),
+                                     act.negative_slope, act.scale, to_rgb.conv.weight, rgb_s,
                                      to_rgb.bias, skip_up, to_rgb.conv.scale, keep_out)
 
-    def forward(self, input, style, return_style_scalars=False, noise=None):
+    def forward(self, input, style, return_style_scalars=False, noise=None, pre=None):
+        if pre is not None:
+            # style bank (Generator(comod=...)): inference on the fused path only — there is no other consumer of `pre`
+            if torch.is_grad_enabled() or not modconv.hip_conv_ok(input, self.conv.weight) or self.conv.downsample:
+                raise RuntimeError('StyledConv: precomputed styles serve the fused inference path on float32 GPU tensors only')
+            return self._fused(input, None, noise, pre)[0]
         if (not torch.is_grad_enabled()) and modconv.hip_conv_ok(input, self.conv.weight) and not self.conv.downsample:
             if torch.is_autocast_enabled():
                 # the fused path hands raw fp32 pointers to the library: run it with autocast off on fp32 inputs (the style
@@ -446,8 +464,8 @@ class ToRGB(nn.Module):
         self.conv = ModulatedConv2d(in_channel, 3, 1, style_dim, demodulate=False)
         self.bias = nn.Parameter(torch.zeros(1, 3, 1, 1))
 
-    def forward(self, input, style, skip=None, return_style_scalars=False):
-        s = self.conv.styles(style)
+    def forward(self, input, style, skip=None, return_style_scalars=False, pre=None):
+        s = self.conv.styles(style) if pre is None else pre[0]
         if skip is not None:
             skip = self.upsample(skip)
         out = modconv.to_rgb(input, self.conv.weight, s, self.bias, skip, self.conv.scale)
@@ -468,6 +486,13 @@ class _LatentColumns:
         if not (isinstance(idx, tuple) and len(idx) == 2 and isinstance(idx[1], int) and idx[0] == slice(None)):
             raise IndexError('only latent[:, i] is served column-wise')
         return self.provider(idx[1])
+
+
+class _BankColumns:
+    """latent[:, i] when the style bank already holds every layer's style: the layers get `pre=` and no latent."""
+
+    def __getitem__(self, idx):
+        return None
 
 
 class Generator(nn.Module):
@@ -515,6 +540,7 @@ class Generator(nn.Module):
             self.convs.append(StyledConv(c_mid, c_out, 3, style_dim, blur_kernel=blur_kernel))
             self.to_rgbs.append(ToRGB(c_out, style_dim))
         self._live_weights = None
+        self._style_bank = None
 
     def make_noise(self):
         device = self.input.input.device
@@ -555,10 +581,58 @@ class Generator(nn.Module):
     def _forward(self, noise_z, return_latents=False, inject_index=None, truncation=1, truncation_latent=None,
                  latent_styles=None, input_is_latent=False, noise=None, randomize_noise=True,
                  use_external_input_tensor=False, external_input_tensor=None, PPL_regularize=False,
-                 return_rgb_list=False, return_style_scalars=False, latent_columns=None):
+                 return_rgb_list=False, return_style_scalars=False, latent_columns=None, comod=None):
         """latent_columns (not in the reference): callable i -> W+[:, i] replacing latent_styles; inference only, with
-        an external input tensor (see _LatentColumns)."""
-        if latent_columns is not None:
+        an external input tensor (see _LatentColumns).
+        comod (not in the reference): (W [T,D], W+ [P,n_styles,D] with P in {1,T}, sliced columns or None for all),
+        replacing latent_styles with latent[:, i] = W * W+[:, i] where sliced, W elsewhere — all known before the network
+        starts, so the styles and demodulation coefficients of every layer come from the style bank's two launches
+        (op/style_bank.py; STYLE_BANK = False / FMGAN_NO_STYLE_BANK=1: per layer, from the same columns).  Inference
+        only, float32 GPU tensors, with an external input tensor of T samples.  The bank reads the LiveWeights buffers, so
+        with STYLE_BANK on a Generator whose weights could not be refreshed (parameters that are not contiguous float32
+        GPU tensors) raises RuntimeError rather than changing to the per-layer form unasked; STYLE_BANK = False serves it."""
+        bank_pre = None
+        if comod is not None:
+            if (PPL_regularize or return_latents or return_style_scalars or torch.is_grad_enabled()
+                    or latent_columns is not None or not use_external_input_tensor or external_input_tensor is None):
+                raise ValueError('comod serves the plain inference forward (no_grad, external input tensor) only')
+            w_r, w_plus, sliced = comod
+            for t in (w_r, w_plus, external_input_tensor):
+                _native.require_gpu(t, 'comod input')
+            if torch.is_autocast_enabled():
+                with torch.autocast('cuda', enabled=False):
+                    f = (lambda n: None if n is None else n.float())
+                    return self._forward(noise_z, noise=None if noise is None else [f(n) for n in noise],
+                                         randomize_noise=randomize_noise, use_external_input_tensor=True,
+                                         external_input_tensor=external_input_tensor.float(),
+                                         return_rgb_list=return_rgb_list,
+                                         comod=(w_r.float(), w_plus.float(), sliced))
+            if (w_r.dim() != 2 or w_plus.dim() != 3 or w_plus.shape[0] not in (1, w_r.shape[0])
+                    or w_plus.shape[2] != w_r.shape[1] or w_plus.shape[1] < self.n_latent
+                    or external_input_tensor.shape[0] != w_r.shape[0]):
+                raise ValueError('comod: W [T,D], W+ [1 or T, n_styles >= n_latent, D] and an external tensor of T samples')
+            for t in (w_r, w_plus, external_input_tensor):
+                _native.fp(t)           # float32 GPU tensors only: the kernels take raw pointers
+            w_r, w_plus = w_r.contiguous(), w_plus.contiguous()
+            cols = range(self.n_latent) if sliced is None else sliced
+            cols = frozenset(i for i in cols if 0 <= i < w_plus.shape[1])
+            if STYLE_BANK:
+                if self._live_weights is None or not self._live_weights.active:
+                    raise RuntimeError('comod: the style bank needs the Generator\'s refreshed weights (call the module, '
+                                       'with float32 parameters on the GPU)')
+                if getattr(self, '_style_bank', None) is None:
+                    self._style_bank = StyleBank(self)
+                bank_pre = self._style_bank.run(w_r, w_plus, cols)
+            else:
+                cache = {}
+
+                def latent_columns(i):
+                    if i not in cache:
+                        cache[i] = w_r * w_plus[:, i] if i in cols else w_r
+                    return cache[i]
+        if bank_pre is not None:
+            styles = None
+        elif latent_columns is not None:
             if PPL_regularize or return_latents or return_style_scalars or not use_external_input_tensor:
                 raise ValueError('latent_columns serves the plain inference forward only')
             styles = None
@@ -569,7 +643,9 @@ class Generator(nn.Module):
                 noise = [None] * self.num_layers
             else:
                 noise = [getattr(self.noises, f'noise_{i}') for i in range(self.num_layers)]
-        if latent_columns is not None:
+        if bank_pre is not None:
+            latent = _BankColumns()
+        elif latent_columns is not None:
             latent = _LatentColumns(latent_columns, self.n_latent)
         else:
             if truncation < 1:
@@ -584,7 +660,11 @@ class Generator(nn.Module):
 
         scalars = []
 
+        def pre(layer):
+            return {} if bank_pre is None else {'pre': bank_pre[layer.conv]}
+
         def run(layer, x, w, **kw):
+            kw.update(pre(layer))
             if return_style_scalars:
                 y, s = layer(x, w, return_style_scalars=True, **kw)
                 scalars.append(s)
@@ -598,8 +678,8 @@ class Generator(nn.Module):
 
         def rgb(layer, x, w, skip):
             if not overlap:
-                return layer(x, w, skip)
-            join, y = run_on(side, layer, x, w, skip)
+                return layer(x, w, skip, **pre(layer))
+            join, y = run_on(side, functools.partial(layer, **pre(layer)), x, w, skip)
             joins.append(join)
             return y
 
@@ -625,11 +705,11 @@ class Generator(nn.Module):
                     joins.append(join_up)
                 else:
                     skip_up = to_rgb.upsample(skip)
-                out = self.convs[2 * blk](out, latent[:, i], noise=noise[i])
+                out = self.convs[2 * blk](out, latent[:, i], noise=noise[i], **pre(self.convs[2 * blk]))
                 if overlap:
                     join_up()
                 out, skip = conv_b.fused_with_rgb(out, latent[:, i + 1], noise[i + 1], to_rgb, latent[:, i + 2], skip_up,
-                                                  keep_out=False)
+                                                  keep_out=False, pre=pre(conv_b).get('pre'), rgb_pre=pre(to_rgb).get('pre'))
                 rgbs.append(skip)
                 continue
             out = run(self.convs[2 * blk], out, latent[:, i], noise=noise[i])

@@ -362,6 +362,38 @@ int fmgan_weight_refresh_f32(const fmgan_refresh_entry *table_dev, int n_entries
                              void *stream);
 
 /*
+ * Style bank: the style vector of EVERY modulated layer of a synthesis network in one launch, and the demodulation
+ * coefficients of every demodulated 3x3 layer in a second one (replaces, when all latent columns are known before the
+ * network starts, one fmgan_equal_linear_f32 + one fmgan_modconv_demod_wsq_f32 + one elementwise W * W+[:, col] per
+ * layer).  table_dev: DEVICE array of n_entries (<= 65535) entries, one per layer:
+ *   ws [cin, style_dim] = modulation weight * scale, bs [cin] = bias * lr_mul (or NULL), wsq [cout, cin] = sum_tap W^2
+ *   (or NULL: no demodulation) — the fmgan_weight_refresh_f32 buffers of the layer;
+ *   col: latent column; sliced != 0: the column is co-modulated; n_styles: columns per sample of `wplus`;
+ *   style_off / demod_off: PER-SAMPLE float offsets of the layer's block in the flat outputs (prefix sums of cin / cout).
+ * fmgan_style_bank_f32:  styles_out[batch*style_off + t*cin + n] = sum_k ws[n,k] * x[t,k] + bs[n],
+ *   x[t,k] = w[t,k], or fl(w[t,k] * wplus[p,col,k]) where sliced; w [batch, style_dim], wplus [wplus_batch, n_styles,
+ *   style_dim], wplus_batch = 1 (one photo shared by the batch: p = 0) or batch (p = t).
+ * fmgan_demod_bank_f32:  demod_out[batch*demod_off + t*cout + o] = 1/sqrt(scale^2 * sum_i wsq[o,i] * s[t,i]^2 + eps) for
+ *   every entry with demodulate != 0 and wsq != NULL, s = that entry's block of `styles`.
+ * Same fma chains, butterfly and rounding as the per-layer entry points (one shared definition): bit-identical.
+ * No atomics, one writer per element.  EINVAL for NULL pointers, n_entries outside [1, 65535], non-positive dims or
+ * wplus_batch not in {1, batch}; batch == 0 is a no-op (both checked before any HIP call).
+ */
+typedef struct fmgan_style_bank_entry {
+  const void *ws;
+  const void *bs;
+  const void *wsq;
+  long long style_off, demod_off;
+  int col, sliced, n_styles, cin, cout, demodulate;
+  float scale, eps;
+} fmgan_style_bank_entry;
+int fmgan_style_bank_entry_bytes(void);   /* sizeof(fmgan_style_bank_entry), for bindings that build the table by hand */
+int fmgan_style_bank_f32(const fmgan_style_bank_entry *table_dev, int n_entries, const float *w, const float *wplus,
+                         int wplus_batch, int batch, int style_dim, float *styles_out, void *stream);
+int fmgan_demod_bank_f32(const fmgan_style_bank_entry *table_dev, int n_entries, const float *styles, int batch,
+                         float *demod_out, void *stream);
+
+/*
  * Modulated 3x3 convolution, input-modulated form with batch-shared weights
  * (algebraically equal to the reference's per-sample weight-modulated grouped conv,
  * stylegan2.py:258-293):
