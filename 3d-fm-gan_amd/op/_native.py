@@ -61,6 +61,8 @@ def lib():
     _sig(L.fmgan_face_region_loss_f32, [vp] * 3 + [i, i, ll, vp])
     _sig(L.fmgan_face_region_backward_f32, [vp] * 4 + [i, i, ll, vp])
     _sig(L.fmgan_render_mask_f32, [vp] * 2 + [i, i, ll, vp])
+    _sig(L.fmgan_face_input_blocks, [i] * 4)
+    _sig(L.fmgan_face_input_f32, [vp] * 5 + [i] * 4 + [vp])
     _sig(L.fmgan_lpips_distance_blocks, [i] * 3)
     _sig(L.fmgan_lpips_distance_f32, [vp] * 4 + [i, i, i, f, vp])
     _sig(L.fmgan_lpips_distance_backward_f32, [vp] * 6 + [i, i, i, f, vp])
@@ -423,6 +425,51 @@ def render_mask(r):
         check(lib().fmgan_render_mask_f32(fp(r), fp(mask), b, c, hw, stream), 'render_mask')
         _observer.end(tok)
     return mask
+
+
+def face_input_pool(width, face_size=128):
+    """Pooling factor of Convert_Tensor_For_Face_Recognition_Loss for images `width` wide."""
+    return max(1, width // face_size)
+
+
+def face_input(a, b=None, want_gray_b=False, want_l1=False, face_size=128):
+    """Metric stage of the quantitative evaluation in one launch (csrc/eval_scores.hip): a, b [B, 3, H, W] f32 contiguous
+    -> (gray_a, gray_b or None, l1 or None): gray_x [B, 1, H/k, W/k] is Convert_Tensor_For_Face_Recognition_Loss(x) with
+    k = face_input_pool(W), l1 [B] = mean |a - b| over (C, H, W) from fixed-order partials (bit-reproducible).  None
+    (alone) when the kernel does not serve the shape (k not 1 / 2 / 4 / 8, H or W no multiple of k): the caller then
+    evaluates the composite.  Tensors of another dtype, device or layout are refused (RuntimeError), as is C != 3 or a `b`
+    of another shape (ValueError)."""
+    if a.ndim != 4 or a.shape[1] != 3 or (b is not None and tuple(b.shape) != tuple(a.shape)):
+        got = f'a {tuple(a.shape)}' + ('' if b is None else f' and b {tuple(b.shape)}')
+        raise ValueError(f'face_input: {got}: expected [N, 3, H, W] tensors of one shape')
+    if b is None and (want_gray_b or want_l1):
+        raise ValueError('face_input: gray_b / l1 asked for without a second image')
+    for t, name in ((a, 'a'), (b, 'b')):
+        if t is not None:
+            require_gpu(t, name)
+            fp(t)
+            if not t.is_contiguous():
+                raise RuntimeError(f'face_input: {name} must be contiguous, got strides {t.stride()}')
+    n, _, h, w = a.shape
+    k = face_input_pool(w, face_size)
+    if n == 0:
+        return None
+    blocks = lib().fmgan_face_input_blocks(n, h, w, k)
+    if blocks <= 0:
+        return None
+    if not (want_gray_b or want_l1):
+        b = None
+    with on_device(a) as stream:
+        gray_a = torch.empty((n, 1, h // k, w // k), dtype=torch.float32, device=a.device)
+        gray_b = torch.empty_like(gray_a) if want_gray_b else None
+        partial = torch.empty((n, blocks), dtype=torch.float32, device=a.device) if want_l1 else None
+        tok = _observer.begin('face_input', (n, h, w, k, b is not None))
+        st = lib().fmgan_face_input_f32(fp(a), fp(b), fp(gray_a), fp(gray_b), fp(partial), n, h, w, k, stream)
+        _observer.end(tok)
+    if st == -2:
+        return None
+    check(st, 'face_input')
+    return gray_a, gray_b, (partial.sum(1) / (3 * h * w) if want_l1 else None)
 
 
 def nhwc_dense(t):

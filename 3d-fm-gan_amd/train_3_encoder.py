@@ -342,3 +342,40 @@ class Trainer:
                                                        extreme_ds_flag=extreme_ds_flag)
         ld = self.step(g_input, r_input, g_ref, ppl_choice, ds_flag, extreme_ds_flag)
         return ld, ds_flag, extreme_ds_flag
+
+    def evaluate(self, rec_eval_loader=None, edit_eval_loader=None, **kwargs):
+        """The quantitative half of Sample_Eval_Save_Ckpt (train_3_encoder.py:708-733): Get_Recon_Score on
+        rec_eval_loader ((photo, render) batches) and Get_Edit_Score on edit_eval_loader ([photo, render_1, ..] batches),
+        with the bare encoders, g_ema, self.face_rec_model and self.lpips_model, under no_grad.  Returns a dict with the
+        reference's log names: cos_score, lpips_score, l1_score (reconstruction), cos_score_edit, fid, hmap_score,
+        lmark_score, face_reg_score (editing); the scores of a loader that was not given, and the three this build does
+        not provide, are None.  kwargs go to Get_Edit_Score (noise, randomize_noise).  Parameters, their requires_grad
+        and the modules' training flags, the optimisers, the counters and mean_path_length are left as they are."""
+        from Evaluation.quant_eval import Get_Edit_Score, Get_Recon_Score
+        a, b = self.args, self.bare
+        device = self.device if self.device is not None else next(b['G'].parameters()).device
+        generative_model = (b['E_Tsr'], b['E_W'], b['E_W_Plus'], self.g_ema)
+        fwd = dict(tsr_encode=a.tsr_encode, sliced_layer=a.w_plus_sliced_layer, use_tanh=a.use_tanh)
+        scores = dict.fromkeys(('cos_score', 'lpips_score', 'l1_score', 'cos_score_edit', 'fid', 'hmap_score',
+                                'lmark_score', 'face_reg_score'))
+        if self.face_rec_model is None or (rec_eval_loader is not None and self.lpips_model is None):
+            raise ValueError('evaluate: the Trainer was built without face_rec_model / lpips_model (Module_Fix_Setup)')
+        # the reference puts g_ema and the three encoders in eval mode for the evaluation and leaves them there; here every
+        # module gets its own flag back
+        was_training = [[m.training for m in net.modules()] for net in generative_model]
+        try:
+            for net in generative_model:
+                net.eval()
+            with torch.no_grad():
+                if rec_eval_loader is not None:
+                    scores['cos_score'], scores['lpips_score'], scores['l1_score'] = Get_Recon_Score(
+                        rec_eval_loader, device, generative_model, (self.face_rec_model, self.lpips_model), **fwd)
+                if edit_eval_loader is not None:
+                    (scores['cos_score_edit'], scores['fid'], scores['hmap_score'], scores['lmark_score'],
+                     scores['face_reg_score']) = Get_Edit_Score(edit_eval_loader, device, generative_model,
+                                                                (self.face_rec_model, None, None), **fwd, **kwargs)
+        finally:
+            for net, flags in zip(generative_model, was_training):
+                for m, f in zip(net.modules(), flags):
+                    m.training = f
+        return scores

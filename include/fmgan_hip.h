@@ -213,6 +213,27 @@ int fmgan_face_region_backward_f32(const float *r, const float *g, const float *
 int fmgan_render_mask_f32(const float *r, float *mask, int batch, int channels, long long hw, void *stream);
 
 /*
+ * Metric stage of the quantitative evaluation (Evaluation/quant_eval.py:25-49, 100): the face-recognition network's input
+ * of one or two [batch, 3, h, w] contiguous f32 image batches and the per-sample L1 between them, every element read once.
+ *   gray_x[b,0,oy,ox] = (1/k^2) * sum over the k x k window of (c0*x0 + c1*x1) + c2*x2   ([batch, 1, h/k, w/k];
+ *                       RGB_to_GrayScale + avg_pool2d(k, k), Util/training_util.py:130-161).  The three products are
+ *                       rounded separately (coefficients float(0.2989), float(0.587), float(0.114)), no fused
+ *                       multiply-add; the window sum is serial from 0, rows top to bottom, columns left to right.
+ *   l1_partial[b, blk] = sum over block blk's share of sample b of |a - b|; [batch, fmgan_face_input_blocks(...)], fixed
+ *                       association (no atomics, longest serial chain 40 additions): the caller sums each row and
+ *                       divides by 3*h*w.
+ * NULL b, gray_a, gray_b or l1_partial: not wanted.  gray_b or l1_partial without b, or no output at all: FMGAN_EINVAL.
+ * Served: k in {1, 2, 4, 8}, h % k == 0, w % k == 0; FMGAN_EUNSUPPORTED otherwise (fmgan_face_input_blocks returns 0, as
+ * it does whenever the launch would refuse the shape): the caller then evaluates the composite.  FMGAN_EOVERFLOW when
+ * batch*3*h*w does not fit a long long, h*w does not fit 31 bits, or batch * blocks exceeds the grid's 2^31 - 1.
+ * 16-byte loads when w % 4 == 0 and a, b are 16-byte aligned, otherwise a bounded scalar form with the same arithmetic
+ * in the same order (same bits).
+ */
+int fmgan_face_input_blocks(int batch, int h, int w, int k);
+int fmgan_face_input_f32(const float *a, const float *b, float *gray_a, float *gray_b, float *l1_partial, int batch,
+                         int h, int w, int k, void *stream);
+
+/*
  * Inference glue of the pSp encoder's IR / IR-SE units (psp_encoder_model/encoders/helpers.py): what runs between the
  * MIOpen convolutions of a unit.  All tensors f32 in NHWC storage ([batch, h, w, channels]); a BatchNorm2d in eval mode is
  * given as its four [channels] vectors and eps and is evaluated in-kernel on every launch as
