@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('FMGAN_LIB') or os.path.join(os.path.dirname(_HERE), 'csrc', 'libfmgan_hip.so')
 
 F32, F64, F16 = 0, 1, 2
+FMGAN_OK, FMGAN_EUNSUPPORTED = 0, -2      # include/fmgan_hip.h, status codes
 _DTYPES = {torch.float32: F32, torch.float64: F64, torch.float16: F16}
 
 _lib = None
@@ -120,8 +121,17 @@ def lib():
 
 
 def check(status, what):
-    if status != 0:
+    if status != FMGAN_OK:
         raise RuntimeError(f'{what}: {lib().fmgan_status_string(status).decode()} (status {status})')
+
+
+def served(status, what):
+    """Did the library serve the launch?  False when it declined the shape (FMGAN_EUNSUPPORTED: the wrapper returns None
+    and its caller takes the composite form); any other failure raises as check() does."""
+    if status == FMGAN_EUNSUPPORTED:
+        return False
+    check(status, what)
+    return True
 
 
 def require_gpu(t, name):
@@ -195,6 +205,35 @@ def set_observer(obs=None):
     _observer = obs if obs is not None else _NullObserver()
 
 
+class launching(on_device):
+    """on_device with the observer's bracket inside it: `with launching(t, name, info) as stream:` makes t's device
+    current, then observer.begin(name, info); the block launches on `stream` and keeps each status; on leaving,
+    observer.end, then the device guard is released — and only then the wrapper interprets the status (check / served).
+    A block that raises releases the guard and leaves the bracket open."""
+
+    def __init__(self, t, name, info):
+        on_device.__init__(self, t)
+        self.name, self.info = name, info
+
+    def __enter__(self):
+        stream = on_device.__enter__(self)
+        self.tok = _observer.begin(self.name, self.info)
+        return stream
+
+    def __exit__(self, *exc):
+        if exc[0] is None:
+            _observer.end(self.tok)
+        return on_device.__exit__(self, *exc)
+
+
+def _noise_args(noise):
+    """The noise argument pair of the entry points: (contiguous noise or None, its batch — 1 when there is none)."""
+    if noise is None:
+        return None, 1
+    nz = noise.contiguous()
+    return nz, nz.shape[0]
+
+
 # ----------------------------------------------------------------------------- raw ops (no autograd)
 def upfirdn2d_out_size(in_h, in_w, kh, kw, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
     oh, ow = ctypes.c_int(), ctypes.c_int()
@@ -216,12 +255,10 @@ def upfirdn2d(input, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0,
     if out_h <= 0 or out_w <= 0:
         raise RuntimeError(f'upfirdn2d: empty output {out_h}x{out_w}')
     out = torch.empty((major, out_h, out_w, minor), dtype=x.dtype, device=x.device)
-    with on_device(x) as stream:
-        tok = _observer.begin('upfirdn2d', (major, in_h, in_w, out_h, out_w, up_x, down_x, x.element_size()))
-        check(lib().fmgan_upfirdn2d(dtype_code(x), ptr(x), ptr(k), ptr(out), major, in_h, in_w, minor, kh, kw,
-                                    up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, force_path, stream),
-              'upfirdn2d')
-        _observer.end(tok)
+    with launching(x, 'upfirdn2d', (major, in_h, in_w, out_h, out_w, up_x, down_x, x.element_size())) as stream:
+        st = lib().fmgan_upfirdn2d(dtype_code(x), ptr(x), ptr(k), ptr(out), major, in_h, in_w, minor, kh, kw,
+                                   up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, force_path, stream)
+    check(st, 'upfirdn2d')
     return out
 
 
@@ -233,12 +270,10 @@ def upfirdn2d_strided(in_ptr, device, major, in_h, in_w, plane_stride, row_strid
     kh, kw = k.shape
     out_h, out_w = upfirdn2d_out_size(in_h, in_w, kh, kw, 1, 1, 1, 1, pad_x0, pad_x1, pad_y0, pad_y1)
     out = torch.empty((major, out_h, out_w), dtype=torch.float32, device=device)
-    with on_device(out) as stream:
-        tok = _observer.begin('upfirdn2d', (major, in_h, in_w, out_h, out_w, 1, 1, 4))
-        check(lib().fmgan_upfirdn2d_strided(F32, in_ptr, fp(k), fp(out), major, in_h, in_w, 1, plane_stride,
-                                            row_stride, kh, kw, 1, 1, 1, 1, pad_x0, pad_x1, pad_y0, pad_y1, force_path,
-                                            stream), 'upfirdn2d_strided')
-        _observer.end(tok)
+    with launching(out, 'upfirdn2d', (major, in_h, in_w, out_h, out_w, 1, 1, 4)) as stream:
+        st = lib().fmgan_upfirdn2d_strided(F32, in_ptr, fp(k), fp(out), major, in_h, in_w, 1, plane_stride, row_stride,
+                                           kh, kw, 1, 1, 1, 1, pad_x0, pad_x1, pad_y0, pad_y1, force_path, stream)
+    check(st, 'upfirdn2d_strided')
     return out
 
 
@@ -266,21 +301,16 @@ def blur_noise_bias_act(in_ptr, device, batch, channels, in_h, in_w, plane_strid
         out = torch.empty((batch, channels, out_h, out_w), dtype=torch.float32, device=device)
     elif tuple(out.shape) != (batch, channels, out_h, out_w) or not out.is_contiguous() or out.dtype != torch.float32:
         raise RuntimeError('blur_noise_bias_act: `out` must be a contiguous f32 [B,C,out_h,out_w] tensor')
-    nz = noise.contiguous() if noise is not None else None
+    nz, nb = _noise_args(noise)
     if getattr(_observer, 'wants_paths', False):
         BLUR_PATHS[(batch * channels, in_h, in_w)] = lib().fmgan_blur_noise_bias_act_select(
             in_ptr, fp(out), fp(nz), batch, channels, in_h, in_w, plane_stride, row_stride, kh, kw, pad0, pad1, pad0, pad1)
-    with on_device(out) as stream:
-        tok = _observer.begin('upfirdn2d', (batch * channels, in_h, in_w, out_h, out_w, 1, 1, 4))
+    with launching(out, 'upfirdn2d', (batch * channels, in_h, in_w, out_h, out_w, 1, 1, 4)) as stream:
         st = lib().fmgan_blur_noise_bias_act_path_f32(in_ptr, fp(k), fp(out), batch, channels, in_h, in_w,
                                                       plane_stride, row_stride, kh, kw, pad0, pad1, pad0, pad1, fp(nz),
-                                                      fp(noise_weight), fp(bias), 1 if nz is None else nz.shape[0],
-                                                      float(alpha), float(scale), force_path, stream)
-        _observer.end(tok)
-    if st == -2:
-        return None
-    check(st, 'blur_noise_bias_act')
-    return out
+                                                      fp(noise_weight), fp(bias), nb, float(alpha), float(scale),
+                                                      force_path, stream)
+    return out if served(st, 'blur_noise_bias_act') else None
 
 
 def fused_bias_act(input, bias, refer, act, grad, alpha, scale):
@@ -298,12 +328,11 @@ def fused_bias_act(input, bias, refer, act, grad, alpha, scale):
     for d in x.shape[2:]:
         step_b *= d
     out = torch.empty_like(x)
-    with on_device(x) as stream:
-        tok = _observer.begin('fused_bias_act', (x.numel(), x.element_size()))
-        check(lib().fmgan_fused_bias_act(dtype_code(x), ptr(x), ptr(b), ptr(r), ptr(out), x.numel(),
-                                         0 if b is None else b.numel(), step_b, int(act), int(grad), float(alpha),
-                                         float(scale), stream), 'fused_bias_act')
-        _observer.end(tok)
+    with launching(x, 'fused_bias_act', (x.numel(), x.element_size())) as stream:
+        st = lib().fmgan_fused_bias_act(dtype_code(x), ptr(x), ptr(b), ptr(r), ptr(out), x.numel(),
+                                        0 if b is None else b.numel(), step_b, int(act), int(grad), float(alpha),
+                                        float(scale), stream)
+    check(st, 'fused_bias_act')
     return out
 
 
@@ -323,15 +352,10 @@ def fused_bias_act_backward(grad_output, out, alpha, scale):
         return None
     gi = torch.empty_like(g)
     partial = torch.empty((b, c, gx), dtype=torch.float32, device=g.device)
-    with on_device(g) as stream:
-        tok = _observer.begin('fused_bias_act', (g.numel(), 4))
+    with launching(g, 'fused_bias_act', (g.numel(), 4)) as stream:
         st = lib().fmgan_fused_bias_act_bwd_f32(fp(g), fp(r), fp(gi), fp(partial), b * c, hw, float(alpha),
                                                 float(scale), stream)
-        _observer.end(tok)
-    if st == -2:
-        return None
-    check(st, 'fused_bias_act_backward')
-    return gi, partial.sum((0, 2))
+    return (gi, partial.sum((0, 2))) if served(st, 'fused_bias_act_backward') else None
 
 
 def noise_bias_act(x, noise, noise_weight, bias, alpha, scale):
@@ -339,14 +363,12 @@ def noise_bias_act(x, noise, noise_weight, bias, alpha, scale):
     require_gpu(x, 'input')
     x = x.contiguous()
     b, c, h, w = x.shape
-    nz = noise.contiguous() if noise is not None else None
-    nb = 1 if nz is None else nz.shape[0]
+    nz, nb = _noise_args(noise)
     out = torch.empty_like(x)
-    with on_device(x) as stream:
-        tok = _observer.begin('noise_bias_act', (x.numel(), 4))
-        check(lib().fmgan_noise_bias_act_f32(fp(x), fp(nz), fp(noise_weight), fp(bias), fp(out), b, c, h * w, nb,
-                                             float(alpha), float(scale), stream), 'noise_bias_act')
-        _observer.end(tok)
+    with launching(x, 'noise_bias_act', (x.numel(), 4)) as stream:
+        st = lib().fmgan_noise_bias_act_f32(fp(x), fp(nz), fp(noise_weight), fp(bias), fp(out), b, c, h * w, nb,
+                                            float(alpha), float(scale), stream)
+    check(st, 'noise_bias_act')
     return out
 
 
@@ -362,10 +384,7 @@ def prelu_backward(x, grad, slope):
     partial = torch.empty((blocks, c), dtype=torch.float32, device=x.device)
     with on_device(x) as stream:
         st = lib().fmgan_prelu_backward_f32(fp(x), fp(grad), fp(slope), fp(gx), fp(partial), rows, c, stream)
-    if st == -2:
-        return None
-    check(st, 'prelu_backward')
-    return gx, partial.sum(0)
+    return (gx, partial.sum(0)) if served(st, 'prelu_backward') else None
 
 
 def _face_region_shape(r, g):
@@ -390,11 +409,10 @@ def face_region_loss(r, g):
     r (render), g (generated image) [B, C, H, W] f32 of one shape -> S [B] f32.  Fixed-order per-block partials from
     the kernel, summed here: bit-reproducible.  loss = S.sum() / numel; face_diff_score = S / (C*H*W)."""
     r, g, (b, c, hw) = _face_region_shape(r, g)
-    with on_device(r) as stream:
-        partial = torch.empty((b, lib().fmgan_face_region_blocks(b, hw)), dtype=torch.float32, device=r.device)
-        tok = _observer.begin('face_region', (b, c, hw, 0))
-        check(lib().fmgan_face_region_loss_f32(fp(r), fp(g), fp(partial), b, c, hw, stream), 'face_region_loss')
-        _observer.end(tok)
+    partial = torch.empty((b, lib().fmgan_face_region_blocks(b, hw)), dtype=torch.float32, device=r.device)
+    with launching(r, 'face_region', (b, c, hw, 0)) as stream:
+        st = lib().fmgan_face_region_loss_f32(fp(r), fp(g), fp(partial), b, c, hw, stream)
+    check(st, 'face_region_loss')
     return partial.sum(1)
 
 
@@ -407,11 +425,9 @@ def face_region_loss_backward(r, g, grad_loss):
         raise ValueError(f'face_region_loss_backward: grad_loss must hold one element, got {tuple(grad_loss.shape)}')
     gl = gl.to(device=r.device, dtype=torch.float32).contiguous()
     dg = torch.empty_like(g)
-    with on_device(r) as stream:
-        tok = _observer.begin('face_region', (b, c, hw, 1))
-        check(lib().fmgan_face_region_backward_f32(fp(r), fp(g), fp(gl), fp(dg), b, c, hw, stream),
-              'face_region_loss_backward')
-        _observer.end(tok)
+    with launching(r, 'face_region', (b, c, hw, 1)) as stream:
+        st = lib().fmgan_face_region_backward_f32(fp(r), fp(g), fp(gl), fp(dg), b, c, hw, stream)
+    check(st, 'face_region_loss_backward')
     return dg
 
 
@@ -420,10 +436,9 @@ def render_mask(r):
     (mean_c(r) > -1, the same decision as torch's r.mean(1) > -1 on the same device)."""
     r, _, (b, c, hw) = _face_region_shape(r, None)
     mask = torch.empty((b, r.shape[2], r.shape[3]), dtype=torch.float32, device=r.device)
-    with on_device(r) as stream:
-        tok = _observer.begin('face_region', (b, c, hw, 2))
-        check(lib().fmgan_render_mask_f32(fp(r), fp(mask), b, c, hw, stream), 'render_mask')
-        _observer.end(tok)
+    with launching(r, 'face_region', (b, c, hw, 2)) as stream:
+        st = lib().fmgan_render_mask_f32(fp(r), fp(mask), b, c, hw, stream)
+    check(st, 'render_mask')
     return mask
 
 
@@ -459,16 +474,13 @@ def face_input(a, b=None, want_gray_b=False, want_l1=False, face_size=128):
         return None
     if not (want_gray_b or want_l1):
         b = None
-    with on_device(a) as stream:
-        gray_a = torch.empty((n, 1, h // k, w // k), dtype=torch.float32, device=a.device)
-        gray_b = torch.empty_like(gray_a) if want_gray_b else None
-        partial = torch.empty((n, blocks), dtype=torch.float32, device=a.device) if want_l1 else None
-        tok = _observer.begin('face_input', (n, h, w, k, b is not None))
+    gray_a = torch.empty((n, 1, h // k, w // k), dtype=torch.float32, device=a.device)
+    gray_b = torch.empty_like(gray_a) if want_gray_b else None
+    partial = torch.empty((n, blocks), dtype=torch.float32, device=a.device) if want_l1 else None
+    with launching(a, 'face_input', (n, h, w, k, b is not None)) as stream:
         st = lib().fmgan_face_input_f32(fp(a), fp(b), fp(gray_a), fp(gray_b), fp(partial), n, h, w, k, stream)
-        _observer.end(tok)
-    if st == -2:
+    if not served(st, 'face_input'):
         return None
-    check(st, 'face_input')
     return gray_a, gray_b, (partial.sum(1) / (3 * h * w) if want_l1 else None)
 
 
@@ -496,24 +508,17 @@ def lpips_distance(f0, f1, w, eps=1e-10):
     the kernel, summed here: bit-reproducible.  None when the kernel does not serve the shape (C not 64 / 128 / 256 /
     512, pointers not 16-byte aligned): the caller then evaluates the composite."""
     n, c, hw = _lpips_distance_shape(f0, f1, w)
+    w = w.contiguous()
     p0, p1, pw = fp(f0), fp(f1), fp(w)
     if n == 0:
         return torch.zeros((0,), dtype=torch.float32, device=f0.device)
     blocks = lib().fmgan_lpips_distance_blocks(n, c, hw)
     if blocks <= 0:
         return None
-    if not w.is_contiguous():
-        w = w.contiguous()
-        pw = fp(w)
-    with on_device(f0) as stream:
-        partial = torch.empty((n, blocks), dtype=torch.float32, device=f0.device)
-        tok = _observer.begin('lpips_distance', (n, c, hw, 0))
+    partial = torch.empty((n, blocks), dtype=torch.float32, device=f0.device)
+    with launching(f0, 'lpips_distance', (n, c, hw, 0)) as stream:
         st = lib().fmgan_lpips_distance_f32(p0, p1, pw, fp(partial), n, c, hw, float(eps), stream)
-        _observer.end(tok)
-    if st == -2:
-        return None
-    check(st, 'lpips_distance')
-    return partial.sum(1) / hw
+    return partial.sum(1) / hw if served(st, 'lpips_distance') else None
 
 
 def lpips_distance_backward(f0, f1, w, grad, need0, need1, eps=1e-10):
@@ -533,14 +538,9 @@ def lpips_distance_backward(f0, f1, w, grad, need0, need1, eps=1e-10):
     g1 = torch.empty_like(f1) if need1 else None
     if n == 0:
         return g0, g1
-    with on_device(f0) as stream:
-        tok = _observer.begin('lpips_distance', (n, c, hw, 1))
+    with launching(f0, 'lpips_distance', (n, c, hw, 1)) as stream:
         st = lib().fmgan_lpips_distance_backward_f32(p0, p1, pw, pg, fp(g0), fp(g1), n, c, hw, float(eps), stream)
-        _observer.end(tok)
-    if st == -2:
-        return None
-    check(st, 'lpips_distance_backward')
-    return g0, g1
+    return (g0, g1) if served(st, 'lpips_distance_backward') else None
 
 
 # ----------------------------------------------------------------------------- pSp encoder glue (inference)
@@ -548,7 +548,7 @@ def _nhwc(t, name):
     """(B, C, H, W) of a [B,C,H,W] f32 GPU tensor whose storage is NHWC-dense."""
     require_gpu(t, name)
     fp(t)
-    if t.dim() != 4 or not t.permute(0, 2, 3, 1).is_contiguous():
+    if not nhwc_dense(t):
         raise RuntimeError(f'{name}: expected a [B,C,H,W] tensor in channels_last storage, got {tuple(t.shape)} with '
                            f'strides {t.stride()}')
     return tuple(t.shape)
@@ -559,7 +559,7 @@ def _bn_args(bn, c):
     if bn is None:
         return None, None, None, None, 0.0
     mean, var, gamma, beta, eps = bn
-    vs = [v if v.is_contiguous() else v.contiguous() for v in (mean, var, gamma, beta)]
+    vs = [v.contiguous() for v in (mean, var, gamma, beta)]
     if any(v.numel() != c for v in vs):
         raise ValueError(f'BatchNorm vectors must hold {c} elements, got {[v.numel() for v in vs]}')
     return fp(vs[0]), fp(vs[1]), fp(vs[2]), fp(vs[3]), float(eps)
@@ -577,7 +577,7 @@ def bn_prelu(x, bn, slope, want_y=True, bn_next=None, sub_stride=0):
     b, c, h, w = _nhwc(x, 'bn_prelu input')
     if not (want_y or bn_next is not None or sub_stride >= 1):
         raise ValueError('bn_prelu: no output requested')
-    slope = slope if slope.is_contiguous() else slope.contiguous()
+    slope = slope.contiguous()
     if slope.numel() != c:
         raise ValueError(f'bn_prelu: {slope.numel()} slopes for {c} channels')
     y = torch.empty_like(x) if want_y else None
@@ -585,15 +585,10 @@ def bn_prelu(x, bn, slope, want_y=True, bn_next=None, sub_stride=0):
     y_sub = None
     if sub_stride >= 1:
         y_sub = _nhwc_empty(b, c, (h - 1) // sub_stride + 1, (w - 1) // sub_stride + 1, x.device)
-    with on_device(x) as stream:
-        tok = _observer.begin('bn_prelu', (b, c, h, w))
+    with launching(x, 'bn_prelu', (b, c, h, w)) as stream:
         st = lib().fmgan_bn_prelu_f32(fp(x), *_bn_args(bn, c), fp(slope), fp(y), *_bn_args(bn_next, c), fp(y_next),
                                       fp(y_sub), b, c, h, w, max(int(sub_stride), 0), stream)
-        _observer.end(tok)
-    if st == -2:
-        return None
-    check(st, 'bn_prelu')
-    return y, y_next, y_sub
+    return (y, y_next, y_sub) if served(st, 'bn_prelu') else None
 
 
 def se_pool(r):
@@ -604,14 +599,9 @@ def se_pool(r):
     if chunks <= 0:
         return None
     partial = torch.empty((b, chunks, c), dtype=torch.float32, device=r.device)
-    with on_device(r) as stream:
-        tok = _observer.begin('se_pool', (b, c, h, w))
+    with launching(r, 'se_pool', (b, c, h, w)) as stream:
         st = lib().fmgan_se_pool_f32(fp(r), fp(partial), b, c, h, w, stream)
-        _observer.end(tok)
-    if st == -2:
-        return None
-    check(st, 'se_pool')
-    return partial
+    return partial if served(st, 'se_pool') else None
 
 
 def se_gate(partial, hw, bn, fc1, fc2):
@@ -623,21 +613,12 @@ def se_gate(partial, hw, bn, fc1, fc2):
     if tuple(fc1.shape[:2]) != (mid, c) or tuple(fc2.shape[:2]) != (c, mid) or fc1.numel() != mid * c \
             or fc2.numel() != mid * c:
         raise ValueError(f'se_gate: fc1 {tuple(fc1.shape)} / fc2 {tuple(fc2.shape)} do not fit {c} channels')
-    fc1 = fc1.reshape(mid, c)
-    fc2 = fc2.reshape(c, mid)
-    fc1 = fc1 if fc1.is_contiguous() else fc1.contiguous()
-    fc2 = fc2 if fc2.is_contiguous() else fc2.contiguous()
-    partial = partial if partial.is_contiguous() else partial.contiguous()
+    fc1, fc2, partial = fc1.reshape(mid, c).contiguous(), fc2.reshape(c, mid).contiguous(), partial.contiguous()
     gate = torch.empty((b, c), dtype=torch.float32, device=partial.device)
-    with on_device(partial) as stream:
-        tok = _observer.begin('se_gate', (b, c, mid, chunks))
+    with launching(partial, 'se_gate', (b, c, mid, chunks)) as stream:
         st = lib().fmgan_se_gate_f32(fp(partial), chunks, int(hw), *_bn_args(bn, c), fp(fc1), fp(fc2), fp(gate), b, c,
                                      mid, stream)
-        _observer.end(tok)
-    if st == -2:
-        return None
-    check(st, 'se_gate')
-    return gate
+    return gate if served(st, 'se_gate') else None
 
 
 def ir_tail(r, bn, gate, shortcut, sc_stride=1, bn_sc=None, bn_next=None):
@@ -653,18 +634,13 @@ def ir_tail(r, bn, gate, shortcut, sc_stride=1, bn_sc=None, bn_next=None):
     if gate is not None:
         if tuple(gate.shape) != (b, c):
             raise ValueError(f'ir_tail: gate {tuple(gate.shape)} for {tuple(r.shape)}')
-        gate = gate if gate.is_contiguous() else gate.contiguous()
+        gate = gate.contiguous()
     out = torch.empty_like(r)
     out_next = torch.empty_like(r) if bn_next is not None else None
-    with on_device(r) as stream:
-        tok = _observer.begin('ir_tail', (b, c, h, w, sc_stride, bn_sc is not None))
+    with launching(r, 'ir_tail', (b, c, h, w, sc_stride, bn_sc is not None)) as stream:
         st = lib().fmgan_ir_tail_f32(fp(r), *_bn_args(bn, c), fp(gate), fp(shortcut), sh, sw, int(sc_stride),
                                      *_bn_args(bn_sc, c), fp(out), *_bn_args(bn_next, c), fp(out_next), b, c, h, w, stream)
-        _observer.end(tok)
-    if st == -2:
-        return None
-    check(st, 'ir_tail')
-    return out, out_next
+    return (out, out_next) if served(st, 'ir_tail') else None
 
 
 def modconv_demod(weight, style, scale, eps=1e-8, wsq=None):
@@ -821,11 +797,10 @@ def wino_output(m, demod, batch, h, w, noise=None, noise_weight=None, bias=None,
     if m.shape[0] != 16 or m.shape[2] != batch * (h // 2) * (w // 2):
         raise RuntimeError('wino_output: M must be [16, cout, B*(H/2)*(W/2)]')
     out = torch.empty((batch, cout, h, w), dtype=torch.float32, device=m.device)
-    nz = noise.contiguous() if noise is not None else None
+    nz, nb = _noise_args(noise)
     with on_device(m) as stream:
         check(lib().fmgan_wino_output_f32(fp(m), fp(demod), fp(nz), fp(noise_weight), fp(bias), fp(out), batch, cout, h, w,
-                                          1 if nz is None else nz.shape[0], int(bool(fuse_act)), float(alpha),
-                                          float(act_scale), stream), 'wino_output')
+                                          nb, int(bool(fuse_act)), float(alpha), float(act_scale), stream), 'wino_output')
     return out
 
 
@@ -846,15 +821,13 @@ def modconv2d_winograd(x, wt, style, demod, noise=None, noise_weight=None, bias=
     v = torch.empty((16, cin, n), dtype=torch.float32, device=x.device)
     m = torch.empty((16, cout, n), dtype=torch.float32, device=x.device)
     out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device)
-    nz = noise.contiguous() if noise is not None else None
-    with on_device(x) as stream:
-        tok = _observer.begin('modconv2d_winograd', (b, cin, cout, h, w, 0))
+    nz, nb = _noise_args(noise)
+    with launching(x, 'modconv2d_winograd', (b, cin, cout, h, w, 0)) as stream:      # one bracket round the three steps
         check(lib().fmgan_wino_input_f32(fp(x), fp(style), fp(v), b, cin, h, w, stream), 'wino_input')
         torch.bmm(u, v, out=m)
-        check(lib().fmgan_wino_output_f32(fp(m), fp(demod), fp(nz), fp(noise_weight), fp(bias), fp(out), b, cout, h, w,
-                                          1 if nz is None else nz.shape[0], int(bool(fuse_act)), float(alpha),
-                                          float(act_scale), stream), 'wino_output')
-        _observer.end(tok)
+        st = lib().fmgan_wino_output_f32(fp(m), fp(demod), fp(nz), fp(noise_weight), fp(bias), fp(out), b, cout, h, w,
+                                         nb, int(bool(fuse_act)), float(alpha), float(act_scale), stream)
+    check(st, 'wino_output')
     return out
 
 
@@ -889,7 +862,7 @@ def modconv2d(x, wt, style, demod, mode, noise=None, noise_weight=None, bias=Non
     else:
         out = None
         out_ptr, ops, ors = strided_out
-    nz = noise.contiguous() if noise is not None else None
+    nz, nb = _noise_args(noise)
     prec, L = precision or _mc_precision, lib()
     # one launch for the three contractions: the name (also the observer's), the per-call weight image, the extra arguments
     if prec == 'bf16x3' and L.fmgan_modconv2d_bf16x3_supported(b, cin, cout, h, w, mode):
@@ -901,12 +874,11 @@ def modconv2d(x, wt, style, demod, mode, noise=None, noise_weight=None, bias=Non
         ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
         name, wtb, extra = 'modconv2d', None, (fp(ws), ws_bytes)
     launch = getattr(L, 'fmgan_' + name + ('_f32' if wtb is None else ''))
-    with on_device(x) as stream:
-        tok = _observer.begin(name, (b, cin, cout, h, w, mode))
-        check(launch(fp(x), fp(wt) if wtb is None else ptr(wtb), fp(style), fp(demod), out_ptr, b, cin, cout, h, w, mode,
-                     fp(nz), fp(noise_weight), fp(bias), 1 if nz is None else nz.shape[0], int(bool(fuse_act)),
-                     float(alpha), float(act_scale), ops, ors, *extra, stream), name)
-        _observer.end(tok)
+    with launching(x, name, (b, cin, cout, h, w, mode)) as stream:
+        st = launch(fp(x), fp(wt) if wtb is None else ptr(wtb), fp(style), fp(demod), out_ptr, b, cin, cout, h, w, mode,
+                    fp(nz), fp(noise_weight), fp(bias), nb, int(bool(fuse_act)), float(alpha), float(act_scale), ops, ors,
+                    *extra, stream)
+    check(st, name)
     return out
 
 
@@ -945,18 +917,17 @@ def modconv2d_rgb(x, wt, style, demod, noise, noise_weight, bias, alpha, act_sca
     rgb_c = rgb_weight.numel() // cout
     out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device) if keep_out else None
     rgb = torch.empty((b, rgb_c, h, w), dtype=torch.float32, device=x.device)
-    nz = noise.contiguous() if noise is not None else None
+    nz, nb = _noise_args(noise)
     sk = rgb_skip.contiguous() if rgb_skip is not None else None
     wmod = torch.empty((b, 3, cout), dtype=torch.float32, device=x.device)
-    with on_device(x) as stream:
+    with on_device(x) as stream:                                  # the per-forward ToRGB weight: outside the bracket
         check(lib().fmgan_torgb_weight_mod_f32(fp(rgb_weight), fp(rgb_style), fp(wmod), b, cout, rgb_c,
                                                float(rgb_scale), stream), 'torgb_weight_mod')
-        tok = _observer.begin('modconv2d', (b, cin, cout, h, w, 0))
-        check(lib().fmgan_modconv2d_rgb_f32(fp(x), fp(wt), fp(style), fp(demod), fp(out), b, cin, cout, h, w,
-                                            fp(nz), fp(noise_weight), fp(bias), 1 if nz is None else nz.shape[0],
-                                            1, float(alpha), float(act_scale), fp(wmod), fp(rgb_bias), fp(sk),
-                                            fp(rgb), rgb_c, stream), 'modconv2d_rgb')
-        _observer.end(tok)
+    with launching(x, 'modconv2d', (b, cin, cout, h, w, 0)) as stream:
+        st = lib().fmgan_modconv2d_rgb_f32(fp(x), fp(wt), fp(style), fp(demod), fp(out), b, cin, cout, h, w,
+                                           fp(nz), fp(noise_weight), fp(bias), nb, 1, float(alpha), float(act_scale),
+                                           fp(wmod), fp(rgb_bias), fp(sk), fp(rgb), rgb_c, stream)
+    check(st, 'modconv2d_rgb')
     return out, rgb
 
 
@@ -974,11 +945,10 @@ def modconv_wgrad(go, demod, x, style, scale, fast_only=False, mode=0):
         return None
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
     gw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
-    with on_device(x) as stream:
-        tok = _observer.begin('modconv_wgrad', (b, cin, cout, h, w, int(mode)))
-        check(lib().fmgan_modconv_wgrad_mode_f32(fp(go), fp(demod), fp(x), fp(style), fp(gw), b, cin, cout, h, w,
-                                                 int(mode), float(scale), fp(ws), ws_bytes, stream), 'modconv_wgrad')
-        _observer.end(tok)
+    with launching(x, 'modconv_wgrad', (b, cin, cout, h, w, int(mode))) as stream:
+        st = lib().fmgan_modconv_wgrad_mode_f32(fp(go), fp(demod), fp(x), fp(style), fp(gw), b, cin, cout, h, w,
+                                                int(mode), float(scale), fp(ws), ws_bytes, stream)
+    check(st, 'modconv_wgrad')
     return gw
 
 
@@ -991,11 +961,10 @@ def torgb(x, weight, style, bias, skip, scale):
     cout = weight.numel() // cin
     sk = skip.contiguous() if skip is not None else None
     out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device)
-    with on_device(x) as stream:
-        tok = _observer.begin('torgb', (b, cin, cout, h * w))
-        check(lib().fmgan_torgb_f32(fp(x), fp(weight), fp(style), fp(bias), fp(sk), fp(out), b, cin, cout, h * w,
-                                    float(scale), stream), 'torgb')
-        _observer.end(tok)
+    with launching(x, 'torgb', (b, cin, cout, h * w)) as stream:
+        st = lib().fmgan_torgb_f32(fp(x), fp(weight), fp(style), fp(bias), fp(sk), fp(out), b, cin, cout, h * w,
+                                   float(scale), stream)
+    check(st, 'torgb')
     return out
 
 
@@ -1015,14 +984,11 @@ def torgb_backward(x, grad_out, weight, style, scale):
     gx = torch.empty_like(x)
     mpart = torch.empty((splits, b, cout, cin), dtype=torch.float32, device=x.device)
     wgt = weight.contiguous()
-    with on_device(x) as stream:
-        tok = _observer.begin('torgb_backward', (b, cin, cout, h * w))
+    with launching(x, 'torgb_backward', (b, cin, cout, h * w)) as stream:
         st = lib().fmgan_torgb_backward_f32(fp(x), fp(go), fp(wgt), fp(style), fp(gx), fp(mpart), b, cin, cout, h * w,
                                             float(scale), stream)
-        _observer.end(tok)
-    if st == -2:
+    if not served(st, 'torgb_backward'):
         return None
-    check(st, 'torgb_backward')
     return gx, (mpart.sum(0) if splits > 1 else mpart[0])
 
 
@@ -1077,11 +1043,10 @@ def resize_images(images, out_h, out_w, to_tensor=False, mean=0.5, std=0.5):
     else:
         out = torch.empty((b, out_h, out_w, 3), dtype=torch.uint8, device=x.device)
         o8, o32 = out, None
-    with on_device(x) as stream:
-        tok = _observer.begin('resize', (b, h, w, out_h, out_w))
-        check(lib().fmgan_resize_bilinear_u8(ptr(x), ptr(plan), ptr(o8), ptr(o32), b, h, w, out_h, out_w, float(mean),
-                                             float(std), stream), 'resize_bilinear_u8')
-        _observer.end(tok)
+    with launching(x, 'resize', (b, h, w, out_h, out_w)) as stream:
+        st = lib().fmgan_resize_bilinear_u8(ptr(x), ptr(plan), ptr(o8), ptr(o32), b, h, w, out_h, out_w, float(mean),
+                                            float(std), stream)
+    check(st, 'resize_bilinear_u8')
     return out
 
 

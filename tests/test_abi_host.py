@@ -33,6 +33,47 @@ def test_library_exports_header_symbols():
     assert b'invalid' in L.fmgan_status_string(-1)
 
 
+def test_signature_table_matches_header():
+    """The argtypes / restype table of _native.lib() against include/fmgan_hip.h, declaration by declaration: a miscounted
+    int / long long / float in the table would hand a kernel garbage pointers.  The rule: every pointer parameter is bound
+    as c_void_p (the wrappers pass data_ptr() integers or None), except `int *`: the host-side out-parameters the wrappers
+    fill through ctypes.byref or a ctypes array (fmgan_upfirdn2d_out_size, fmgan_modconv2d_select, ...) are
+    POINTER(c_int), and only an `int *` named `plan` — the resize table, handed over as the raw address of an int32
+    tensor, host or device — is c_void_p.  `const char *` is returned as c_char_p; int, long long and float map to c_int,
+    c_longlong and c_float."""
+    hdr = open(os.path.join(ROOT, 'include', 'fmgan_hip.h')).read()
+    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    hdr = re.sub(r'^\s*#.*$', '', hdr, flags=re.M)
+    scalars = {'int': ctypes.c_int, 'long long': ctypes.c_longlong, 'float': ctypes.c_float}
+
+    def ctype_of(decl, is_return=False):
+        """ctypes forms the table may use for a C type; `decl` still carries the parameter name unless is_return."""
+        decl = ' '.join(decl.replace('*', ' * ').split())
+        if '*' in decl:
+            base = decl[:decl.index('*')].replace('const', '').strip()
+            if is_return:
+                assert base == 'char', decl
+                return (ctypes.c_char_p,)
+            by_ref = base == 'int' and not decl.endswith('* plan')
+            return (ctypes.POINTER(ctypes.c_int),) if by_ref else (ctypes.c_void_p,)
+        words = decl.split() if is_return else decl.split()[:-1]
+        return (scalars[' '.join(words)],)
+
+    decls = re.findall(r'([\w \t*]+?)\b(fmgan_\w+)\s*\(([^()]*)\)\s*;', hdr)
+    assert len(decls) == len(re.findall(r'\bfmgan_\w+\s*\(', hdr)) == len({name for _, name, _ in decls})
+    L = _lib()
+    for ret, name, params in decls:
+        fn = getattr(L, name)
+        assert fn.argtypes is not None, f'{name} is declared in the header but lib() gives it no signature'
+        want = [] if params.strip() == 'void' else [ctype_of(p) for p in params.split(',')]
+        assert len(fn.argtypes) == len(want), f'{name}: {len(fn.argtypes)} argtypes for {len(want)} parameters'
+        for k, (got, ok) in enumerate(zip(fn.argtypes, want)):
+            assert got in ok, f'{name} parameter {k}: bound as {got.__name__}, the header wants {[t.__name__ for t in ok]}'
+        assert fn.restype in ctype_of(ret, is_return=True), f'{name}: restype {fn.restype}'
+    bound = [n for n, fn in vars(L).items() if n.startswith('fmgan_') and fn.argtypes is not None]
+    assert len(bound) == len(decls), set(bound) ^ {name for _, name, _ in decls}
+
+
 def test_out_size_matches_reference_formula():
     from op import _native
     for c in cases.UPFIRDN2D_CASES:
@@ -93,12 +134,9 @@ def test_fused_bias_act_backward_host_logic():
     """fmgan_fused_bias_act_bwd_blocks / _f32: which planes the one-pass backward serves, partial columns per plane,
     argument checks — all before any HIP call."""
     L = _lib()
-    L.fmgan_fused_bias_act_bwd_blocks.argtypes = [ctypes.c_longlong, ctypes.c_int]
     for planes, hw, want in ((0, 64, 0), (8, 16, 0), (8, 63, 0), (8, 66, 0), (8, 64, 1), (8, 4096, 1), (8, 4100, 2),
                              (256, 1024 * 1024, 64), (1 << 31, 64, 0)):
         assert L.fmgan_fused_bias_act_bwd_blocks(planes, hw) == want, (planes, hw)
-    L.fmgan_fused_bias_act_bwd_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_float,
-                                               ctypes.c_float, ctypes.c_void_p]
     assert L.fmgan_fused_bias_act_bwd_f32(None, None, None, None, 0, 64, 0.2, 1.4, None) == 0       # empty
     assert L.fmgan_fused_bias_act_bwd_f32(None, None, None, None, 4, 64, 0.2, 1.4, None) == -1      # null pointers
     assert L.fmgan_fused_bias_act_bwd_f32(None, None, None, None, -1, 64, 0.2, 1.4, None) == -1
@@ -112,7 +150,6 @@ def test_torgb_backward_host_logic():
     assert L.fmgan_torgb_backward_splits(2, 512, 16) == 1
     assert L.fmgan_torgb_backward_splits(2, 512, 18) == 0                   # H*W % 4 != 0: composite instead
     assert L.fmgan_torgb_backward_splits(0, 512, 16) == 0
-    L.fmgan_torgb_backward_f32.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_void_p]
     assert L.fmgan_torgb_backward_f32(None, None, None, None, None, None, 0, 32, 3, 64, 1.0, None) == 0
     assert L.fmgan_torgb_backward_f32(None, None, None, None, None, None, 2, 32, 3, 64, 1.0, None) == -1
     assert L.fmgan_torgb_backward_f32(16, 16, 16, 16, 16, 16, 2, 32, 5, 64, 1.0, None) == -1     # cout > 4
