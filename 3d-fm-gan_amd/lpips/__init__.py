@@ -101,11 +101,17 @@ class PNetLin(nn.Module):
             setattr(self, f'lin{i}', NetLinLayer(c, use_dropout=use_dropout))
 
     def forward(self, in0, in1):
+        s0 = self.scaling_layer(in0)
+        return self.forward_scaled(s0, s0 if in1 is in0 else self.scaling_layer(in1))
+
+    def forward_scaled(self, s0, s1):
+        """The trunk and the distances on inputs that already went through the ScalingLayer (op/ppl_input.py produces
+        them in one launch)."""
         # MIOpen's convolutions are not bit-reproducible from call to call (two trunk passes over the same values differ
         # in the last bit at every tap), so the distance of an image to itself is exactly 0 only if its features are
         # computed once.
-        f0 = self.net(self.scaling_layer(in0))
-        f1 = f0 if in1 is in0 else self.net(self.scaling_layer(in1))
+        f0 = self.net(s0)
+        f1 = f0 if s1 is s0 else self.net(s1)
         val = None
         for i in range(len(self.chns)):
             lin = getattr(self, f'lin{i}').model
@@ -132,3 +138,7 @@ class PerceptualLoss(nn.Module):
         if normalize:
             target, pred = 2 * target - 1, 2 * pred - 1
         return self.net(target, pred)
+
+    def forward_scaled(self, pred_s, target_s):
+        """forward on inputs that are already scaled (ScalingLayer applied): the same argument order."""
+        return self.net.forward_scaled(target_s, pred_s)

@@ -64,6 +64,8 @@ def lib():
     _sig(L.fmgan_render_mask_f32, [vp] * 2 + [i, i, ll, vp])
     _sig(L.fmgan_face_input_blocks, [i] * 4)
     _sig(L.fmgan_face_input_f32, [vp] * 5 + [i] * 4 + [vp])
+    _sig(L.fmgan_lpips_pair_input_select, [i] * 8)
+    _sig(L.fmgan_lpips_pair_input_f32, [vp] * 5 + [i] * 8 + [vp])
     _sig(L.fmgan_lpips_distance_blocks, [i] * 3)
     _sig(L.fmgan_lpips_distance_f32, [vp] * 4 + [i, i, i, f, vp])
     _sig(L.fmgan_lpips_distance_backward_f32, [vp] * 6 + [i, i, i, f, vp])
@@ -482,6 +484,35 @@ def face_input(a, b=None, want_gray_b=False, want_l1=False, face_size=128):
     if not served(st, 'face_input'):
         return None
     return gray_a, gray_b, (partial.sum(1) / (3 * h * w) if want_l1 else None)
+
+
+def lpips_pair_input(image, shift, scale, window, f):
+    """Input stage of the perceptual path length in one launch (csrc/ppl_input.hip): image [2P, 3, H, W] f32 contiguous
+    (sample 2p / 2p+1: the two images of pair p), shift / scale the three floats of lpips.ScalingLayer's buffers on the
+    image's device (read by the kernel), window = (y0, x0, hc, wc), f in {1, 2, 4} the bilinear reduction ->
+    (in0, in1), each [P, 3, hc/f, wc/f] in channels_last storage: ((window of image[::2] / image[1::2], reduced) - shift)
+    / scale.  None when the library declines (another f, a window f does not divide): the caller then evaluates the
+    composite.  Tensors of another dtype, device or layout are refused (RuntimeError), as is another shape (ValueError)."""
+    if image.ndim != 4 or image.shape[1] != 3 or image.shape[0] % 2 != 0 or shift.numel() != 3 or scale.numel() != 3:
+        raise ValueError(f'lpips_pair_input: image {tuple(image.shape)}, shift {tuple(shift.shape)}, scale '
+                         f'{tuple(scale.shape)}: expected [2P, 3, H, W] and three floats each')
+    require_gpu(image, 'image')
+    shift, scale = shift.contiguous(), scale.contiguous()
+    pi, ps, pc = fp(image), fp(shift), fp(scale)
+    if not image.is_contiguous():
+        raise RuntimeError(f'lpips_pair_input: image must be contiguous, got strides {image.stride()}')
+    if shift.device != image.device or scale.device != image.device:
+        raise RuntimeError('lpips_pair_input: shift and scale must be on the image\'s device')
+    n, _, h, w = image.shape
+    y0, x0, hc, wc = (int(v) for v in window)
+    f = int(f)
+    if n == 0 or lib().fmgan_lpips_pair_input_select(n // 2, h, w, y0, x0, hc, wc, f) == FMGAN_EUNSUPPORTED:
+        return None
+    with launching(image, 'lpips_pair_input', (n // 2, h, w, y0, x0, hc, wc, f)) as stream:
+        out0 = _nhwc_empty(n // 2, 3, max(hc // f, 0), max(wc // f, 0), image.device)
+        out1 = torch.empty_like(out0)
+        st = lib().fmgan_lpips_pair_input_f32(pi, ps, pc, fp(out0), fp(out1), n // 2, h, w, y0, x0, hc, wc, f, stream)
+    return (out0, out1) if served(st, 'lpips_pair_input') else None
 
 
 def nhwc_dense(t):

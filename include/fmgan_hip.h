@@ -234,6 +234,31 @@ int fmgan_face_input_f32(const float *a, const float *b, float *gray_a, float *g
                          int h, int w, int k, void *stream);
 
 /*
+ * Input stage of the perceptual path length (Evaluation/ppl.py; lpips ScalingLayer): from the Generator's interleaved
+ * image batch to the two inputs of the channels_last VGG trunk, every needed source pixel read once.
+ *   img [2*pairs, 3, h, w] contiguous f32 NCHW; sample 2p is the first image of pair p, sample 2p+1 the second.
+ *   Window: rows y0 .. y0+hc, columns x0 .. x0+wc (the whole image: 0, 0, h, w);  oh = hc/f, ow = wc/f.
+ *   v = img[n, c, y0+y, x0+x] at f = 1; at f = 2 or 4, with o = f/2 - 1, a, b the pixels at row y0+f*y+o, columns
+ *       x0+f*x+o and +1, and c, d the same columns one row below:  v = 0.5*(0.5*a + 0.5*b) + 0.5*(0.5*c + 0.5*d), in
+ *       exactly this association (columns inside a row first), no fused multiply-add.  This is bilinear interpolation
+ *       with align_corners = false at the integer ratios 2 and 4 (source index f*d + f/2 - 0.5: both weights 1/2).
+ *   out0[p, y, x, c] (n = 2p) / out1[p, y, x, c] (n = 2p+1) = (v - shift[c]) / scale[c], IEEE subtraction and correctly
+ *       rounded division; [pairs, oh, ow, 3] dense: the NHWC storage of a [pairs, 3, oh, ow] channels_last tensor.
+ *   shift, scale: DEVICE pointers to three floats each, read by the kernel (no host copy, no synchronisation).
+ * No allocation, no synchronisation, no global state; the kernel runs on `stream`.  Dword-aligned pointers suffice.
+ * fmgan_lpips_pair_input_select is the launch's plan with the launch left out: a positive kernel id exactly when the
+ * launch with these arguments runs that kernel (f: the vector form, ow % 4 == 0, a lane writes four pixels as three
+ * 16-byte stores; 8 + f: the bounded form for any other width, same arithmetic, same bits), otherwise the status the
+ * launch returns: FMGAN_EINVAL for pairs <= 0, non-positive sizes or a window outside the image (the launch also for a
+ * NULL pointer), FMGAN_EUNSUPPORTED for f outside {1, 2, 4} or hc % f != 0 or wc % f != 0 (the caller then evaluates the
+ * composite), FMGAN_EOVERFLOW when h*w does not fit 31 bits, 2*pairs*3*h*w does not fit a long long, or samples * blocks
+ * exceeds the grid's 2^31 - 1.
+ */
+int fmgan_lpips_pair_input_select(int pairs, int h, int w, int y0, int x0, int hc, int wc, int f);
+int fmgan_lpips_pair_input_f32(const float *img, const float *shift, const float *scale, float *out0, float *out1,
+                               int pairs, int h, int w, int y0, int x0, int hc, int wc, int f, void *stream);
+
+/*
  * Inference glue of the pSp encoder's IR / IR-SE units (psp_encoder_model/encoders/helpers.py): what runs between the
  * MIOpen convolutions of a unit.  All tensors f32 in NHWC storage ([batch, h, w, channels]); a BatchNorm2d in eval mode is
  * given as its four [channels] vectors and eps and is evaluated in-kernel on every launch as
