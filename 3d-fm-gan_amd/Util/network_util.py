@@ -13,6 +13,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from op import _native
+from op.style_bank import comod_column, sliced_columns
 from stylegan2 import Generator
 from Util.streams import side_streams, run_on, overlap_ok
 
@@ -62,18 +63,14 @@ def _pipelined(p_input, r_input, tsr_input, E_Tsr, E_W, e_wp, g_ema, sliced_laye
     join2, encoded_W = run_on(s2, E_W, r_input)
     heads = e_wp.forward_deferred(p_input)
     join1(); join2()
-    n_styles = len(heads)
-    g = _unwrapped(g_ema)
-    if sliced_layer is None:
-        sliced_layer = range(g.n_latent)
-    sliced = {i for i in sliced_layer if 0 <= i < n_styles}
+    sliced = sliced_columns(sliced_layer, _unwrapped(g_ema).n_latent, len(heads))
     cache = {}
 
     def column(i):
         if i not in cache:
             wait, wp = heads[i]
             wait()
-            cache[i] = encoded_W * wp if i in sliced else encoded_W
+            cache[i] = comod_column(encoded_W, wp, i, sliced)
         return cache[i]
 
     g_output = g_ema(noise_z=None, use_external_input_tensor=True, external_input_tensor=encoded_tensor,
@@ -109,16 +106,13 @@ def Forward_Inference_3_Encoder(p_input, r_input, E_Tsr, E_W, E_W_Plus, g_ema, t
         encoded_W_plus = E_W_Plus(p_input)
 
     n_styles = encoded_W_plus.shape[1]
-    if sliced_layer is None:
-        sliced_layer = range(_unwrapped(g_ema).n_latent)
-    sliced = {i for i in sliced_layer if 0 <= i < n_styles}
+    sliced = sliced_columns(sliced_layer, _unwrapped(g_ema).n_latent, n_styles)
     # W (.) W+ where sliced, W elsewhere.  Built from device tensors only (no host-side mask upload), so the whole
     # forward stays capturable in a HIP graph.
     if len(sliced) == n_styles:
         encoded_latent = encoded_W.unsqueeze(1) * encoded_W_plus
     else:
-        encoded_latent = torch.stack([encoded_W * encoded_W_plus[:, i] if i in sliced else encoded_W
-                                      for i in range(n_styles)], 1)
+        encoded_latent = torch.stack([comod_column(encoded_W, encoded_W_plus[:, i], i, sliced) for i in range(n_styles)], 1)
 
     g_output = g_ema(noise_z=None, latent_styles=[encoded_latent], input_is_latent=True,
                      use_external_input_tensor=True, external_input_tensor=encoded_tensor,

@@ -9,11 +9,30 @@ in two flat output buffers.  The table holds raw pointers of the LiveWeights buf
 LiveWeights rebuilds (recognised by the identity of its device table, which every rebuild replaces), a deep copy starts
 without one, and it is valid only inside the Generator's inference forward, after the weight refresh.
 """
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 
 from . import _native
 from .live_weights import live
+
+
+class Modulation(NamedTuple):
+    """A layer's modulation, already computed: what a StyledConv / ToRGB accepts as `style` in place of a latent column."""
+    style: torch.Tensor             # [B, cin]
+    demod: Optional[torch.Tensor]   # [B, cout]; None where the layer does not demodulate
+
+
+def sliced_columns(sliced_layer, n_latent, n_styles):
+    """The co-modulated columns of a W+ with n_styles columns: `sliced_layer`, or every column of the Generator for None,
+    minus what W+ does not have."""
+    return frozenset(i for i in (range(n_latent) if sliced_layer is None else sliced_layer) if 0 <= i < n_styles)
+
+
+def comod_column(w, wplus_i, i, sliced):
+    """Latent column i of the multiplicative co-modulation: W * W+[:, i] where sliced, W elsewhere."""
+    return w * wplus_i if i in sliced else w
 
 _ENTRY = np.dtype([('ws', '<u8'), ('bs', '<u8'), ('wsq', '<u8'), ('style_off', '<i8'), ('demod_off', '<i8'),
                    ('col', '<i4'), ('sliced', '<i4'), ('n_styles', '<i4'), ('cin', '<i4'), ('cout', '<i4'),
@@ -69,12 +88,12 @@ class Table:
             _native.demod_bank(self.dev, self.n, styles, w.shape[0], demod)
 
     def views(self, batch, styles, demod):
-        """Per-layer ([batch,cin] style, [batch,cout] demod or None): views into the flat buffers."""
+        """Per-layer Modulation([batch,cin] style, [batch,cout] demod or None): views into the flat buffers."""
         out = []
         for (so, cin), ds in zip(self.style_slots, self.demod_slots):
             s = styles[batch * so:batch * (so + cin)].view(batch, cin)
             d = None if ds is None else demod[batch * ds[0]:batch * (ds[0] + ds[1])].view(batch, ds[1])
-            out.append((s, d))
+            out.append(Modulation(s, d))
         return out
 
 
@@ -124,7 +143,7 @@ class StyleBank:
         return self._tables[tk]
 
     def run(self, w, wplus, sliced):
-        """{ModulatedConv2d: (style [T,cin], demod [T,cout] or None)} for W [T,D], W+ [P,n_styles,D], P in {1,T}, and
+        """{ModulatedConv2d: Modulation(style [T,cin], demod [T,cout] or None)} for W [T,D], W+ [P,n_styles,D], P in {1,T}, and
         the set of co-modulated columns."""
         table = self._table(frozenset(sliced), int(wplus.shape[1]))
         batch = int(w.shape[0])

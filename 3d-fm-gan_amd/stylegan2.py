@@ -9,7 +9,6 @@ tests/golden/*_manifest.json), but the hot ops are hand-written gfx950 kernels r
   ToRGB (1x1 + bias + skip add)         -> one HBM pass                         (reference: stylegan2.py:389-404)
 Host code stays PyTorch-ROCm.  There is no CPU path: CPU tensors raise RuntimeError in `op`.
 """
-import functools
 import math
 import os
 import random
@@ -22,7 +21,7 @@ from op import FusedLeakyReLU, fused_leaky_relu, upfirdn2d
 from op import _native, conv_grad, modconv, placement
 from op._native import amp_fwd as _amp_fwd, amp_bwd as _amp_bwd
 from op.live_weights import LiveWeights, live
-from op.style_bank import StyleBank
+from op.style_bank import Modulation, StyleBank, comod_column, sliced_columns
 from Util.streams import side_streams, run_on, overlap_ok
 
 _SQRT2 = math.sqrt(2.0)
@@ -314,6 +313,33 @@ FUSE_RGB = os.environ.get('FMGAN_NO_RGB_FUSE', '0') != '1'   # ToRGB in the prec
 STYLE_BANK = os.environ.get('FMGAN_NO_STYLE_BANK', '0') != '1'
 
 
+def _fp32(fn, *args):
+    """fn(*args); under autocast, with autocast off and every tensor (also inside a list) as float32: the fused inference
+    path hands raw fp32 pointers to the library, and the style MLP would otherwise produce a bf16 vector (the training path
+    gets this from its autograd Functions).  A Modulation passes as it is: the bank's results are fp32 already."""
+    if not torch.is_autocast_enabled():
+        return fn(*args)
+
+    def f(a):
+        if isinstance(a, list):
+            return [f(x) for x in a]
+        return a.float() if torch.is_tensor(a) else a
+    with torch.autocast('cuda', enabled=False):
+        return fn(*[f(a) for a in args])
+
+
+def _modulation(conv, style):
+    """Modulation of a ModulatedConv2d: `style` itself if it is one already (the enclosing Generator's style bank computed
+    it for this forward), else from the latent column `style` by this layer's own two launches."""
+    if isinstance(style, Modulation):
+        return style
+    s = conv.styles(style)
+    if not conv.demodulate:
+        return Modulation(s, None)
+    lv = live(conv)     # (wt, wsq) refreshed by the enclosing network's forward, if any
+    return Modulation(s, _native.modconv_demod(conv.weight, s, conv.scale, conv.eps, lv[1] if lv else None))
+
+
 class StyledConv(nn.Module):
     """ModulatedConv2d -> NoiseInjection -> FusedLeakyReLU (stylegan2.py:332-376).
 
@@ -330,66 +356,57 @@ class StyledConv(nn.Module):
         self.noise = NoiseInjection()
         self.activate = FusedLeakyReLU(out_channel)
 
-    def _modulation(self, style, pre):
-        """(style vector, demodulation coefficients or None): `pre` if the enclosing Generator's style bank already
-        computed them for this forward, else this layer's own two launches."""
-        if pre is not None:
-            return pre
-        conv = self.conv
-        s = conv.styles(style)
-        lv = live(conv)     # (wt, wsq) refreshed by the enclosing network's forward, if any
-        demod = (_native.modconv_demod(conv.weight, s, conv.scale, conv.eps, lv[1] if lv else None)
-                 if conv.demodulate else None)
-        return s, demod
-
-    def _fused(self, input, style, noise, pre=None):
+    def _fused_upsample(self, input, s, demod, noise):
+        """Transposed conv into a private intermediate [B,C,2H+1,2W+1], then blur + noise + bias + act in the blur's store.
+        The intermediate is in the aligned-row layout: every dwordx4 load of the blur is 16-byte aligned (the contiguous
+        2W+1-float rows never are).  It is released when this returns."""
         conv, act = self.conv, self.activate
-        s, demod = self._modulation(style, pre)
         b, _, h, w = input.shape
-        oh, ow = (2 * h, 2 * w) if conv.upsample else (h, w)
+        c = conv.out_channel
+        pad0, pad1 = conv.blur.pad
+        shape, off, ps, rs = _native.aligned_rows_shape(b, c, 2 * h + 1, 2 * w + 1, pad0)
+        wt = conv.mfma_weight()
+
+        def produce(buf):
+            _native.modconv2d(input, wt, s, demod, 1, strided_out=(buf.data_ptr() + 4 * off, ps, rs))
+
+        def consume(buf, out):
+            # row-march / LDS-DMA ring for planes >= 64 wide, plane-tile (whole planes in LDS) for the 8^2..32^2 layers
+            return _native.blur_noise_bias_act(buf.data_ptr() + 4 * off, input.device, b, c, 2 * h + 1, 2 * w + 1, ps, rs,
+                                               conv.blur.kernel, (pad0, pad1), noise, self.noise.weight, act.bias,
+                                               act.negative_slope, act.scale, out=out)
+        nbytes = 4 * shape[0] * shape[1] * shape[2]
+        ws = None
+        if (placement.active() and nbytes >= placement.MIN_BYTES
+                and _native.blur_noise_bias_act_serves(b, c, 2 * h + 1, 2 * w + 1, ps, rs, conv.blur.kernel.shape,
+                                                       (pad0, pad1))):
+            # the largest buffers of the forward: a persistent pair whose placement was selected by measurement
+            # (op/placement.py: the same kernel runs at 4.85 or 5.17 TB/s depending on which two blocks it gets).
+            # Only where the fused blur has a kernel for the shape: otherwise consume() launches nothing, the
+            # selection would time a no-op and the persistent output would never be written.
+            ws = placement.workspace(self, (b, c, h, w), shape, (b, c, 2 * h, 2 * w), input.device, produce, consume)
+        if ws is not None:
+            produce(ws.buf)
+            if consume(ws.buf, ws.out) is None:
+                raise RuntimeError('StyledConv: the fused blur declined a shape its selection reported as served')
+            return ws.out
+        buf = torch.empty(shape, dtype=torch.float32, device=input.device)
+        produce(buf)
+        out = consume(buf, None)
+        if out is None:   # neither kernel serves it (planes > ~110^2 narrower than 64, FIRs wider than 4 taps): two passes
+            out = _native.upfirdn2d_strided(buf.data_ptr() + 4 * off, input.device, b * c, 2 * h + 1, 2 * w + 1, ps,
+                                            rs, conv.blur.kernel, pad0, pad1, pad0, pad1).view(b, c, 2 * h, 2 * w)
+            out = _native.noise_bias_act(out, noise, self.noise.weight, act.bias, act.negative_slope, act.scale)
+        return out
+
+    def _fused(self, input, style, noise):
+        conv, act = self.conv, self.activate
+        s, demod = _modulation(conv, style)
+        b, _, h, w = input.shape
         if noise is None:
-            noise = input.new_empty(b, 1, oh, ow).normal_()
+            noise = input.new_empty(b, 1, *((2 * h, 2 * w) if conv.upsample else (h, w))).normal_()
         if conv.upsample:
-            # private intermediate [B,C,2H+1,2W+1] in the aligned-row layout: every dwordx4 load of the blur is
-            # 16-byte aligned (the contiguous 2W+1-float rows never are)
-            c = conv.out_channel
-            pad0, pad1 = conv.blur.pad
-            shape, off, ps, rs = _native.aligned_rows_shape(b, c, 2 * h + 1, 2 * w + 1, pad0)
-            wt = conv.mfma_weight()
-
-            def produce(buf_):
-                _native.modconv2d(input, wt, s, demod, 1, strided_out=(buf_.data_ptr() + 4 * off, ps, rs))
-
-            def consume(buf_, out_):
-                # blur + noise + bias + act in the blur's store: row-march / LDS-DMA ring for planes >= 64 wide,
-                # plane-tile (whole planes in LDS) for the 8^2..32^2 layers
-                return _native.blur_noise_bias_act(buf_.data_ptr() + 4 * off, input.device, b, c, 2 * h + 1, 2 * w + 1, ps, rs,
-                                                   conv.blur.kernel, (pad0, pad1), noise, self.noise.weight, act.bias,
-                                                   act.negative_slope, act.scale, out=out_)
-            nbytes = 4 * shape[0] * shape[1] * shape[2]
-            ws = None
-            if (placement.active() and nbytes >= placement.MIN_BYTES
-                    and _native.blur_noise_bias_act_serves(b, c, 2 * h + 1, 2 * w + 1, ps, rs, conv.blur.kernel.shape,
-                                                           (pad0, pad1))):
-                # the largest buffers of the forward: a persistent pair whose placement was selected by measurement
-                # (op/placement.py: the same kernel runs at 4.85 or 5.17 TB/s depending on which two blocks it gets).
-                # Only where the fused blur has a kernel for the shape: otherwise consume() launches nothing, the
-                # selection would time a no-op and the persistent output would never be written.
-                ws = placement.workspace(self, (b, c, h, w), shape, (b, c, oh, ow), input.device, produce, consume)
-            if ws is not None:
-                buf, out = ws.buf, ws.out
-                produce(buf)
-                if consume(buf, out) is None:
-                    raise RuntimeError('StyledConv: the fused blur declined a shape its selection reported as served')
-            else:
-                buf = torch.empty(shape, dtype=torch.float32, device=input.device)
-                produce(buf)
-                out = consume(buf, None)
-                if out is None:   # neither kernel serves it (planes > ~110^2 narrower than 64, FIRs wider than 4 taps): two passes
-                    out = _native.upfirdn2d_strided(buf.data_ptr() + 4 * off, input.device, b * c, 2 * h + 1, 2 * w + 1, ps,
-                                                    rs, conv.blur.kernel, pad0, pad1, pad0, pad1).view(b, c, oh, ow)
-                    out = _native.noise_bias_act(out, noise, self.noise.weight, act.bias, act.negative_slope, act.scale)
-            del buf
+            out = self._fused_upsample(input, s, demod, noise)
         elif winograd_pays(b, conv.in_channel, conv.out_channel, h, w):
             # 16 products per 2x2 output tile instead of 36 (own transform kernels around 16 batched library GEMMs): the
             # direct kernel is already at 0.84-0.88 of the fp32 matrix peak on these layers
@@ -412,37 +429,27 @@ class StyledConv(nn.Module):
         b, _, h, w = x_shape
         return _native.modconv2d_rgb_fusable(b, conv.in_channel, conv.out_channel, h, w)
 
-    def fused_with_rgb(self, input, style, noise, to_rgb, rgb_latent, skip_up, keep_out, pre=None, rgb_pre=None):
-        """StyledConv + ToRGB in one kernel (inference): returns (activation or None, rgb).  pre / rgb_pre: this layer's
-        (style, demod) and the ToRGB's (style, None) from the style bank (then `style` / `rgb_latent` are None)."""
-        if torch.is_autocast_enabled():
-            f = (lambda t: None if t is None else t.float())    # the bank's results are fp32 already; they carry no latent
-            with torch.autocast('cuda', enabled=False):
-                return self.fused_with_rgb(input.float(), f(style), f(noise), to_rgb, f(rgb_latent), f(skip_up), keep_out,
-                                           pre=pre, rgb_pre=rgb_pre)
+    def fused_with_rgb(self, input, style, noise, to_rgb, rgb_style, skip_up, keep_out):
+        """StyledConv + ToRGB in one kernel (inference): returns (activation or None, rgb)."""
+        return _fp32(self._fused_with_rgb, input, style, noise, to_rgb, rgb_style, skip_up, keep_out)
+
+    def _fused_with_rgb(self, input, style, noise, to_rgb, rgb_style, skip_up, keep_out):
         conv, act = self.conv, self.activate
-        s, demod = self._modulation(style, pre)
-        rgb_s = to_rgb.conv.styles(rgb_latent) if rgb_pre is None else rgb_pre[0]
+        s, demod = _modulation(conv, style)
+        rgb_s = _modulation(to_rgb.conv, rgb_style).style
         if noise is None:
             noise = input.new_empty(input.shape[0], 1, input.shape[2], input.shape[3]).normal_()
         return _native.modconv2d_rgb(input, conv.mfma_weight(), s, demod, noise, self.noise.weight, act.bias,
                                      act.negative_slope, act.scale, to_rgb.conv.weight, rgb_s,
                                      to_rgb.bias, skip_up, to_rgb.conv.scale, keep_out)
 
-    def forward(self, input, style, return_style_scalars=False, noise=None, pre=None):
-        if pre is not None:
-            # style bank (Generator(comod=...)): inference on the fused path only — there is no other consumer of `pre`
-            if torch.is_grad_enabled() or not modconv.hip_conv_ok(input, self.conv.weight) or self.conv.downsample:
-                raise RuntimeError('StyledConv: precomputed styles serve the fused inference path on float32 GPU tensors only')
-            return self._fused(input, None, noise, pre)[0]
-        if (not torch.is_grad_enabled()) and modconv.hip_conv_ok(input, self.conv.weight) and not self.conv.downsample:
-            if torch.is_autocast_enabled():
-                # the fused path hands raw fp32 pointers to the library: run it with autocast off on fp32 inputs (the style
-                # MLP would otherwise produce a bf16 vector; the training path gets this from its autograd Functions)
-                with torch.autocast('cuda', enabled=False):
-                    out, s = self._fused(input.float(), style.float(), None if noise is None else noise.float())
-            else:
-                out, s = self._fused(input, style, noise)
+    def forward(self, input, style, return_style_scalars=False, noise=None):
+        """`style`: a latent column [B, D], or a Modulation (inference on the fused path only: it has no other consumer)."""
+        fused = (not torch.is_grad_enabled()) and modconv.hip_conv_ok(input, self.conv.weight) and not self.conv.downsample
+        if isinstance(style, Modulation) and not fused:
+            raise RuntimeError('StyledConv: precomputed styles serve the fused inference path on float32 GPU tensors only')
+        if fused:
+            out, s = _fp32(self._fused, input, style, noise)
             if return_style_scalars:
                 return out, s.view(s.shape[0], 1, self.conv.in_channel, 1, 1)
             return out
@@ -464,8 +471,8 @@ class ToRGB(nn.Module):
         self.conv = ModulatedConv2d(in_channel, 3, 1, style_dim, demodulate=False)
         self.bias = nn.Parameter(torch.zeros(1, 3, 1, 1))
 
-    def forward(self, input, style, skip=None, return_style_scalars=False, pre=None):
-        s = self.conv.styles(style) if pre is None else pre[0]
+    def forward(self, input, style, skip=None, return_style_scalars=False):
+        s = _modulation(self.conv, style).style
         if skip is not None:
             skip = self.upsample(skip)
         out = modconv.to_rgb(input, self.conv.weight, s, self.bias, skip, self.conv.scale)
@@ -474,25 +481,27 @@ class ToRGB(nn.Module):
         return out
 
 
-class _LatentColumns:
-    """W+ given one column at a time: latent[:, i] calls provider(i) (which may first wait for the stream that is
-    still producing that column).  Used by Forward_Inference_3_Encoder to start the synthesis network before the last
-    style heads of the encoder have finished."""
+class _LatentStyles:
+    """Style source of the synthesis loop, source(layer, i) -> the `style` argument of `layer`, which reads latent column
+    i.  This one: the W+ tensor [B, columns, D] (training and plain inference)."""
 
-    def __init__(self, provider, n_latent):
-        self.provider, self.n = provider, n_latent
+    def __init__(self, latent):
+        self.latent, self.columns = latent, latent.shape[1]
 
-    def __getitem__(self, idx):
-        if not (isinstance(idx, tuple) and len(idx) == 2 and isinstance(idx[1], int) and idx[0] == slice(None)):
-            raise IndexError('only latent[:, i] is served column-wise')
-        return self.provider(idx[1])
+    def __call__(self, layer, i):
+        return self.latent[:, i]
 
 
-class _BankColumns:
-    """latent[:, i] when the style bank already holds every layer's style: the layers get `pre=` and no latent."""
+def _column_styles(provider):
+    """Style source for W+ given one column at a time: provider(i), which may first wait for the stream that is still
+    producing that column.  Used by Forward_Inference_3_Encoder to start the synthesis network before the last style heads
+    of the encoder have finished."""
+    return lambda layer, i: provider(i)
 
-    def __getitem__(self, idx):
-        return None
+
+def _bank_styles(modulations):
+    """Style source for {ModulatedConv2d: Modulation}, every layer's already computed by the style bank."""
+    return lambda layer, i: modulations[layer.conv]
 
 
 class Generator(nn.Module):
@@ -583,7 +592,7 @@ class Generator(nn.Module):
                  use_external_input_tensor=False, external_input_tensor=None, PPL_regularize=False,
                  return_rgb_list=False, return_style_scalars=False, latent_columns=None, comod=None):
         """latent_columns (not in the reference): callable i -> W+[:, i] replacing latent_styles; inference only, with
-        an external input tensor (see _LatentColumns).
+        an external input tensor (see _column_styles).
         comod (not in the reference): (W [T,D], W+ [P,n_styles,D] with P in {1,T}, sliced columns or None for all),
         replacing latent_styles with latent[:, i] = W * W+[:, i] where sliced, W elsewhere — all known before the network
         starts, so the styles and demodulation coefficients of every layer come from the style bank's two launches
@@ -591,106 +600,100 @@ class Generator(nn.Module):
         only, float32 GPU tensors, with an external input tensor of T samples.  The bank reads the LiveWeights buffers, so
         with STYLE_BANK on a Generator whose weights could not be refreshed (parameters that are not contiguous float32
         GPU tensors) raises RuntimeError rather than changing to the per-layer form unasked; STYLE_BANK = False serves it."""
-        bank_pre = None
+        def run(noise, external_input_tensor, *comod):
+            source = self._style_source(noise_z, return_latents, inject_index, truncation, truncation_latent, latent_styles,
+                                        input_is_latent, noise, randomize_noise, use_external_input_tensor,
+                                        external_input_tensor, PPL_regularize, return_style_scalars, latent_columns,
+                                        comod or None)
+            return self._synthesis(*source, PPL_regularize, return_rgb_list, return_style_scalars)
+        if comod is None:
+            return run(noise, external_input_tensor)
+        return _fp32(run, noise, external_input_tensor, *comod)    # the bank takes raw fp32 pointers, like the fused layers
+
+    def _comod_styles(self, comod, external_input_tensor):
+        """Style source of comod=(W, W+, sliced): the bank's result, or (STYLE_BANK = False) the columns one at a time."""
+        w_r, w_plus, sliced = comod
+        for t in (w_r, w_plus, external_input_tensor):
+            _native.require_gpu(t, 'comod input')
+        if (w_r.dim() != 2 or w_plus.dim() != 3 or w_plus.shape[0] not in (1, w_r.shape[0])
+                or w_plus.shape[2] != w_r.shape[1] or w_plus.shape[1] < self.n_latent
+                or external_input_tensor.shape[0] != w_r.shape[0]):
+            raise ValueError('comod: W [T,D], W+ [1 or T, n_styles >= n_latent, D] and an external tensor of T samples')
+        for t in (w_r, w_plus, external_input_tensor):
+            _native.fp(t)           # float32 GPU tensors only: the kernels take raw pointers
+        w_r, w_plus = w_r.contiguous(), w_plus.contiguous()
+        cols = sliced_columns(sliced, self.n_latent, w_plus.shape[1])
+        if STYLE_BANK:
+            if self._live_weights is None or not self._live_weights.active:
+                raise RuntimeError('comod: the style bank needs the Generator\'s refreshed weights (call the module, '
+                                   'with float32 parameters on the GPU)')
+            if getattr(self, '_style_bank', None) is None:
+                self._style_bank = StyleBank(self)
+            return _bank_styles(self._style_bank.run(w_r, w_plus, cols))
+        cache = {}
+
+        def column(i):
+            if i not in cache:
+                cache[i] = comod_column(w_r, w_plus[:, i], i, cols)
+            return cache[i]
+        return _column_styles(column)
+
+    def _style_source(self, noise_z, return_latents, inject_index, truncation, truncation_latent, latent_styles,
+                      input_is_latent, noise, randomize_noise, use_external_input_tensor, external_input_tensor,
+                      PPL_regularize, return_style_scalars, latent_columns, comod):
+        """(style source, noise of every layer, first activation) for the arguments of _forward."""
+        plain = use_external_input_tensor and not (PPL_regularize or return_latents or return_style_scalars)
         if comod is not None:
-            if (PPL_regularize or return_latents or return_style_scalars or torch.is_grad_enabled()
-                    or latent_columns is not None or not use_external_input_tensor or external_input_tensor is None):
+            if not plain or torch.is_grad_enabled() or latent_columns is not None or external_input_tensor is None:
                 raise ValueError('comod serves the plain inference forward (no_grad, external input tensor) only')
-            w_r, w_plus, sliced = comod
-            for t in (w_r, w_plus, external_input_tensor):
-                _native.require_gpu(t, 'comod input')
-            if torch.is_autocast_enabled():
-                with torch.autocast('cuda', enabled=False):
-                    f = (lambda n: None if n is None else n.float())
-                    return self._forward(noise_z, noise=None if noise is None else [f(n) for n in noise],
-                                         randomize_noise=randomize_noise, use_external_input_tensor=True,
-                                         external_input_tensor=external_input_tensor.float(),
-                                         return_rgb_list=return_rgb_list,
-                                         comod=(w_r.float(), w_plus.float(), sliced))
-            if (w_r.dim() != 2 or w_plus.dim() != 3 or w_plus.shape[0] not in (1, w_r.shape[0])
-                    or w_plus.shape[2] != w_r.shape[1] or w_plus.shape[1] < self.n_latent
-                    or external_input_tensor.shape[0] != w_r.shape[0]):
-                raise ValueError('comod: W [T,D], W+ [1 or T, n_styles >= n_latent, D] and an external tensor of T samples')
-            for t in (w_r, w_plus, external_input_tensor):
-                _native.fp(t)           # float32 GPU tensors only: the kernels take raw pointers
-            w_r, w_plus = w_r.contiguous(), w_plus.contiguous()
-            cols = range(self.n_latent) if sliced is None else sliced
-            cols = frozenset(i for i in cols if 0 <= i < w_plus.shape[1])
-            if STYLE_BANK:
-                if self._live_weights is None or not self._live_weights.active:
-                    raise RuntimeError('comod: the style bank needs the Generator\'s refreshed weights (call the module, '
-                                       'with float32 parameters on the GPU)')
-                if getattr(self, '_style_bank', None) is None:
-                    self._style_bank = StyleBank(self)
-                bank_pre = self._style_bank.run(w_r, w_plus, cols)
-            else:
-                cache = {}
-
-                def latent_columns(i):
-                    if i not in cache:
-                        cache[i] = w_r * w_plus[:, i] if i in cols else w_r
-                    return cache[i]
-        if bank_pre is not None:
-            styles = None
+            styles = self._comod_styles(comod, external_input_tensor)
         elif latent_columns is not None:
-            if PPL_regularize or return_latents or return_style_scalars or not use_external_input_tensor:
+            if not plain:
                 raise ValueError('latent_columns serves the plain inference forward only')
-            styles = None
+            styles = _column_styles(latent_columns)
         else:
-            styles = latent_styles if input_is_latent else [self.style(z) for z in noise_z]
-        if noise is None:
-            if randomize_noise:
-                noise = [None] * self.num_layers
-            else:
-                noise = [getattr(self.noises, f'noise_{i}') for i in range(self.num_layers)]
-        if bank_pre is not None:
-            latent = _BankColumns()
-        elif latent_columns is not None:
-            latent = _LatentColumns(latent_columns, self.n_latent)
-        else:
+            ws = latent_styles if input_is_latent else [self.style(z) for z in noise_z]
             if truncation < 1:
-                styles = [truncation_latent + truncation * (w - truncation_latent) for w in styles]
-            latent = self._latents(styles, inject_index)
-
+                ws = [truncation_latent + truncation * (w - truncation_latent) for w in ws]
+            styles = _LatentStyles(self._latents(ws, inject_index))
+        if noise is None:
+            noise = [None if randomize_noise else getattr(self.noises, f'noise_{i}') for i in range(self.num_layers)]
         if use_external_input_tensor:
             assert external_input_tensor is not None
-            out = external_input_tensor
-        else:
-            out = self.input(latent)
+            return styles, noise, external_input_tensor
+        return styles, noise, self.input(styles.latent)
 
+    def _synthesis(self, styles, noise, out, PPL_regularize, return_rgb_list, return_style_scalars):
+        """The synthesis network on the first activation `out`: layer L, reading latent column i, gets styles(L, i)."""
         scalars = []
 
-        def pre(layer):
-            return {} if bank_pre is None else {'pre': bank_pre[layer.conv]}
-
-        def run(layer, x, w, **kw):
-            kw.update(pre(layer))
+        def run(layer, x, i, **kw):
             if return_style_scalars:
-                y, s = layer(x, w, return_style_scalars=True, **kw)
+                y, s = layer(x, styles(layer, i), return_style_scalars=True, **kw)
                 scalars.append(s)
                 return y
-            return layer(x, w, **kw)
+            return layer(x, styles(layer, i), **kw)
 
         # Inference: the RGB branch (ToRGB + skip upsample, HBM-bound) of resolution r has no consumer until the
         # image is returned, so it runs on a side stream beside the MFMA-bound convs of resolution 2r.
         overlap = overlap_ok(out) and not return_style_scalars
         joins = []
 
-        def rgb(layer, x, w, skip):
+        def rgb(layer, x, i, skip):
             if not overlap:
-                return layer(x, w, skip, **pre(layer))
-            join, y = run_on(side, functools.partial(layer, **pre(layer)), x, w, skip)
+                return layer(x, styles(layer, i), skip)
+            join, y = run_on(side, layer, x, styles(layer, i), skip)
             joins.append(join)
             return y
 
         if overlap:
             side, = side_streams(out.device, 1)
-        out = run(self.conv1, out, latent[:, 0], noise=noise[0])
-        skip = rgb(self.to_rgb1, out, latent[:, 1], None)
+        out = run(self.conv1, out, 0, noise=noise[0])
+        skip = rgb(self.to_rgb1, out, 1, None)
         rgbs = [skip]
         for blk, to_rgb in enumerate(self.to_rgbs):
             i = 1 + 2 * blk
-            conv_b = self.convs[2 * blk + 1]
+            conv_a, conv_b = self.convs[2 * blk], self.convs[2 * blk + 1]
             b_, _, h_, w_ = out.shape
             # Inference, last resolution: its ToRGB cannot hide beside later convs (there are none) and is the only
             # consumer of conv_b's activation, so it rides in conv_b's epilogue and the [B,C,size,size] activation is
@@ -705,19 +708,19 @@ class Generator(nn.Module):
                     joins.append(join_up)
                 else:
                     skip_up = to_rgb.upsample(skip)
-                out = self.convs[2 * blk](out, latent[:, i], noise=noise[i], **pre(self.convs[2 * blk]))
+                out = conv_a(out, styles(conv_a, i), noise=noise[i])
                 if overlap:
                     join_up()
-                out, skip = conv_b.fused_with_rgb(out, latent[:, i + 1], noise[i + 1], to_rgb, latent[:, i + 2], skip_up,
-                                                  keep_out=False, pre=pre(conv_b).get('pre'), rgb_pre=pre(to_rgb).get('pre'))
+                out, skip = conv_b.fused_with_rgb(out, styles(conv_b, i + 1), noise[i + 1], to_rgb, styles(to_rgb, i + 2),
+                                                  skip_up, keep_out=False)
                 rgbs.append(skip)
                 continue
-            out = run(self.convs[2 * blk], out, latent[:, i], noise=noise[i])
-            out = run(self.convs[2 * blk + 1], out, latent[:, i + 1], noise=noise[i + 1])
-            if return_style_scalars and i + 3 == latent.shape[1]:   # style scalars of the last ToRGB only (:660-662)
-                skip = run(to_rgb, out, latent[:, i + 2], skip=skip)
+            out = run(conv_a, out, i, noise=noise[i])
+            out = run(conv_b, out, i + 1, noise=noise[i + 1])
+            if return_style_scalars and i + 3 == styles.columns:   # style scalars of the last ToRGB only (:660-662)
+                skip = run(to_rgb, out, i + 2, skip=skip)
             else:
-                skip = rgb(to_rgb, out, latent[:, i + 2], skip)
+                skip = rgb(to_rgb, out, i + 2, skip)
             rgbs.append(skip)
         for join in joins[-1:]:
             join()                      # the side stream is in order: joining its last launch joins all of them
@@ -729,7 +732,7 @@ class Generator(nn.Module):
         if PPL_regularize:
             # path-length regulariser evaluated inside forward so it shards with the batch (stylegan2.py:683-688)
             probe = torch.randn_like(image) / math.sqrt(image.shape[2] * image.shape[3])
-            grad, = autograd.grad(outputs=(image * probe).sum(), inputs=latent, create_graph=True)
+            grad, = autograd.grad(outputs=(image * probe).sum(), inputs=styles.latent, create_graph=True)
             return image, torch.sqrt(grad.pow(2).sum(2).mean(1))
 
         returns = rgbs if return_rgb_list else image

@@ -190,6 +190,25 @@ def test_generator_comod_bits_narrow(T, P):
     assert not torch.equal(plain, _plain(G, w, wp, tsr, None, randomize_noise=False))
 
 
+def test_generator_latent_columns_bits_narrow():
+    """W+ handed over one column at a time is the W+ tensor, bit for bit (the pipelined forward is compared to a
+    tolerance only because its encoders are not reproducible; the Generator is), each column asked for in layer order."""
+    G = _narrow_g()
+    lat = synth.tensor('gcols/lat', (3, G.n_latent, 512)).to(dev())
+    tsr = synth.tensor('gcols/tsr', (3, 16, 4, 4)).to(dev())
+    kw = dict(use_external_input_tensor=True, external_input_tensor=tsr, randomize_noise=False)
+    asked = []
+
+    def column(i):
+        asked.append(i)
+        return lat[:, i]
+    with torch.no_grad():
+        tensor = G(None, latent_styles=[lat], input_is_latent=True, **kw)
+        columns = G(None, latent_columns=column, **kw)
+    assert tuple(tensor.shape) == (3, 3, 64, 64) and torch.equal(columns, tensor)
+    assert asked == [0, 1] + [i + j for i in range(1, G.n_latent - 1, 2) for j in range(3)]
+
+
 def test_generator_comod_bits_full_256():
     """Generator(256, 512, 8) at T = 2: a Winograd layer (16^2..128^2 x >= 256 channels) and the fused RGB epilogue at
     the last resolution are on the path."""

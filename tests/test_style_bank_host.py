@@ -106,6 +106,39 @@ def test_comod_is_rejected_outside_the_plain_inference_forward():
         G(None, **kw)                                                   # grad mode
 
 
+def test_sliced_columns_and_comod_column():
+    """The one statement of the co-modulation rule that the pipelined, the serial and the per-layer forward share."""
+    from op.style_bank import comod_column, sliced_columns
+    assert sliced_columns(None, 10, 18) == frozenset(range(10))
+    assert sliced_columns(None, 14, 10) == frozenset(range(10))
+    assert sliced_columns([-1, 0, 3, 9, 10, 99], 10, 10) == frozenset({0, 3, 9})
+    assert sliced_columns(range(2, 20), 18, 10) == frozenset(range(2, 10))
+    assert sliced_columns([], 10, 10) == frozenset()
+    assert isinstance(sliced_columns([1], 10, 10), frozenset)
+    w = synth.tensor('comod/w', (3, 16))
+    for wp in (synth.tensor('comod/wp3', (3, 10, 16)), synth.tensor('comod/wp1', (1, 10, 16))):
+        sliced = sliced_columns([0, 3, 4, 12], 10, wp.shape[1])
+        for i in range(wp.shape[1]):
+            col = comod_column(w, wp[:, i], i, sliced)
+            assert tuple(col.shape) == (3, 16)
+            if i in (0, 3, 4):
+                assert torch.equal(col, w * wp[:, i]), i
+            else:
+                assert torch.equal(col, w), i
+
+
+def test_styled_conv_refuses_a_precomputed_modulation_outside_the_fused_path():
+    import stylegan2
+    from op.style_bank import Modulation
+    layer = stylegan2.StyledConv(8, 6, 3, 16)
+    pre = Modulation(torch.ones(2, 8), torch.ones(2, 6))
+    msg = 'precomputed styles serve the fused inference path on float32 GPU tensors only'
+    with torch.enable_grad(), pytest.raises(RuntimeError, match=msg):
+        layer(torch.zeros(2, 8, 4, 4), pre)
+    with torch.no_grad(), pytest.raises(RuntimeError, match=msg):       # no_grad, but not on the GPU
+        layer(torch.zeros(2, 8, 4, 4), pre)
+
+
 def test_style_bank_starts_without_table_after_deepcopy():
     import copy
     from op.style_bank import StyleBank

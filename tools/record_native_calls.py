@@ -10,7 +10,7 @@ GPU.  After the first _native.lib() the module's `_lib` cache is replaced by a p
 to one list: integers and floats as they are; a pointer argument (by the entry point's argtypes) as "null", as its address
 & 15 when it is an address, or as "host" for a ctypes object (byref out-parameters, host arrays).  An observer appends
     ["begin", name, info]  /  ["end"]
-to the same list.  Needs a GPU; uses nothing but the package (tools/ and tests/ helpers only for deterministic inputs).
+to the same list, and the callable given as `latent_columns=` appends ["column", i] at each fetch.  Needs a GPU; uses nothing but the package (tools/ and tests/ helpers only for deterministic inputs).
 """
 import ctypes
 import json
@@ -107,6 +107,59 @@ def generator(d):
     ((lengths - 0.5).pow(2).mean() + 0 * img[0, 0, 0, 0]).backward()
 
 
+def _g(size, dim, d):
+    """(G, W+ [2,n,dim], tensor [2,cin,4,4], W [2,dim], per-frame W+ [2,n,dim]) of a seeded Generator(size, dim, 2)."""
+    import stylegan2
+    G = stylegan2.Generator(size, dim, 2)
+    G.load_state_dict(synth.state_dict('generator', G.state_dict(), seed=3))
+    G = G.to(d).eval()
+    n, cin = G.n_latent, G.conv1.conv.weight.shape[2]
+    tag = f'g{size}/'
+    return (G, t(tag + 'lat', (2, n, dim), d), t(tag + 'tsr', (2, cin, 4, 4), d), t(tag + 'w', (2, dim), d),
+            t(tag + 'wplus', (2, n, dim), d, scale=0.5, shift=1.0))
+
+
+def generator_styles(d):
+    """Every way the Generator's layers get their style (W+ tensor, column callable, style bank, per-layer comod), with the
+    column fetches in the log: for refactors of the host code between the launches."""
+    import stylegan2
+    G, lat, tsr, w, wplus = _g(64, 64, d)
+    ext = dict(use_external_input_tensor=True, external_input_tensor=tsr)
+
+    def column(i):
+        LOG.append(['column', i])
+        return lat[:, i]
+
+    with torch.no_grad():
+        section('generator latent_columns')
+        G(None, latent_columns=column, **ext)
+        section('generator comod sliced per-frame')
+        G(None, comod=(w, wplus, [0, 3, 4]), **ext)
+        prev = stylegan2.STYLE_BANK
+        try:
+            stylegan2.STYLE_BANK = False
+            section('generator comod, STYLE_BANK off')
+            G(None, comod=(w, wplus[:1].contiguous(), None), **ext)
+            section('generator comod sliced per-frame, STYLE_BANK off')
+            G(None, comod=(w, wplus, [0, 3, 4]), **ext)
+        finally:
+            stylegan2.STYLE_BANK = prev
+        section('generator return_style_scalars')
+        G(None, latent_styles=[lat], input_is_latent=True, return_style_scalars=True, **ext)
+        with torch.autocast('cuda', dtype=torch.bfloat16):
+            section('generator plain under autocast')
+            G(None, latent_styles=[lat], input_is_latent=True, **ext)
+            section('generator comod under autocast')
+            G(None, comod=(w, wplus, [0, 3, 4]), **ext)
+        # the smallest Generator that reaches the Winograd form, the fused RGB epilogue and the row-march blur
+        G, lat, tsr, w, wplus = _g(256, 512, d)
+        ext = dict(use_external_input_tensor=True, external_input_tensor=tsr, randomize_noise=False)
+        section('generator 256 plain')
+        G(None, latent_styles=[lat], input_is_latent=True, **ext)
+        section('generator 256 comod')
+        G(None, comod=(w, wplus, [0, 3, 4]), **ext)
+
+
 def small_ops(d):
     from op import upfirdn2d, fused_leaky_relu, face_region, lpips_distance, eval_scores
     section('upfirdn2d')
@@ -155,6 +208,7 @@ def main():
     _native.set_observer(RecordingObserver())
     try:
         generator(d)
+        generator_styles(d)
         small_ops(d)
         torch.cuda.synchronize()
     finally:
