@@ -123,6 +123,25 @@ class PNetLin(nn.Module):
             val = r if val is None else val + r
         return val
 
+    def features_scaled(self, s):
+        """The five trunk taps of an input that already went through the ScalingLayer: what forward_scaled computes for
+        each side, to be kept when one side never changes (the target of an image projection)."""
+        return self.net(s)
+
+    def forward_features(self, f0, s1):
+        """forward_scaled(s0, s1) with the trunk pass over s0 already done: f0 = features_scaled(s0)."""
+        f1 = self.net(s1)
+        val = None
+        for i in range(len(self.chns)):
+            lin = getattr(self, f'lin{i}').model
+            if FUSED and not self.training and lpips_distance_serves(f0[i], f1[i], lin[-1].weight):
+                r = lpips_distance(f0[i], f1[i], lin[-1].weight)
+            else:
+                diff = (normalize_tensor(f0[i]) - normalize_tensor(f1[i])) ** 2
+                r = lin(diff).mean([2, 3], keepdim=True)
+            val = r if val is None else val + r
+        return val
+
 
 class PerceptualLoss(nn.Module):
     """`lpips.PerceptualLoss(model='net-lin', net='vgg', ...)` of the reference's Module_Fix_Setup; returns [N,1,1,1]."""
@@ -142,3 +161,13 @@ class PerceptualLoss(nn.Module):
     def forward_scaled(self, pred_s, target_s):
         """forward on inputs that are already scaled (ScalingLayer applied): the same argument order."""
         return self.net.forward_scaled(target_s, pred_s)
+
+    def target_features(self, target_s):
+        """The trunk taps of a scaled target, detached: computed once for a target that stays (image projection)."""
+        with torch.no_grad():
+            return [f.detach() for f in self.net.features_scaled(target_s)]
+
+    def forward_cached(self, pred_s, target_feats):
+        """forward_scaled(pred_s, target_s) with target_feats = target_features(target_s): the same argument order inside
+        (the target's features are f0, the prediction's f1), one trunk pass instead of two."""
+        return self.net.forward_features(target_feats, pred_s)

@@ -66,6 +66,10 @@ def lib():
     _sig(L.fmgan_face_input_f32, [vp] * 5 + [i] * 4 + [vp])
     _sig(L.fmgan_lpips_pair_input_select, [i] * 8)
     _sig(L.fmgan_lpips_pair_input_f32, [vp] * 5 + [i] * 8 + [vp])
+    _sig(L.fmgan_projection_loss_select, [i] * 4)
+    _sig(L.fmgan_projection_loss_blocks, [i] * 4)
+    _sig(L.fmgan_projection_loss_fwd_f32, [vp] * 7 + [i] * 4 + [vp])
+    _sig(L.fmgan_projection_loss_bwd_f32, [vp] * 7 + [i] * 4 + [vp])
     _sig(L.fmgan_lpips_distance_blocks, [i] * 3)
     _sig(L.fmgan_lpips_distance_f32, [vp] * 4 + [i, i, i, f, vp])
     _sig(L.fmgan_lpips_distance_backward_f32, [vp] * 6 + [i, i, i, f, vp])
@@ -513,6 +517,67 @@ def lpips_pair_input(image, shift, scale, window, f):
         out1 = torch.empty_like(out0)
         st = lib().fmgan_lpips_pair_input_f32(pi, ps, pc, fp(out0), fp(out1), n // 2, h, w, y0, x0, hc, wc, f, stream)
     return (out0, out1) if served(st, 'lpips_pair_input') else None
+
+
+def _projection_loss_args(x, target, mask, vectors):
+    """(batch, size, f) after the checks shared by the two projection-stage entry points: shapes first (ValueError), then
+    device, dtype (RuntimeError from fp(), no fallback) and layout.  `vectors`: the three-float device vectors."""
+    if x.ndim != 4 or x.shape[1] != 3 or tuple(target.shape) != tuple(x.shape) or \
+            (mask is not None and tuple(mask.shape) != tuple(x.shape[2:])) or any(v.numel() != 3 for v in vectors):
+        raise ValueError(f'projection_loss: x {tuple(x.shape)}, target {tuple(target.shape)}, mask '
+                         f'{None if mask is None else tuple(mask.shape)}: expected two [B, 3, S, S] tensors, an [S, S] '
+                         f'mask or none, and three floats each of shift / scale')
+    require_gpu(x, 'x')
+    for t, name in ((x, 'x'), (target, 'target'), (mask, 'mask')) + tuple((v, 'shift / scale') for v in vectors):
+        if t is not None:
+            fp(t)
+            if not t.is_contiguous():
+                raise RuntimeError(f'projection_loss: {name} must be contiguous, got strides {t.stride()}')
+            if t.device != x.device:
+                raise RuntimeError(f'projection_loss: {name} must be on x\'s device')
+    b, _, h, w = x.shape
+    return b, h, w, max(h // 256, 1)
+
+
+def projection_loss_fwd(x, target, mask, shift, scale, want_y=True):
+    """Forward of the projection criterion's image stage in one launch (csrc/projection_loss.hip): x, target [B, 3, S, S]
+    f32 contiguous, S in {256, 512, 1024}, mask [S, S] or None, shift / scale the three floats of lpips.ScalingLayer's
+    buffers on x's device -> (partial, y): partial [blocks] f32, fixed-order sums of (x - target)^2 (* mask) whose total is
+    the squared error (bit-reproducible; add with sum(dtype=float64)); y [B, 3, 256, 256] in channels_last storage,
+    (bilinear(clamp(x, -1, 1)) - shift) / scale, or None when not wanted.  None (alone) when the library declines the
+    shape: the caller then evaluates the composite."""
+    b, h, w, f = _projection_loss_args(x, target, mask, (shift, scale))
+    blocks = 0 if b == 0 else lib().fmgan_projection_loss_blocks(b, h, w, f)
+    if blocks <= 0:
+        return None
+    with launching(x, 'projection_loss', (b, h, f, mask is not None, bool(want_y), 0)) as stream:
+        partial = torch.empty((blocks,), dtype=torch.float32, device=x.device)
+        y = _nhwc_empty(b, 3, 256, 256, x.device) if want_y else None
+        st = lib().fmgan_projection_loss_fwd_f32(fp(x), fp(target), fp(mask), fp(shift), fp(scale), fp(partial), fp(y),
+                                                 b, h, w, f, stream)
+    return (partial, y) if served(st, 'projection_loss_fwd') else None
+
+
+def projection_loss_bwd(x, target, mask, g_y, k, scale):
+    """Backward of the stage in one launch: grad_x = k * (x - target) * mask + the gradient g_y [B, 3, 256, 256]
+    (channels_last storage, or None) of y carried back through ScalingLayer, the bilinear reduction and the clamp.
+    k: one f32 element ON THE DEVICE (grad_loss * 2 * mse_weight / denominator), read by the kernel (no .item()).
+    None when the library declines the shape."""
+    b, h, w, f = _projection_loss_args(x, target, mask, (scale,))
+    if k.numel() != 1 or k.device != x.device:
+        raise ValueError(f'projection_loss_bwd: k must hold one element on x\'s device, got {tuple(k.shape)} on {k.device}')
+    if g_y is not None:
+        if tuple(g_y.shape) != (b, 3, 256, 256) or not nhwc_dense(g_y) or g_y.device != x.device:
+            raise ValueError(f'projection_loss_bwd: g_y {tuple(g_y.shape)} with strides {g_y.stride()}: expected '
+                             f'[{b}, 3, 256, 256] in channels_last storage on x\'s device')
+    pk, pg = fp(k), fp(g_y)
+    if b == 0 or lib().fmgan_projection_loss_select(b, h, w, f) <= 0:
+        return None
+    with launching(x, 'projection_loss', (b, h, f, mask is not None, g_y is not None, 1)) as stream:
+        grad_x = torch.empty_like(x)
+        st = lib().fmgan_projection_loss_bwd_f32(fp(x), fp(target), fp(mask), pg, pk, fp(scale), fp(grad_x), b, h, w, f,
+                                                 stream)
+    return grad_x if served(st, 'projection_loss_bwd') else None
 
 
 def nhwc_dense(t):

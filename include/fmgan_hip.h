@@ -259,6 +259,43 @@ int fmgan_lpips_pair_input_f32(const float *img, const float *shift, const float
                                int pairs, int h, int w, int y0, int x0, int hc, int wc, int f, void *stream);
 
 /*
+ * Image stage of the projection criterion (Evaluation/image_projection/project: mse (+ mask) and the LPIPS trunk input
+ * of the optimised image), forward and backward, one launch each.
+ *   x, target [batch, 3, h, w] contiguous f32 NCHW, h = w = 256 * f, f in {1, 2, 4};  mask [h, w] f32 or NULL.
+ *   forward : partial[i], i < fmgan_projection_loss_blocks(...): the sum over block i's elements of q = (x - t)^2, or of
+ *             q * mask[row, col]; per-lane serial fma, wave butterfly, waves in order: no atomics, bit-reproducible.  The
+ *             caller adds the partials (in float64).
+ *             y [batch, 256, 256, 3] dense (NHWC storage of a channels_last [batch, 3, 256, 256]) or NULL (not wanted):
+ *             with a = clamp(x, -1, 1) (NaN stays NaN), v = a at f = 1; at f = 2 or 4, with o = f/2 - 1, a, b the clamped
+ *             pixels at row f*i + o, columns f*j + o and + 1, and c, d the same columns one row below,
+ *                 v = 0.5*(0.5*a + 0.5*b) + 0.5*(0.5*c + 0.5*d)
+ *             in exactly this association (columns inside a row first), no fused multiply-add: bilinear interpolation
+ *             to 256 with align_corners = false;  y[n, i, j, c] = (v - shift[c]) / scale[c], IEEE subtraction and
+ *             correctly rounded division.  shift, scale: DEVICE pointers to three floats (needed only with y).
+ *   backward: grad_x[n, c, row, col] = (k[0] * (x - t)) * mask[row, col] + p,  (without a mask: k[0] * (x - t) + p)
+ *             p = wf * (g_y[n, row/f, col/f, c] / scale[c]) where -1 <= x <= 1 (the bounds included) and (row, col) is
+ *             one of the four taps of its reduced pixel, 0 otherwise, wf = 1 at f = 1 and 0.25 at f = 2, 4; in exactly
+ *             this association, no fused multiply-add.  g_y NULL: p = 0 everywhere.  k: DEVICE pointer to one float,
+ *             grad_loss * 2 * mse_weight / denominator (no host copy, no synchronisation).
+ *   The mask multiplies: a NaN of x or target reaches the sum and its own grad_x element also where the mask is 0.
+ * No allocation, no synchronisation, no global state; the kernels run on `stream`.  Dword-aligned pointers suffice.
+ * fmgan_projection_loss_select is the launch's plan with the launch left out: the positive kernel id f exactly when the
+ * launches with these arguments run, otherwise the status they return: FMGAN_EINVAL for a non-positive argument (the
+ * launches also for a NULL x, target, partial, grad_x or k, a y without shift and scale, a g_y without scale),
+ * FMGAN_EUNSUPPORTED for h != w, h outside {256, 512, 1024} or f != h / 256 (the caller then evaluates the composite),
+ * FMGAN_EOVERFLOW when batch * blocks per sample exceeds the grid's 2^31 - 1 (element offsets are 64-bit).
+ * fmgan_projection_loss_blocks: the number of partials, 0 where select is not positive.
+ */
+int fmgan_projection_loss_select(int batch, int h, int w, int f);
+int fmgan_projection_loss_blocks(int batch, int h, int w, int f);
+int fmgan_projection_loss_fwd_f32(const float *x, const float *target, const float *mask, const float *shift,
+                                  const float *scale, float *partial, float *y, int batch, int h, int w, int f,
+                                  void *stream);
+int fmgan_projection_loss_bwd_f32(const float *x, const float *target, const float *mask, const float *g_y,
+                                  const float *k, const float *scale, float *grad_x, int batch, int h, int w, int f,
+                                  void *stream);
+
+/*
  * Inference glue of the pSp encoder's IR / IR-SE units (psp_encoder_model/encoders/helpers.py): what runs between the
  * MIOpen convolutions of a unit.  All tensors f32 in NHWC storage ([batch, h, w, channels]); a BatchNorm2d in eval mode is
  * given as its four [channels] vectors and eps and is evaluated in-kernel on every launch as
