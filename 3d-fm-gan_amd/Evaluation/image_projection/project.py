@@ -38,6 +38,7 @@ import os
 
 import torch
 
+from lpips import scaling_layer_of
 from op.projection_loss import TARGET, projection_stage, projection_stage_serves, projection_trunk_input
 
 # Image stage of the criterion on the HIP kernels where they serve; False keeps the aten composite.
@@ -70,14 +71,6 @@ class ImageReconstructionLoss(torch.nn.Module):
             self.perceptual = percept
         self.use_lpips = False
 
-    def _scaling_layer(self):
-        """The perceptual module's ScalingLayer when it can take cached target features: an eval-mode module with
-        forward_cached."""
-        p = self.perceptual
-        if not isinstance(p, torch.nn.Module) or p.training or not hasattr(p, 'forward_cached'):
-            return None
-        return getattr(getattr(p, 'net', None), 'scaling_layer', None)
-
     def _lpips(self, y, output, target, mask, perceptual_size, scaling):
         """The LPIPS term.  y: the trunk input of `output` when the stage has produced it, else None."""
         if mask is not None:
@@ -109,7 +102,8 @@ class ImageReconstructionLoss(torch.nn.Module):
         else:
             denom = output.numel()
         may_join = self.mse_T > 0.0
-        scaling = self._scaling_layer() if may_join else None
+        # the perceptual module's ScalingLayer when it can take cached target features
+        scaling = scaling_layer_of(self.perceptual, 'forward_cached') if may_join else None
         fuse = PROJECT_FUSE and (scaling is not None or not may_join)
         served = fuse and perceptual_size == TARGET and projection_stage_serves(output, target, mask, scaling)
         # the trunk input comes with the stage when LPIPS is on; the kernel also writes it in a call in which LPIPS may

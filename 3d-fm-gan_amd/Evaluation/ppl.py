@@ -31,6 +31,7 @@ Out of scope: Z-space sampling with slerp, FID, image projection.
 import numpy as np
 import torch
 
+from lpips import scaling_layer_of
 from op.ppl_input import pair_input, pair_resize
 
 
@@ -43,13 +44,6 @@ def default_sampler(batch_index, batch_size, latent_dim, device):
     noise_z = torch.randn([batch_size * 2, latent_dim], device=device)
     lerp_t = torch.rand(batch_size, device=device)
     return noise_z, lerp_t
-
-
-def _scaling_layer(percept):
-    """percept's ScalingLayer when the fused input stage applies to it: an eval-mode module with forward_scaled."""
-    if not isinstance(percept, torch.nn.Module) or percept.training or not hasattr(percept, 'forward_scaled'):
-        return None
-    return getattr(getattr(percept, 'net', None), 'scaling_layer', None)
 
 
 def Interpolated_Latents(style, noise_z, lerp_t, eps):
@@ -73,7 +67,7 @@ def PPL_Distances(generator, percept, n_sample, batch_size, eps, latent_dim, dev
         raise ValueError(f'PPL_Distances: n_sample {n_sample} gives no batch of {batch_size} pairs')
     sampler = sampler or default_sampler
     style = getattr(generator, 'module', generator).style
-    scaling = _scaling_layer(percept)
+    scaling = scaling_layer_of(percept, 'forward_scaled')     # None: the fused input stage does not apply
     distances = []
     with torch.no_grad():
         for idx in range(n_sample // batch_size):

@@ -63,3 +63,41 @@ typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// Four consecutive floats at p + i of a run of n.  VEC: one 16-byte access (the caller has checked alignment and
+// n % 4 == 0); otherwise four bounded scalar accesses, 0 past the end: the same values in the same lanes.
+template <bool VEC, typename I>
+__device__ __forceinline__ f32x4 load4(const float* __restrict__ p, I i, I n) {
+  if constexpr (VEC) {
+    return *reinterpret_cast<const f32x4*>(p + i);
+  } else {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (i < n) v.x = p[i];
+    if (i + 1 < n) v.y = p[i + 1];
+    if (i + 2 < n) v.z = p[i + 2];
+    if (i + 3 < n) v.w = p[i + 3];
+    return v;
+  }
+}
+
+template <bool VEC, typename I>
+__device__ __forceinline__ void store4(float* __restrict__ p, I i, I n, f32x4 v) {
+  if constexpr (VEC) {
+    *reinterpret_cast<f32x4*>(p + i) = v;
+  } else {
+    if (i < n) p[i] = v.x;
+    if (i + 1 < n) p[i + 1] = v.y;
+    if (i + 2 < n) p[i + 2] = v.z;
+    if (i + 3 < n) p[i + 3] = v.w;
+  }
+}
+
+// grid.x of a stage that walks `work` block-sized pieces per sample: no block without work, about 8 blocks per CU over
+// the batch, at most `max_blocks`.
+static inline int fmgan_stage_blocks(long long work, int batch, int max_blocks) {
+  long long gx = work;
+  const long long want = ((long long)FMGAN_NUM_CU * 8 + batch - 1) / batch;
+  if (gx > want) gx = want;
+  if (gx > max_blocks) gx = max_blocks;
+  return (int)(gx < 1 ? 1 : gx);
+}

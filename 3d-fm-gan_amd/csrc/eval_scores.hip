@@ -21,31 +21,17 @@
 // the same order: both forms give identical bits.
 //
 // L1 partial sums, fixed order, no atomics: a row of a unit is summed serially from 0 (channel 0..2, then column:
-// 3*CS <= 24 terms), the k <= 8 row sums are added serially, then the wave butterfly (6 steps) and the four waves in
-// order (2 steps) -> partial[b, block].  Longest serial chain: 24 + 8 + 6 + 2 = 40 additions, for every image size; all
-// terms are non-negative, so the relative error of a partial is at most 40 * 2^-24 = 2.4e-6.
+// 3*CS <= 24 terms), the k <= 8 row sums are added serially, then block_sum_ordered of block_sum.h (butterfly: 6 steps,
+// four waves: 2 steps) -> partial[b, block].  Longest serial chain: 24 + 8 + 6 + 2 = 40 additions, for every image size;
+// all terms are non-negative, so the relative error of a partial is at most 40 * 2^-24 = 2.4e-6.
 #include <climits>
 
-#include "common.h"
+#include "block_sum.h"
 
 namespace {
 
 constexpr int FI_THREADS = 256;
 static_assert(FI_THREADS == 4 * FMGAN_WAVE, "the block sum below adds four waves");
-
-template <bool VEC>
-__device__ __forceinline__ f32x4 fi_load(const float* __restrict__ row, int x, int w) {
-  if constexpr (VEC) {
-    return *reinterpret_cast<const f32x4*>(row + x);
-  } else {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (x < w) v.x = row[x];
-    if (x + 1 < w) v.y = row[x + 1];
-    if (x + 2 < w) v.z = row[x + 2];
-    if (x + 3 < w) v.w = row[x + 3];
-    return v;
-  }
-}
 
 // (c0*r + c1*g) + c2*b with three separately rounded products
 __device__ __forceinline__ float fi_gray(float r, float g, float b) {
@@ -122,8 +108,8 @@ __global__ __launch_bounds__(FI_THREADS) void face_input_f32(const float* __rest
       for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int q = 0; q < CS / 4; ++q) {
-          va[c][q] = fi_load<VEC>(ra + c * hw, x0 + 4 * q, w);
-          if constexpr (PAIR) vb[c][q] = fi_load<VEC>(rb + c * hw, x0 + 4 * q, w);
+          va[c][q] = load4<VEC>(ra + c * hw, x0 + 4 * q, w);
+          if constexpr (PAIR) vb[c][q] = load4<VEC>(rb + c * hw, x0 + 4 * q, w);
         }
 #pragma unroll
       for (int q = 0; q < CS / 4; ++q) {
@@ -146,10 +132,8 @@ __global__ __launch_bounds__(FI_THREADS) void face_input_f32(const float* __rest
   }
   if constexpr (PAIR) {
     if (partial) {                                             // uniform over the grid
-      for (int m = 32; m > 0; m >>= 1) l1 += __shfl_xor(l1, m, FMGAN_WAVE);
-      if ((threadIdx.x & (FMGAN_WAVE - 1)) == 0) red[threadIdx.x / FMGAN_WAVE] = l1;
-      __syncthreads();
-      if (threadIdx.x == 0) partial[(long long)sample * gx + blk] = (red[0] + red[1]) + (red[2] + red[3]);
+      const float sum = block_sum_ordered<4>(l1, red);
+      if (threadIdx.x == 0) partial[(long long)sample * gx + blk] = sum;
     }
   }
 }

@@ -17,7 +17,8 @@
 // grid.x = blocks per sample (fmgan_face_region_blocks).  The scalar form (misaligned pointers or H*W % 4 != 0) walks
 // the same groups with 4 bounded scalar loads, so it performs the same arithmetic in the same order: both forms give
 // bit-identical partials.  Forward partial sums: per-lane serial (explicit fma), wave butterfly, 4 waves in order
-// (the form of fba_bwd_bias_f32) -> partial[b, blockIdx.x]; no atomics, bit-reproducible run to run.
+// (the association of block_sum_ordered in block_sum.h, spelled out in the sample loop) -> partial[b, blockIdx.x]; no
+// atomics, bit-reproducible run to run.
 #include <climits>
 
 #include "common.h"
@@ -29,32 +30,6 @@ constexpr int FR_MAX_BLOCKS_X = 1024;
 
 enum { FR_LOSS = 0, FR_GRAD = 1, FR_MASK = 2 };
 static_assert(FR_THREADS == 4 * FMGAN_WAVE, "the block sum below adds four waves");
-
-template <bool VEC>
-__device__ __forceinline__ f32x4 fr_load(const float* __restrict__ plane, long long p, long long hw) {
-  if constexpr (VEC) {
-    return *reinterpret_cast<const f32x4*>(plane + p);
-  } else {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (p < hw) v.x = plane[p];
-    if (p + 1 < hw) v.y = plane[p + 1];
-    if (p + 2 < hw) v.z = plane[p + 2];
-    if (p + 3 < hw) v.w = plane[p + 3];
-    return v;
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void fr_store(float* __restrict__ plane, long long p, long long hw, f32x4 v) {
-  if constexpr (VEC) {
-    *reinterpret_cast<f32x4*>(plane + p) = v;
-  } else {
-    if (p < hw) plane[p] = v.x;
-    if (p + 1 < hw) plane[p + 1] = v.y;
-    if (p + 2 < hw) plane[p + 2] = v.z;
-    if (p + 3 < hw) plane[p + 3] = v.w;
-  }
-}
 
 __device__ __forceinline__ float fr_sq(bool m, float r, float g, float acc) {
   const float d = m ? r - g : 0.f;
@@ -85,7 +60,7 @@ __global__ __launch_bounds__(FR_THREADS) void face_region_f32(const float* __res
       f32x4 rv[CT > 0 ? CT : 1];
       f32x4 s = {0.f, 0.f, 0.f, 0.f};
       for (int c = 0; c < C; ++c) {
-        const f32x4 v = fr_load<VEC>(rb + c * hw, p, hw);
+        const f32x4 v = load4<VEC>(rb + c * hw, p, hw);
         if constexpr (CT > 0) rv[c] = v;
         s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
       }
@@ -96,13 +71,13 @@ __global__ __launch_bounds__(FR_THREADS) void face_region_f32(const float* __res
       const bool mw = p + 3 < hw && s.w * factor > -1.f;
       if constexpr (MODE == FR_MASK) {
         const f32x4 mv = {mx ? 1.f : 0.f, my ? 1.f : 0.f, mz ? 1.f : 0.f, mw ? 1.f : 0.f};
-        fr_store<VEC>(out + (long long)b * hw, p, hw, mv);
+        store4<VEC>(out + (long long)b * hw, p, hw, mv);
       } else {
         for (int c = 0; c < C; ++c) {
           f32x4 a;
           if constexpr (CT > 0) a = rv[c];
-          else a = fr_load<VEC>(rb + c * hw, p, hw);
-          const f32x4 v = fr_load<VEC>(gb + c * hw, p, hw);
+          else a = load4<VEC>(rb + c * hw, p, hw);
+          const f32x4 v = load4<VEC>(gb + c * hw, p, hw);
           if constexpr (MODE == FR_LOSS) {
             acc = fr_sq(mx, a.x, v.x, acc);
             acc = fr_sq(my, a.y, v.y, acc);
@@ -111,7 +86,7 @@ __global__ __launch_bounds__(FR_THREADS) void face_region_f32(const float* __res
           } else {
             const f32x4 d = {fr_grad(mx, a.x, v.x, cf), fr_grad(my, a.y, v.y, cf), fr_grad(mz, a.z, v.z, cf),
                              fr_grad(mw, a.w, v.w, cf)};
-            fr_store<VEC>(out + (long long)b * chw + c * hw, p, hw, d);
+            store4<VEC>(out + (long long)b * chw + c * hw, p, hw, d);
           }
         }
       }
@@ -180,11 +155,7 @@ int fr_launch(const float* r, const float* g, float* out, const float* grad_loss
 extern "C" int fmgan_face_region_blocks(int batch, long long hw) {
   if (batch <= 0 || hw <= 0) return 0;
   const long long groups = (hw + 3) / 4;
-  long long gx = (groups + FR_THREADS - 1) / FR_THREADS;            // no block without work
-  const long long want = ((long long)FMGAN_NUM_CU * 8 + batch - 1) / batch;   // ~8 blocks per CU over the batch
-  if (gx > want) gx = want;
-  if (gx > FR_MAX_BLOCKS_X) gx = FR_MAX_BLOCKS_X;
-  return (int)(gx < 1 ? 1 : gx);
+  return fmgan_stage_blocks((groups + FR_THREADS - 1) / FR_THREADS, batch, FR_MAX_BLOCKS_X);
 }
 
 extern "C" int fmgan_face_region_loss_f32(const float* r, const float* g, float* partial, int batch, int channels,

@@ -252,7 +252,8 @@ extern "C" int fmgan_fused_bias_act(int dtype, const void* x, const void* bias, 
 // ...)` followed by `grad_input.sum(dims)` for the bias: a second kernel that reads the whole gradient again (667 torch
 // reduce launches, 30 ms per 4 training iterations at 256^2).  Here the pass that writes grad_input also leaves one
 // partial sum per (plane, block): the bias gradient is then a [B, C, blocks] -> [C] sum over a few KB.  Fixed
-// association (per-lane serial, wave butterfly, 4 waves in order): bit-reproducible.
+// association (per-lane serial, wave butterfly, 4 waves in order: block_sum_ordered of block_sum.h, spelled out in the
+// plane loop): bit-reproducible.
 __global__ __launch_bounds__(256) void fba_bwd_bias_f32(float* __restrict__ gi, float* __restrict__ partial,
                                                         const float* __restrict__ g, const float* __restrict__ ref,
                                                         int planes, int step4, float alpha, float scale) {

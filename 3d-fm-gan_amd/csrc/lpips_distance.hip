@@ -16,8 +16,8 @@
 // for the whole block.  Channel sums are xor-butterflies inside the 16-lane group: every lane of the group ends with the
 // same bits.
 //
-// Forward sums: each lane adds its pixels' contributions in pixel order, then wave butterfly, then the four waves in
-// order -> partial[n, blockIdx.x].  No atomics: bit-reproducible; the caller sums each row and divides by HW.
+// Forward sums: each lane adds its pixels' contributions in pixel order, then block_sum_ordered (block_sum.h)
+// -> partial[n, blockIdx.x].  No atomics: bit-reproducible; the caller sums each row and divides by HW.
 //
 // 1/n_k is formed once per pixel (IEEE division) and multiplied in: one rounding more per element than the composite's
 // division.  Contraction is off in the kernels, products that should fuse say so (__builtin_fmaf): u0 - u1 is then an
@@ -25,7 +25,7 @@
 //
 // A pixel whose f_k is exactly zero: forward u_k = 0 (as the composite's 0 / eps); backward 0 * (0 / (0 * eps)) = NaN for
 // that pixel's grad_fk, which is what autograd's composite gives (sqrt backward).  No other pixel sees it.
-#include "common.h"
+#include "block_sum.h"
 
 namespace {
 
@@ -116,12 +116,8 @@ __global__ __launch_bounds__(LD_THREADS, LD_WAVES_PER_SIMD) void lpips_dist_fwd_
       acc += d;
     }
   }
-#pragma unroll
-  for (int m = FMGAN_WAVE / 2; m > 0; m >>= 1) acc += __shfl_xor(acc, m, FMGAN_WAVE);
-  if ((threadIdx.x & (FMGAN_WAVE - 1)) == 0) red[threadIdx.x / FMGAN_WAVE] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    partial[(long long)blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  const float sum = block_sum_ordered<4>(acc, red);
+  if (threadIdx.x == 0) partial[(long long)blockIdx.y * gridDim.x + blockIdx.x] = sum;
 }
 
 // G0 / G1: grad_f0 / grad_f1 is wanted (its pointer is not null).
@@ -224,11 +220,7 @@ extern "C" int fmgan_lpips_distance_blocks(int batch, int channels, int hw) {
   if (batch <= 0 || batch > 65535 || hw <= 0 || !ld_served(channels)) return 0;
   if ((long long)hw * channels >= (1LL << 30)) return 0;
   const int pix = ld_pixels_per_step(channels);
-  long long gx = ((long long)hw + pix - 1) / pix;                             // no block without work
-  const long long want = ((long long)FMGAN_NUM_CU * 8 + batch - 1) / batch;   // ~8 blocks per CU over the batch
-  if (gx > want) gx = want;
-  if (gx > LD_MAX_BLOCKS_X) gx = LD_MAX_BLOCKS_X;
-  return (int)(gx < 1 ? 1 : gx);
+  return fmgan_stage_blocks(((long long)hw + pix - 1) / pix, batch, LD_MAX_BLOCKS_X);
 }
 
 extern "C" int fmgan_lpips_distance_f32(const float* f0, const float* f1, const float* w, float* partial, int batch,

@@ -2,13 +2,7 @@
 // whole-network style bank (style_bank.hip): one definition of each summation chain, so the bank's bits equal the
 // per-layer launches' by construction.  Every function is called by all 64 lanes of a wave with wave-uniform arguments.
 #pragma once
-#include "common.h"
-
-__device__ __forceinline__ float wave_sum_xor(float acc) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  return acc;
-}
+#include "block_sum.h"
 
 // sum_k wn[k] * x[k] (COMOD: x[k] = xb[k] * pb[k], rounded to fp32 first, i.e. the elementwise product a caller would
 // have materialised): lane-strided fma chain, then the butterfly.  The bias is the caller's.

@@ -22,25 +22,12 @@
 // scalar loads and stores, the same arithmetic in the same order: the same bits), chosen per launch, never per lane.
 #include <climits>
 
-#include "common.h"
+#include "lpips_input.h"
 
 namespace {
 
 constexpr int PI_THREADS = 256;
-constexpr int PI_PIX = 4;          // output pixels of a unit
-
-// 0.5*(0.5*a + 0.5*b) + 0.5*(0.5*c + 0.5*d): columns inside a row first
-__device__ __forceinline__ float pi_quad(float a, float b, float c, float d) {
-#pragma clang fp contract(off)
-  const float t = 0.5f * a + 0.5f * b;
-  const float u = 0.5f * c + 0.5f * d;
-  return 0.5f * t + 0.5f * u;
-}
-
-__device__ __forceinline__ float pi_scaled(float v, float shift, float scale) {
-  const float u = v - shift;
-  return u / scale;
-}
+constexpr int PI_PIX = LPIPS_IN_PIX;      // output pixels of a unit
 
 template <int F, bool VEC>
 __global__ __launch_bounds__(PI_THREADS) void lpips_pair_input_f32(const float* __restrict__ img,
@@ -49,7 +36,7 @@ __global__ __launch_bounds__(PI_THREADS) void lpips_pair_input_f32(const float* 
                                                                    float* __restrict__ out0, float* __restrict__ out1,
                                                                    int h, int w, int y0, int x0, int oh, int ow,
                                                                    int units_x, int units, int gx) {
-  constexpr int O = F / 2 - (F > 1 ? 1 : 0);        // first tap inside an f x f cell
+  constexpr int O = lpips_in_first_tap(F);
   const int n = blockIdx.x / gx, blk = blockIdx.x % gx;
   const int u = blk * PI_THREADS + threadIdx.x;
   if (u >= units) return;
@@ -63,15 +50,13 @@ __global__ __launch_bounds__(PI_THREADS) void lpips_pair_input_f32(const float* 
     const float* r0 = src + c * hw;
     const float* r1 = r0 + w;                        // read at f > 1 only
     if constexpr (VEC && F == 1) {
-      const f32x4_u q = *reinterpret_cast<const f32x4_u*>(r0);
-      v[c][0] = q.x, v[c][1] = q.y, v[c][2] = q.z, v[c][3] = q.w;
+      lpips_in_load<PI_PIX>(r0, v[c]);
     } else if constexpr (VEC && F == 2) {
-      const f32x4_u a0 = *reinterpret_cast<const f32x4_u*>(r0), a1 = *reinterpret_cast<const f32x4_u*>(r0 + 4);
-      const f32x4_u b0 = *reinterpret_cast<const f32x4_u*>(r1), b1 = *reinterpret_cast<const f32x4_u*>(r1 + 4);
-      v[c][0] = pi_quad(a0.x, a0.y, b0.x, b0.y);
-      v[c][1] = pi_quad(a0.z, a0.w, b0.z, b0.w);
-      v[c][2] = pi_quad(a1.x, a1.y, b1.x, b1.y);
-      v[c][3] = pi_quad(a1.z, a1.w, b1.z, b1.w);
+      float a[F * PI_PIX], b[F * PI_PIX];
+      lpips_in_load<F * PI_PIX>(r0, a);
+      lpips_in_load<F * PI_PIX>(r1, b);
+#pragma unroll
+      for (int j = 0; j < PI_PIX; ++j) v[c][j] = lpips_in_quad(a[F * j], a[F * j + 1], b[F * j], b[F * j + 1]);
     } else if constexpr (VEC) {
       f32x2_u a[PI_PIX], b[PI_PIX];
 #pragma unroll
@@ -80,12 +65,12 @@ __global__ __launch_bounds__(PI_THREADS) void lpips_pair_input_f32(const float* 
         b[j] = *reinterpret_cast<const f32x2_u*>(r1 + F * j);
       }
 #pragma unroll
-      for (int j = 0; j < PI_PIX; ++j) v[c][j] = pi_quad(a[j].x, a[j].y, b[j].x, b[j].y);
+      for (int j = 0; j < PI_PIX; ++j) v[c][j] = lpips_in_quad(a[j].x, a[j].y, b[j].x, b[j].y);
     } else {
 #pragma unroll
       for (int j = 0; j < PI_PIX; ++j) {
         v[c][j] = 0.f;
-        if (ox + j < ow) v[c][j] = F == 1 ? r0[j] : pi_quad(r0[F * j], r0[F * j + 1], r1[F * j], r1[F * j + 1]);
+        if (ox + j < ow) v[c][j] = F == 1 ? r0[j] : lpips_in_quad(r0[F * j], r0[F * j + 1], r1[F * j], r1[F * j + 1]);
       }
     }
   }
@@ -94,13 +79,10 @@ __global__ __launch_bounds__(PI_THREADS) void lpips_pair_input_f32(const float* 
 #pragma unroll
   for (int j = 0; j < PI_PIX; ++j)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) o[3 * j + c] = pi_scaled(v[c][j], sh[c], sc[c]);
+    for (int c = 0; c < 3; ++c) o[3 * j + c] = lpips_in_scaled(v[c][j], sh[c], sc[c]);
   if constexpr (VEC) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const f32x4_u s = {o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
-      *reinterpret_cast<f32x4_u*>(dst + 4 * q) = s;
-    }
+    for (int q = 0; q < 3; ++q) lpips_in_store4(dst + 4 * q, o + 4 * q);
   } else {
 #pragma unroll
     for (int j = 0; j < PI_PIX; ++j)

@@ -7,8 +7,8 @@
 //   backward  grad_x = (k * (x - t)) * mask + 1[-1 <= x <= 1] * w_f(h, w) * (g_y[b, h/f, w/f, c] / scale[c])
 //
 // bilinear_f is F.interpolate(size=256, mode='bilinear', align_corners=False) at the integer ratio f: the identity at
-// f = 1, and at f = 2 / 4 the mean of the 2x2 pixels at rows and columns f*i + f/2 - 1 and + 1 (both weights 1/2), in the
-// association of fmgan_lpips_pair_input_f32: 0.5*(0.5*a + 0.5*b) + 0.5*(0.5*c + 0.5*d), no fused multiply-add.  Hence
+// f = 1, and at f = 2 / 4 the mean of the 2x2 pixels at rows and columns f*i + f/2 - 1 and + 1 (both weights 1/2), built
+// from lpips_in_half (lpips_input.h, shared with the PPL input stage): 0.5*(0.5*a + 0.5*b) + 0.5*(0.5*c + 0.5*d).  Hence
 // w_f = 1 at f = 1, 1/4 at f = 2, and at f = 4 1/4 on rows and columns 4i+1, 4i+2 and 0 elsewhere: every source pixel
 // feeds at most one reduced pixel, and the backward is a gather.
 //
@@ -22,19 +22,20 @@
 // 12 floats of y / g_y are 48 contiguous bytes (three 16-byte accesses).  Lanes of a wave own consecutive units of a
 // row, so a wave covers one contiguous run of every source row it reads and of y.  grid.x = B * 128 blocks of 128
 // threads, one unit per lane, no grid-stride loop.  All vector accesses need dword alignment only (f32x4_u).
-// Forward sum: per-lane serial (explicit fma) over rows, planes, columns in that order, wave butterfly, the two waves
-// in order -> partial[blockIdx.x] (the form of fba_bwd_bias_f32); bit-reproducible run to run.
+// Forward sum: per-lane serial (explicit fma) over rows, planes, columns in that order, then block_sum_ordered
+// (block_sum.h) over the two waves -> partial[blockIdx.x]; bit-reproducible run to run.
 // A NaN in x or target reaches the sum and its own grad_x element also where mask is 0 (NaN * 0 = NaN), as in the
 // reference's weighted_mse_loss, which multiplies too.
 #include <climits>
 
-#include "common.h"
+#include "block_sum.h"
+#include "lpips_input.h"
 
 namespace {
 
 constexpr int PL_THREADS = 128;
 constexpr int PL_OUT = 256;                                  // the size LPIPS is evaluated at
-constexpr int PL_PIX = 4;                                    // reduced pixels of a unit
+constexpr int PL_PIX = LPIPS_IN_PIX;                         // reduced pixels of a unit
 constexpr int PL_UNITS_X = PL_OUT / PL_PIX;
 constexpr int PL_BLOCKS = PL_OUT * PL_UNITS_X / PL_THREADS;  // blocks per sample
 constexpr int PL_MAX_BATCH = 0x7fffffff / PL_BLOCKS;         // grid.x and the partial count stay below 2^31
@@ -49,15 +50,6 @@ template <int F>
 __device__ __forceinline__ constexpr bool pl_tap(int r, int j) {
   if (F < 4) return true;
   return (r == 1 || r == 2) && (j % 4 == 1 || j % 4 == 2);
-}
-
-template <int W>
-__device__ __forceinline__ void pl_load(const float* __restrict__ p, float (&v)[W]) {
-#pragma unroll
-  for (int q = 0; q < W / 4; ++q) {
-    const f32x4_u a = *reinterpret_cast<const f32x4_u*>(p + 4 * q);
-    v[4 * q] = a.x, v[4 * q + 1] = a.y, v[4 * q + 2] = a.z, v[4 * q + 3] = a.w;
-  }
 }
 
 struct PlUnit {
@@ -79,7 +71,7 @@ __global__ __launch_bounds__(PL_THREADS) void projection_loss_fwd_f32(const floa
                                                                       float* __restrict__ y) {
 #pragma clang fp contract(off)
   constexpr int S = PL_OUT * F, W = PL_PIX * F;
-  constexpr int R0 = F / 2 - (F > 1 ? 1 : 0);                // first tap row (and column) inside an f x f cell
+  constexpr int R0 = lpips_in_first_tap(F);
   __shared__ float red[PL_THREADS / FMGAN_WAVE];
   const PlUnit un = pl_unit();
   const long long hw = (long long)S * S;
@@ -91,12 +83,12 @@ __global__ __launch_bounds__(PL_THREADS) void projection_loss_fwd_f32(const floa
 #pragma unroll
   for (int r = 0; r < F; ++r) {
     float m[W];
-    if (mask) pl_load<W>(mask + win + r * S, m);
+    if (mask) lpips_in_load<W>(mask + win + r * S, m);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       float xv[W], tv[W];
-      pl_load<W>(xs + c * hw + r * S, xv);
-      pl_load<W>(ts + c * hw + r * S, tv);
+      lpips_in_load<W>(xs + c * hw + r * S, xv);
+      lpips_in_load<W>(ts + c * hw + r * S, tv);
 #pragma unroll
       for (int j = 0; j < W; ++j) {
         const float d = xv[j] - tv[j];
@@ -108,6 +100,7 @@ __global__ __launch_bounds__(PL_THREADS) void projection_loss_fwd_f32(const floa
       } else if (r == R0 || r == R0 + 1) {
 #pragma unroll
         for (int j = 0; j < PL_PIX; ++j)
+          // lpips_in_half, spelled out: each clamp stays next to its product
           row[r - R0][c][j] = 0.5f * pl_clamp(xv[F * j + R0]) + 0.5f * pl_clamp(xv[F * j + R0 + 1]);
       }
     }
@@ -119,22 +112,16 @@ __global__ __launch_bounds__(PL_THREADS) void projection_loss_fwd_f32(const floa
       const float sh = shift[c], sc = scale[c];
 #pragma unroll
       for (int j = 0; j < PL_PIX; ++j) {
-        const float v = F == 1 ? row[0][c][j] : 0.5f * row[0][c][j] + 0.5f * row[1][c][j];
-        const float u = v - sh;
-        o[3 * j + c] = u / sc;
+        const float v = F == 1 ? row[0][c][j] : lpips_in_half(row[0][c][j], row[1][c][j]);
+        o[3 * j + c] = lpips_in_scaled(v, sh, sc);
       }
     }
     float* dst = y + (((long long)un.n * PL_OUT + un.oy) * PL_OUT + un.ox) * 3;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const f32x4_u s = {o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
-      *reinterpret_cast<f32x4_u*>(dst + 4 * q) = s;
-    }
+    for (int q = 0; q < 3; ++q) lpips_in_store4(dst + 4 * q, o + 4 * q);
   }
-  for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s, FMGAN_WAVE);
-  if ((threadIdx.x & (FMGAN_WAVE - 1)) == 0) red[threadIdx.x / FMGAN_WAVE] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1];
+  const float sum = block_sum_ordered<2>(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 template <int F>
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(PL_THREADS) void projection_loss_bwd_f32(const floa
   float term[3][PL_PIX];                                     // w_f * (g_y / scale) of the unit's reduced pixels
   if (g_y) {
     float o[3 * PL_PIX];
-    pl_load<3 * PL_PIX>(g_y + (((long long)un.n * PL_OUT + un.oy) * PL_OUT + un.ox) * 3, o);
+    lpips_in_load<3 * PL_PIX>(g_y + (((long long)un.n * PL_OUT + un.oy) * PL_OUT + un.ox) * 3, o);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float sc = scale[c];
@@ -169,12 +156,12 @@ __global__ __launch_bounds__(PL_THREADS) void projection_loss_bwd_f32(const floa
 #pragma unroll
   for (int r = 0; r < F; ++r) {
     float m[W];
-    if (mask) pl_load<W>(mask + win + r * S, m);
+    if (mask) lpips_in_load<W>(mask + win + r * S, m);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       float xv[W], tv[W];
-      pl_load<W>(x + base + c * hw + r * S, xv);
-      pl_load<W>(target + base + c * hw + r * S, tv);
+      lpips_in_load<W>(x + base + c * hw + r * S, xv);
+      lpips_in_load<W>(target + base + c * hw + r * S, tv);
       float* dst = grad_x + base + c * hw + r * S;
 #pragma unroll
       for (int q = 0; q < W / 4; ++q) {

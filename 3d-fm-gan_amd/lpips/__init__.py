@@ -111,17 +111,7 @@ class PNetLin(nn.Module):
         # in the last bit at every tap), so the distance of an image to itself is exactly 0 only if its features are
         # computed once.
         f0 = self.net(s0)
-        f1 = f0 if s1 is s0 else self.net(s1)
-        val = None
-        for i in range(len(self.chns)):
-            lin = getattr(self, f'lin{i}').model
-            if FUSED and not self.training and lpips_distance_serves(f0[i], f1[i], lin[-1].weight):
-                r = lpips_distance(f0[i], f1[i], lin[-1].weight)
-            else:
-                diff = (normalize_tensor(f0[i]) - normalize_tensor(f1[i])) ** 2
-                r = lin(diff).mean([2, 3], keepdim=True)
-            val = r if val is None else val + r
-        return val
+        return self._tap_sum(f0, f0 if s1 is s0 else self.net(s1))
 
     def features_scaled(self, s):
         """The five trunk taps of an input that already went through the ScalingLayer: what forward_scaled computes for
@@ -130,7 +120,11 @@ class PNetLin(nn.Module):
 
     def forward_features(self, f0, s1):
         """forward_scaled(s0, s1) with the trunk pass over s0 already done: f0 = features_scaled(s0)."""
-        f1 = self.net(s1)
+        return self._tap_sum(f0, self.net(s1))
+
+    def _tap_sum(self, f0, f1):
+        """The distance from the two lists of trunk taps: per tap the kernel where it serves, else the composite; the
+        taps added in order."""
         val = None
         for i in range(len(self.chns)):
             lin = getattr(self, f'lin{i}').model
@@ -141,6 +135,14 @@ class PNetLin(nn.Module):
                 r = lin(diff).mean([2, 3], keepdim=True)
             val = r if val is None else val + r
         return val
+
+
+def scaling_layer_of(percept, method):
+    """percept's ScalingLayer when a caller may scale the inputs itself and hand them to `method` (forward_scaled,
+    forward_cached): percept is an eval-mode module that offers it.  None otherwise."""
+    if not isinstance(percept, nn.Module) or percept.training or not hasattr(percept, method):
+        return None
+    return getattr(getattr(percept, 'net', None), 'scaling_layer', None)
 
 
 class PerceptualLoss(nn.Module):

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('FMGAN_LIB') or os.path.join(os.path.dirname(_HERE), '
 
 F32, F64, F16 = 0, 1, 2
 FMGAN_OK, FMGAN_EUNSUPPORTED = 0, -2      # include/fmgan_hip.h, status codes
+LPIPS_SIZE = 256                          # the size LPIPS is evaluated at (TARGET of op.ppl_input, op.projection_loss)
 _DTYPES = {torch.float32: F32, torch.float64: F64, torch.float16: F16}
 
 _lib = None
@@ -167,6 +168,24 @@ def fp(t):
         raise RuntimeError(f'libfmgan_hip f32 entry point got a {t.dtype} tensor on {t.device}: float32 GPU tensors only '
                            f'(cast before the call; under autocast the package\'s autograd Functions do)')
     return t.data_ptr()
+
+
+def require_f32_gpu(what, named, contiguous=True, same_device=True):
+    """The device and dtype checks of the stage wrappers, made after their own shape test: every tensor of `named`
+    ((tensor or None, name) pairs) is a float32 GPU tensor (RuntimeError from require_gpu / fp(), no fallback), and,
+    unless switched off, contiguous and on the device of the first one."""
+    first = None
+    for t, name in named:
+        if t is None:
+            continue
+        require_gpu(t, name)
+        fp(t)
+        if contiguous and not t.is_contiguous():
+            raise RuntimeError(f'{what}: {name} must be contiguous, got strides {t.stride()}')
+        if first is None:
+            first = (t.device, name)
+        elif same_device and t.device != first[0]:
+            raise RuntimeError(f'{what}: {name} must be on {first[1]}\'s device')
 
 
 class on_device:
@@ -400,10 +419,7 @@ def _face_region_shape(r, g):
         got = f'render {tuple(r.shape)}' + ('' if g is None else f' and image {tuple(g.shape)}')
         raise ValueError(f'face_region: {got}: expected [N, C, H, W] tensors of one shape (the face-regional loss '
                          f'compares the render with the generated image pixel by pixel; renders are not resampled)')
-    for t, name in ((r, 'render'), (g, 'image')):
-        if t is not None:
-            require_gpu(t, name)
-            fp(t)
+    require_f32_gpu('face_region', ((r, 'render'), (g, 'image')), contiguous=False, same_device=False)
     r = r.contiguous()
     g = g.contiguous() if g is not None else None
     b, c, h, w = r.shape
@@ -465,12 +481,7 @@ def face_input(a, b=None, want_gray_b=False, want_l1=False, face_size=128):
         raise ValueError(f'face_input: {got}: expected [N, 3, H, W] tensors of one shape')
     if b is None and (want_gray_b or want_l1):
         raise ValueError('face_input: gray_b / l1 asked for without a second image')
-    for t, name in ((a, 'a'), (b, 'b')):
-        if t is not None:
-            require_gpu(t, name)
-            fp(t)
-            if not t.is_contiguous():
-                raise RuntimeError(f'face_input: {name} must be contiguous, got strides {t.stride()}')
+    require_f32_gpu('face_input', ((a, 'a'), (b, 'b')))
     n, _, h, w = a.shape
     k = face_input_pool(w, face_size)
     if n == 0:
@@ -500,13 +511,8 @@ def lpips_pair_input(image, shift, scale, window, f):
     if image.ndim != 4 or image.shape[1] != 3 or image.shape[0] % 2 != 0 or shift.numel() != 3 or scale.numel() != 3:
         raise ValueError(f'lpips_pair_input: image {tuple(image.shape)}, shift {tuple(shift.shape)}, scale '
                          f'{tuple(scale.shape)}: expected [2P, 3, H, W] and three floats each')
-    require_gpu(image, 'image')
     shift, scale = shift.contiguous(), scale.contiguous()
-    pi, ps, pc = fp(image), fp(shift), fp(scale)
-    if not image.is_contiguous():
-        raise RuntimeError(f'lpips_pair_input: image must be contiguous, got strides {image.stride()}')
-    if shift.device != image.device or scale.device != image.device:
-        raise RuntimeError('lpips_pair_input: shift and scale must be on the image\'s device')
+    require_f32_gpu('lpips_pair_input', ((image, 'image'), (shift, 'shift'), (scale, 'scale')))
     n, _, h, w = image.shape
     y0, x0, hc, wc = (int(v) for v in window)
     f = int(f)
@@ -515,7 +521,8 @@ def lpips_pair_input(image, shift, scale, window, f):
     with launching(image, 'lpips_pair_input', (n // 2, h, w, y0, x0, hc, wc, f)) as stream:
         out0 = _nhwc_empty(n // 2, 3, max(hc // f, 0), max(wc // f, 0), image.device)
         out1 = torch.empty_like(out0)
-        st = lib().fmgan_lpips_pair_input_f32(pi, ps, pc, fp(out0), fp(out1), n // 2, h, w, y0, x0, hc, wc, f, stream)
+        st = lib().fmgan_lpips_pair_input_f32(fp(image), fp(shift), fp(scale), fp(out0), fp(out1), n // 2, h, w, y0, x0,
+                                              hc, wc, f, stream)
     return (out0, out1) if served(st, 'lpips_pair_input') else None
 
 
@@ -527,16 +534,10 @@ def _projection_loss_args(x, target, mask, vectors):
         raise ValueError(f'projection_loss: x {tuple(x.shape)}, target {tuple(target.shape)}, mask '
                          f'{None if mask is None else tuple(mask.shape)}: expected two [B, 3, S, S] tensors, an [S, S] '
                          f'mask or none, and three floats each of shift / scale')
-    require_gpu(x, 'x')
-    for t, name in ((x, 'x'), (target, 'target'), (mask, 'mask')) + tuple((v, 'shift / scale') for v in vectors):
-        if t is not None:
-            fp(t)
-            if not t.is_contiguous():
-                raise RuntimeError(f'projection_loss: {name} must be contiguous, got strides {t.stride()}')
-            if t.device != x.device:
-                raise RuntimeError(f'projection_loss: {name} must be on x\'s device')
+    require_f32_gpu('projection_loss', ((x, 'x'), (target, 'target'), (mask, 'mask')) +
+                    tuple((v, 'shift / scale') for v in vectors))
     b, _, h, w = x.shape
-    return b, h, w, max(h // 256, 1)
+    return b, h, w, max(h // LPIPS_SIZE, 1)
 
 
 def projection_loss_fwd(x, target, mask, shift, scale, want_y=True):
@@ -552,7 +553,7 @@ def projection_loss_fwd(x, target, mask, shift, scale, want_y=True):
         return None
     with launching(x, 'projection_loss', (b, h, f, mask is not None, bool(want_y), 0)) as stream:
         partial = torch.empty((blocks,), dtype=torch.float32, device=x.device)
-        y = _nhwc_empty(b, 3, 256, 256, x.device) if want_y else None
+        y = _nhwc_empty(b, 3, LPIPS_SIZE, LPIPS_SIZE, x.device) if want_y else None
         st = lib().fmgan_projection_loss_fwd_f32(fp(x), fp(target), fp(mask), fp(shift), fp(scale), fp(partial), fp(y),
                                                  b, h, w, f, stream)
     return (partial, y) if served(st, 'projection_loss_fwd') else None
@@ -567,9 +568,9 @@ def projection_loss_bwd(x, target, mask, g_y, k, scale):
     if k.numel() != 1 or k.device != x.device:
         raise ValueError(f'projection_loss_bwd: k must hold one element on x\'s device, got {tuple(k.shape)} on {k.device}')
     if g_y is not None:
-        if tuple(g_y.shape) != (b, 3, 256, 256) or not nhwc_dense(g_y) or g_y.device != x.device:
+        if tuple(g_y.shape) != (b, 3, LPIPS_SIZE, LPIPS_SIZE) or not nhwc_dense(g_y) or g_y.device != x.device:
             raise ValueError(f'projection_loss_bwd: g_y {tuple(g_y.shape)} with strides {g_y.stride()}: expected '
-                             f'[{b}, 3, 256, 256] in channels_last storage on x\'s device')
+                             f'[{b}, 3, {LPIPS_SIZE}, {LPIPS_SIZE}] in channels_last storage on x\'s device')
     pk, pg = fp(k), fp(g_y)
     if b == 0 or lib().fmgan_projection_loss_select(b, h, w, f) <= 0:
         return None

@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from . import _native
 
-TARGET = 256        # the size LPIPS is evaluated at
+TARGET = _native.LPIPS_SIZE
 
 
 def _refuse_grad(image):

@@ -27,7 +27,7 @@ from torch.autograd.function import once_differentiable
 from . import _native
 from ._native import amp_fwd as _amp_fwd, amp_bwd as _amp_bwd
 
-TARGET = 256        # the size LPIPS is evaluated at
+TARGET = _native.LPIPS_SIZE
 SIZES = (256, 512, 1024)
 
 

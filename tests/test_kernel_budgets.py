@@ -1,45 +1,18 @@
 """Register / spill budgets of the kernels the measured occupancies rely on, read from the code objects inside the built
-library (llvm-objdump --offloading + llvm-readelf --notes: no GPU, no recompilation).
+library (tests/codeobj.py: llvm-objdump --offloading + llvm-readelf --notes, no GPU, no recompilation).
 
 DESIGN §3.1 / §3.3 quote blocks per CU per tile (2 / 3 / 4 for the 128- / 64- / 32-channel modulated-conv tiles, 16 waves per
 CU for the DMA-ring blur); those follow from `512 / vgpr_count` waves per SIMD.  A compiler or source change that pushes a
 kernel over its budget, or makes it spill, silently costs a block per CU — this test makes it loud.
 """
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, '3d-fm-gan_amd', 'csrc', 'libfmgan_hip.so')
-LLVM = '/opt/rocm/lib/llvm/bin'
+import codeobj
 
 
 @pytest.fixture(scope='module')
 def kernels(tmp_path_factory):
-    objdump, readelf = os.path.join(LLVM, 'llvm-objdump'), os.path.join(LLVM, 'llvm-readelf')
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip('llvm-objdump / llvm-readelf not found')
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    d = tmp_path_factory.mktemp('codeobj')
-    shutil.copy(LIB, d / 'lib.so')
-    subprocess.run([objdump, '--offloading', str(d / 'lib.so')], check=True, capture_output=True, cwd=d)
-    out = {}
-    for f in sorted(os.listdir(d)):
-        if not f.endswith('gfx950'):
-            continue
-        notes = subprocess.run([readelf, '--notes', str(d / f)], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split('- .agpr_count')[1:]:
-            name = re.search(r'\.name:\s+(\S+)', blk).group(1)
-
-            def num(key):
-                return int(re.search(key + r':\s+(\d+)', blk).group(1))
-            out[name] = {'vgpr': num(r'\.vgpr_count'), 'vgpr_spill': num(r'\.vgpr_spill_count'),
-                         'scratch': num(r'\.private_segment_fixed_size'), 'lds': num(r'\.group_segment_fixed_size')}
+    out = codeobj.kernel_notes(tmp_path_factory.mktemp('codeobj'))
     assert len(out) > 80, f'only {len(out)} kernels found in the library'
     return out
 
