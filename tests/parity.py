@@ -19,11 +19,24 @@ def ref_errors(a, ref32, ref64):
     return e_hip, e_ref
 
 
+def within_reference(e_hip, e_ref, floor=2e-6, margin=4.0):
+    """The rule itself on the two figures of ref_errors, for a test that collects failures before it asserts."""
+    return e_hip <= margin * e_ref + floor
+
+
 def no_farther_than_reference(a, ref32, ref64, floor=2e-6, margin=4.0):
     """|HIP - fp64| <= margin * |reference fp32 - fp64| + floor * max|fp64|: the HIP(+MIOpen) result is as close to the
     exact value as the reference's own fp32 result (fixtures: tools/make_golden.py gen_fp64)."""
     e_hip, e_ref = ref_errors(a, ref32, ref64)
-    assert e_hip <= margin * e_ref + floor, (e_hip, e_ref)
+    assert within_reference(e_hip, e_ref, floor, margin), (e_hip, e_ref)
+
+
+def closer_to_fp64(tag, a, ref32, ref64, ref_name='reference32'):
+    """Prints both errors of ref_errors as `{tag}: |HIP-fp64| ...  |{ref_name}-fp64| ...` (the PARITY / GLUE lines of the
+    logs), then holds `a` to no_farther_than_reference with its defaults."""
+    e_hip, e_ref = ref_errors(a, ref32, ref64)
+    print(f'{tag}: |HIP-fp64| {e_hip:.3e}  |{ref_name}-fp64| {e_ref:.3e}', flush=True)
+    no_farther_than_reference(a, ref32, ref64)
 
 
 def crop(t, y0, x0, h, w):

@@ -11,13 +11,9 @@ import torch.nn.functional as F
 
 import cases
 import synth
+from nets import lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _lib():
-    from op import _native
-    return _native.lib()
 
 
 def test_library_exports_header_symbols():
@@ -25,7 +21,7 @@ def test_library_exports_header_symbols():
     hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
     names = sorted(set(re.findall(r'\b(fmgan_\w+)\s*\(', hdr)))
     assert len(names) >= 11
-    L = _lib()
+    L = lib()
     for n in names:
         assert hasattr(L, n), f'{n} declared in include/fmgan_hip.h but not exported'
     assert L.fmgan_abi_version() == 1
@@ -61,7 +57,7 @@ def test_signature_table_matches_header():
 
     decls = re.findall(r'([\w \t*]+?)\b(fmgan_\w+)\s*\(([^()]*)\)\s*;', hdr)
     assert len(decls) == len(re.findall(r'\bfmgan_\w+\s*\(', hdr)) == len({name for _, name, _ in decls})
-    L = _lib()
+    L = lib()
     for ret, name, params in decls:
         fn = getattr(L, name)
         assert fn.argtypes is not None, f'{name} is declared in the header but lib() gives it no signature'
@@ -88,7 +84,7 @@ def test_out_size_matches_reference_formula():
 
 
 def test_path_selection_is_host_logic():
-    L = _lib()
+    L = lib()
     # headline blur [256,1025,1025] -> row-march; 9x9 plane -> not row-march; f64 -> generic; bad args -> EINVAL
     assert L.fmgan_upfirdn2d_select(0, 256, 1025, 1025, 1, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1) == 1
     assert L.fmgan_upfirdn2d_select(0, 1024, 9, 9, 1, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1) != 1
@@ -98,7 +94,7 @@ def test_path_selection_is_host_logic():
 
 
 def test_invalid_arguments_return_status_without_gpu():
-    L = _lib()
+    L = lib()
     # null pointers / bad dims are rejected before any HIP call
     assert L.fmgan_upfirdn2d(0, None, None, None, 1, 8, 8, 1, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1, -1, None) == -1
     assert L.fmgan_upfirdn2d(0, None, None, None, 1, 8, 8, 1, 4, 4, 0, 1, 1, 1, 1, 1, 1, 1, -1, None) == -1
@@ -116,7 +112,7 @@ def test_invalid_arguments_return_status_without_gpu():
 
 def test_prelu_backward_host_logic():
     """fmgan_prelu_backward_blocks / _f32: partial-sum rows per launch and argument checks, all before any HIP call."""
-    L = _lib()
+    L = lib()
     assert L.fmgan_prelu_backward_blocks(0, 64) == 0 and L.fmgan_prelu_backward_blocks(10, 0) == 0
     for rows, c in ((1, 64), (1 << 20, 64), (1 << 20, 512), (300, 96), (7, 2048)):
         b = L.fmgan_prelu_backward_blocks(rows, c)
@@ -133,7 +129,7 @@ def test_prelu_backward_host_logic():
 def test_fused_bias_act_backward_host_logic():
     """fmgan_fused_bias_act_bwd_blocks / _f32: which planes the one-pass backward serves, partial columns per plane,
     argument checks — all before any HIP call."""
-    L = _lib()
+    L = lib()
     for planes, hw, want in ((0, 64, 0), (8, 16, 0), (8, 63, 0), (8, 66, 0), (8, 64, 1), (8, 4096, 1), (8, 4100, 2),
                              (256, 1024 * 1024, 64), (1 << 31, 64, 0)):
         assert L.fmgan_fused_bias_act_bwd_blocks(planes, hw) == want, (planes, hw)
@@ -145,7 +141,7 @@ def test_fused_bias_act_backward_host_logic():
 
 
 def test_torgb_backward_host_logic():
-    L = _lib()
+    L = lib()
     assert L.fmgan_torgb_backward_splits(8, 32, 1024 * 1024) >= 64          # enough blocks to fill the chip
     assert L.fmgan_torgb_backward_splits(2, 512, 16) == 1
     assert L.fmgan_torgb_backward_splits(2, 512, 18) == 0                   # H*W % 4 != 0: composite instead
@@ -307,7 +303,7 @@ def test_modconv_index_range_guards_refuse_without_launching():
     """Shapes just OUTSIDE each index-range guard of fmgan_modconv2d_f32 / fmgan_modconv_wgrad_f32 return
     FMGAN_EOVERFLOW before anything is launched (the pointers here are fake).  The same guards from the inside —
     shapes just below them must compute correctly — are GPU tests (tests/test_hip_modconv.py::test_guard_boundary_*)."""
-    L = _lib()
+    L = lib()
     fake = ctypes.c_void_p(0x1000)
     EOVER, EINVAL = -4, -1
 
@@ -410,7 +406,7 @@ def test_fused_blur_selection_declines_firs_wider_than_four_taps():
     small planes, row-march / LDS-DMA ring for wide ones); a 5-tap FIR such as [1,4,6,4,1] has none, which is the case in
     which _native.blur_noise_bias_act returns None and StyledConv takes the two-pass form (and no placement workspace)."""
     from op import _native
-    L = _lib()
+    L = lib()
     for b, c, h in ((8, 512, 17), (8, 256, 129), (8, 32, 1025)):
         _, off, ps, rs = _native.aligned_rows_shape(b, c, h, h, 1)
         assert L.fmgan_blur_noise_bias_act_select(None, None, None, b, c, h, h, ps, rs, 4, 4, 1, 1, 1, 1) in (1, 2, 5)
@@ -423,7 +419,7 @@ def test_fused_blur_selection_declines_firs_wider_than_four_taps():
 def test_upfirdn2d_selects_return_the_launch_status():
     """Both select functions are the launch's own plan with the launch left out: arguments the launch refuses get the
     launch's status, not a kernel id.  Every call here is refused before any HIP call (the pointers are placeholders)."""
-    L = _lib()
+    L = lib()
     fake = ctypes.c_void_p(0x1000)
     EINVAL, EOVER = -1, -4
 
@@ -460,7 +456,7 @@ def test_upfirdn2d_kernel_case_tables_reach_their_kernels():
     the plan assumes 256 CUs, the count the two scaled rows were written for.)"""
     import ufd_cases
     from op import _native
-    L = _lib()
+    L = lib()
     assert len(set(ufd_cases.ALL_ROWS)) == len(ufd_cases.ALL_ROWS) == len(ufd_cases.OUT_SIZE)
     assert ufd_cases.rowmarch_tall_major(256) == ufd_cases.ROWMARCH_TALL[1]
     assert ufd_cases.up2_trip_major(256) == ufd_cases.UP2_TRIP[1]
@@ -481,7 +477,7 @@ def test_bf16_launches_ask_supported():
     """fmgan_modconv2d_bf16(_x3)_supported is the one statement of which shapes the bf16 contractions serve, and the
     launch asks it: for every refused shape, and for mode 2 on the split-operand entry, `_supported` is 0 and the launch
     (placeholder pointers, nothing reaches HIP) returns FMGAN_EUNSUPPORTED."""
-    L = _lib()
+    L = lib()
     fake = ctypes.c_void_p(0x1000)
     refused = ((2, 12, 32, 64, 64, 0), (2, 32, 48, 64, 64, 0), (2, 32, 32, 16, 16, 0), (2, 512, 512, 4, 4, 1),
                (1, 32, 32, 40, 40, 2))
@@ -499,7 +495,7 @@ def test_modconv_select_and_tiles_are_host_logic():
     table lists one tile per (mode, cfg, letter) with the channel extent of its class, and the split reported is the one
     fmgan_modconv2d_workspace_bytes sizes the workspace for."""
     from op import _native
-    L = _lib()
+    L = lib()
     tiles = _native.modconv2d_tiles()
     assert L.fmgan_modconv2d_tiles(None, 0) == len(tiles) == 16
     assert len({t[:3] for t in tiles}) == len(tiles)

@@ -19,14 +19,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import launches
 import synth
-from parity import ref_errors
+from gpumem import dev
+from parity import closer_to_fp64
 
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device('cuda', 0)
 
 
 def _cl(t):
@@ -36,9 +34,7 @@ def _cl(t):
 def _gate(tag, got, ref32, ref64):
     a, r32, r64 = (t.detach().cpu().numpy() for t in (got, ref32, ref64))
     assert a.shape == r64.shape, (tag, a.shape, r64.shape)
-    e_hip, e_ref = ref_errors(a, r32, r64)
-    print(f'GLUE {tag}: |HIP-fp64| {e_hip:.3e}  |aten32-fp64| {e_ref:.3e}', flush=True)
-    assert e_hip <= 4.0 * e_ref + 2e-6, f'{tag}: |HIP - fp64| = {e_hip:.3e} > 4 x {e_ref:.3e} + 2e-6'
+    closer_to_fp64(f'GLUE {tag}', a, r32, r64, ref_name='aten32')
 
 
 def _bn_vectors(name, c):
@@ -266,33 +262,21 @@ def test_body_fused_vs_modules_vs_fp64():
 def test_whole_encoder_fused_vs_switched_off():
     """B = 1 at 256^2, one head per pyramid level and more: fused (the default) against ENCODER_FUSE = False within
     5e-6 max|out|, the tolerance of the encoder goldens (MIOpen's own run-to-run spread is 3.9e-7)."""
-    from op import _native
     from psp_encoder_model.encoders import helpers
     enc = _encoder(8).to(dev())
     x = synth.tensor('glue/enc/x', (1, 3, 256, 256), dist='uniform').to(dev())
     assert helpers.ENCODER_FUSE, 'the fused path is the default'
-    seen = []
-
-    class Names:
-        def begin(self, name, info):
-            seen.append(name)
-
-        def end(self, tok):
-            pass
-
-    with torch.no_grad():
-        _native.set_observer(Names())
+    with torch.no_grad(), launches.observed() as rec:
         try:
             a = enc(x)
-            fused_names = [n for n in seen if n in ('bn_prelu', 'se_pool', 'se_gate', 'ir_tail')]
-            del seen[:]
+            fused_names = [n for n in rec.names if n in ('bn_prelu', 'se_pool', 'se_gate', 'ir_tail')]
+            del rec.seen[:]
             helpers.ENCODER_FUSE = False
             b = enc(x)
         finally:
             helpers.ENCODER_FUSE = True
-            _native.set_observer(None)
     assert fused_names == ['bn_prelu'] + ['se_pool', 'se_gate', 'ir_tail'] * 8, fused_names
-    assert not [n for n in seen if n in ('bn_prelu', 'se_pool', 'se_gate', 'ir_tail')]
+    assert not [n for n in rec.names if n in ('bn_prelu', 'se_pool', 'se_gate', 'ir_tail')]
     d, m = float((a - b).abs().max()), float(b.abs().max())
     print(f'GLUE encoder fused vs modules: max|diff| {d:.3e} = {d / m:.3e} of max|out| {m:.3e}', flush=True)
     assert d <= 5e-6 * m

@@ -6,15 +6,9 @@ import pytest
 import torch
 
 import synth
+from gpumem import dev, guarded, guards_intact, misaligned
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64          # guard floats on each side of an output buffer
-SENTINEL = 12345.5
-
-
-def dev():
-    return torch.device('cuda', 0)
 
 
 def emulate_gray(x, k):
@@ -31,18 +25,6 @@ def emulate_gray(x, k):
     return (acc * np.float32(1.0 / (k * k)))[:, None]
 
 
-def _guarded(shape):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * GUARD,), float('nan'), dtype=torch.float32, device=dev())
-    buf[:GUARD] = SENTINEL
-    buf[GUARD + n:] = SENTINEL
-    return buf, buf[GUARD:GUARD + n].view(shape)
-
-
-def _guards_intact(buf):
-    return bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[-GUARD:] == SENTINEL).all())
-
-
 def launch(a, b, k, want_gray_a=True, want_gray_b=False, want_l1=False):
     """fmgan_face_input_f32 into guarded buffers pre-filled with NaN: (gray_a, gray_b, l1 per sample), after checking
     that no guard word changed and every requested element was written."""
@@ -53,30 +35,21 @@ def launch(a, b, k, want_gray_a=True, want_gray_b=False, want_l1=False):
     assert blocks > 0
     bufs = {}
     if want_gray_a:
-        bufs['ga'] = _guarded((n, 1, h // k, w // k))
+        bufs['ga'] = guarded((n, 1, h // k, w // k))
     if want_gray_b:
-        bufs['gb'] = _guarded((n, 1, h // k, w // k))
+        bufs['gb'] = guarded((n, 1, h // k, w // k))
     if want_l1:
-        bufs['l1'] = _guarded((n, blocks))
+        bufs['l1'] = guarded((n, blocks))
     p = {key: v[1].data_ptr() for key, v in bufs.items()}
     st = L.fmgan_face_input_f32(_native.fp(a), _native.fp(b), p.get('ga'), p.get('gb'), p.get('l1'), n, h, w, k,
                                 torch.cuda.current_stream().cuda_stream)
     assert st == 0, st
     torch.cuda.synchronize()
     for key, (buf, view) in bufs.items():
-        assert _guards_intact(buf), key
+        assert guards_intact(buf), key
     out = {key: v[1] for key, v in bufs.items()}
     l1 = out['l1'].sum(1) / (3 * h * w) if want_l1 else None
     return out.get('ga'), out.get('gb'), l1
-
-
-def _misaligned(t):
-    """The same values in a view that starts one float into its storage (contiguous, 4 bytes off a 16-byte boundary)."""
-    store = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    view = store[1:].view(t.shape)
-    view.copy_(t)
-    assert view.is_contiguous() and view.data_ptr() % 16 == 4
-    return view
 
 
 def _pair(tag, shape):
@@ -101,7 +74,7 @@ def test_gray_and_l1_against_emulation(shape, k, misalign):
     launch gives the same grey image; no guard word is touched and no output element is left unwritten."""
     a, b = _pair('x'.join(map(str, shape)) + f'/{k}', shape)
     if misalign:
-        a, b = _misaligned(a), _misaligned(b)
+        a, b = misaligned(a), misaligned(b)
     ga, gb, l1 = launch(a, b, k, want_gray_b=True, want_l1=True)
     assert not torch.isnan(ga).any() and not torch.isnan(gb).any() and not torch.isnan(l1).any()
     np.testing.assert_array_equal(ga.cpu().numpy(), emulate_gray(a.cpu().numpy(), k))
@@ -153,8 +126,8 @@ def test_l1_is_exact_zero_reproducible_and_the_same_in_both_load_forms():
     assert torch.equal(zero, torch.zeros_like(zero))
     first = launch(a, b, 2, want_gray_b=True, want_l1=True)
     again = launch(a, b, 2, want_gray_b=True, want_l1=True)
-    scalar = launch(_misaligned(a), _misaligned(b), 2, want_gray_b=True, want_l1=True)
-    mixed = launch(_misaligned(a), b, 2, want_gray_b=True, want_l1=True)          # one misaligned pointer is enough
+    scalar = launch(misaligned(a), misaligned(b), 2, want_gray_b=True, want_l1=True)
+    mixed = launch(misaligned(a), b, 2, want_gray_b=True, want_l1=True)          # one misaligned pointer is enough
     for other in (again, scalar, mixed):
         for x, y in zip(first, other):
             assert torch.equal(x, y)

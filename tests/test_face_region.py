@@ -15,11 +15,10 @@ import torch
 from torch import nn
 
 import ds_cases
+import launches
 import synth
-
-
-def dev():
-    return torch.device('cuda', 0)
+from gpumem import dev, misaligned
+from nets import PinNoise, load
 
 
 # ------------------------------------------------------------------------------------------------------------- CPU
@@ -98,15 +97,6 @@ def _run(r, g):
     return loss.detach(), face_region_scores(r, g), gg.grad, _native.render_mask(r)
 
 
-def _misaligned(t):
-    """The same values in a contiguous tensor whose data starts 4 bytes past a 16-byte boundary (scalar form)."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    v = buf[1:].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == 4
-    return v
-
-
 SHAPES = [(1, 3, 64, 64), (2, 1, 64, 64), (8, 4, 64, 64),
           (2, 3, 31, 257), (1, 4, 9, 257), (8, 1, 5, 257),
           (8, 3, 64, 1024), (1, 1, 1024, 1024), (2, 4, 32, 1024)]
@@ -130,7 +120,7 @@ def test_kernel_matches_fp64_restatement(shape):
     np.testing.assert_allclose(gd[inside].double().numpy(), d64[inside].numpy(), rtol=1e-6, atol=0)
     assert torch.count_nonzero(gd[~inside]) == 0
     # misaligned copies take the scalar form: the same arithmetic in the same order, the same bits
-    rv, gv = _misaligned(r), _misaligned(g)
+    rv, gv = misaligned(r), misaligned(g)
     loss2, scores2, grad2, mask2 = _run(rv, gv)
     assert torch.equal(loss2, loss) and torch.equal(scores2, scores) and torch.equal(grad2, grad)
     assert torch.equal(mask2, mask)
@@ -181,7 +171,7 @@ def test_mask_bit_identical_to_torch_mean(channels, k):
     ref = (r.mean(1) > -1).float()
     assert 0 < float(ref.sum()) < ref.numel()          # both sides of the boundary are present
     assert torch.equal(_native.render_mask(r), ref)
-    assert torch.equal(_native.render_mask(_misaligned(r)), ref)
+    assert torch.equal(_native.render_mask(misaligned(r)), ref)
     g = torch.zeros_like(r)
     grad = _native.face_region_loss_backward(r, g, torch.ones((), device=dev()))
     assert torch.equal((grad != 0).any(1).float(), ref)
@@ -219,26 +209,12 @@ def test_no_host_synchronisation():
     assert torch.isfinite(loss) and g.grad is not None and torch.isfinite(scores).all()
 
 
-class _Count:
-    wants_paths = False
-
-    def __init__(self):
-        self.names = []
-
-    def begin(self, name, info):
-        self.names.append(name)
-        return None
-
-    def end(self, tok):
-        pass
-
-
 def _ds_nets():
     import stylegan2
     import test_hip_train as H
     c = ds_cases.DS_CASE
     nets = H.build_nets(c['size'], with_d=True, n_mlp=c['n_mlp'])
-    nets['d_edit'] = H._load(stylegan2.Discriminator(c['size']), 'discriminator', c['d_edit_seed'])
+    nets['d_edit'] = load(stylegan2.Discriminator(c['size']), 'discriminator', c['d_edit_seed'])
     return nets
 
 
@@ -272,7 +248,7 @@ def test_ds_g_phase_golden(phase, golden):
     g_input, r_input, g_ref = dataset.Data_Loading(iter(()), iter([batch]), True, dev(), extreme_loader=iter([batch]),
                                                    extreme_ds_flag=extreme)
     assert g_input.shape[0] == (c['b'] // 2 if extreme else c['b'])
-    G = H.PinNoise(nets['g'], tr.nets['G'])
+    G = PinNoise(nets['g'], tr.nets['G'])
     ld = {}
     T.G_Loss_BackProp(G, tr.nets['E_Tsr'], tr.nets['E_W'], tr.nets['E_W_Plus'], Dn, g_input, r_input, g_ref, tr.args,
                       ld, None, iter_idx=0, extreme_ds_flag=extreme, ds_flag=True)
@@ -305,7 +281,6 @@ def test_train_iteration_schedule_with_d_edit():
     """Six iterations of Trainer.train_iteration at 256^2 with D_edit: flags rec, ds, rec, ds, rec, extreme; D_edit moves
     only in the dual-supervision iterations and D only in the others; the extreme batch is half the size; the
     face-regional term runs (two launches) exactly in the dual-supervision iterations; every loss is finite."""
-    from op import _native
     nets = _ds_nets()
     tr = _trainer(nets)
     b = 4
@@ -316,16 +291,12 @@ def test_train_iteration_schedule_with_d_edit():
     flags = []
     for it in range(6):
         before = {k: [p.detach().clone() for p in nets[k].parameters()] for k in ('d', 'd_edit')}
-        obs = _Count()
-        _native.set_observer(obs)
-        try:
+        with launches.observed() as obs:
             ld, ds_flag, extreme = tr.train_iteration(rec, ds, ep)
-        finally:
-            _native.set_observer(None)
         flags.append((ds_flag, extreme))
         moved = {k: any(not torch.equal(a, p) for a, p in zip(before[k], nets[k].parameters())) for k in before}
         assert moved == {'d': not ds_flag, 'd_edit': ds_flag}, (it, moved)
-        assert obs.names.count('face_region') == (2 if ds_flag else 0), (it, obs.names.count('face_region'))
+        assert obs.count('face_region') == (2 if ds_flag else 0), (it, obs.count('face_region'))
         for k in ('d', 'g', 'l1', 'face_reg', 'r1', 'g_reg'):
             assert torch.isfinite(ld[k]).all(), (it, k)
         assert (float(ld['face_reg'].detach()) > 0) == ds_flag
@@ -341,18 +312,13 @@ def test_reconstruction_step_launches_no_face_region_and_mismatch_raises():
     import cases
     import test_hip_train as H
     import train_3_encoder as T
-    from op import _native
     c = cases.TRAIN_STEP_CASE
     nets = H.build_nets(c['size'], with_d=True, n_mlp=2)
     photo, render, ref, _ = H.train_inputs()
     tr = T.Trainer(dict(G=nets['g'], E_Tsr=nets['e_tsr'], E_W=nets['e_w'], E_W_Plus=nets['e_wp'], D=nets['d']),
                    H.train_args(), dev())
-    obs = _Count()
-    _native.set_observer(obs)
-    try:
+    with launches.observed() as obs:
         ld = tr.step(photo, render, ref)
-    finally:
-        _native.set_observer(None)
     assert 'face_region' not in obs.names and len(obs.names) > 0
     assert float(ld['face_reg']) == 0.0
     with pytest.raises(ValueError, match=r'\(4, 3, 256, 256\).*\(4, 3, 64, 64\)'):

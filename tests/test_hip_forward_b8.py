@@ -24,18 +24,17 @@ import torch
 import torch.nn.functional as F
 
 import cases
+import launches
 import synth
-from parity import crop, img_close, input_window, ref_errors, tol
+from gpumem import dev
+from nets import load
+from parity import crop, img_close, input_window, ref_errors, tol, within_reference
 
 pytestmark = pytest.mark.gpu
 
 B = 8
 WINDOW = 32
 SAMPLES = [0, 3, 7]          # of the windows of the large layers: first, a middle and the last sample of the batch
-
-
-def dev():
-    return torch.device('cuda', 0)
 
 
 # ------------------------------------------------------------------------------------------------------- layer table
@@ -108,9 +107,7 @@ def _windows(res):
 @pytest.fixture(scope='module')
 def gen():
     import stylegan2
-    g = stylegan2.Generator(1024, 512, 8)
-    g.load_state_dict(synth.state_dict('generator', g.state_dict(), seed=4))
-    g = g.to(dev()).eval()
+    g = load(stylegan2.Generator(1024, 512, 8), 'generator', 4)
     yield g
     del g
     _CACHE.clear()
@@ -140,35 +137,9 @@ def _cpu_sd(m):
     return {k: v.detach().cpu() for k, v in m.state_dict().items()}
 
 
-class _Recorder:
-    """Launch observer: (name, info) of everything begun; wants_paths makes _native note the fused blur's kernel id."""
-    wants_paths = True
-
-    def __init__(self):
-        self.calls = []
-
-    def begin(self, name, info):
-        self.calls.append((name, tuple(info)))
-
-    def end(self, tok):
-        pass
-
-    @property
-    def names(self):
-        return [c[0] for c in self.calls]
-
-
-class _observe:
-    def __enter__(self):
-        from op import _native
-        self.rec = _Recorder()
-        _native.set_observer(self.rec)
-        return self.rec
-
-    def __exit__(self, *exc):
-        from op import _native
-        _native.set_observer(None)
-        return False
+def _observe():
+    """The launches of the block; wants_paths makes _native note the fused blur's kernel id."""
+    return launches.observed(wants_paths=True)
 
 
 # ------------------------------------------------------------------------------------------------------- references
@@ -235,7 +206,7 @@ def _gates(tag, got, refs):
         t = tol(r32)
         if not np.all(np.abs(a - r32) <= t['atol'] + t['rtol'] * np.abs(r32)):
             fails.append(f'{tag} window {(y0, x0)}: |HIP - oracle fp32| = {d32:.3e} of max(1, max|ref|) exceeds 2e-5 / rtol 1e-5')
-        if not e_hip <= 4.0 * e_ref + 2e-6:
+        if not within_reference(e_hip, e_ref):
             fails.append(f'{tag} window {(y0, x0)}: |HIP - fp64| = {e_hip:.3e} > 4 x {e_ref:.3e} + 2e-6')
     print(f'PARITY {tag}: |HIP-fp64| {worst[0]:.3e}  |oracle32-fp64| {worst[1]:.3e}  |HIP-oracle32| {worst[2]:.3e}', flush=True)
     assert not fails, '\n'.join(fails)
@@ -287,15 +258,15 @@ def test_styled_conv_at_batch_8(r, precision, gen):
         # ---- the path that ran is the path meant (after the values: a wrong path with right values shows as such)
         contraction = 'modconv2d_bf16x3' if precision == 'bf16x3' else 'modconv2d'
         if r['kind'] == 'up':
-            assert rec.calls[0] == (contraction, (B, r['cin'], r['cout'], h, h, 1)), rec.calls
+            assert rec.seen[0] == (contraction, (B, r['cin'], r['cout'], h, h, 1)), rec.seen
             assert rec.names == [contraction, 'upfirdn2d'], rec.names          # one fused blur, no two-pass fall-back
             path = _native.BLUR_PATHS.get((B * r['cout'], 2 * h + 1, 2 * h + 1))
             # plane-tile below 64 columns, register row-march from 64, LDS-DMA ring from 256 (csrc/upfirdn2d.hip)
             assert path == (2 if res < 64 else (1 if res < 256 else 5)), (path, res)
         elif wino:
-            assert rec.calls == [('modconv2d_winograd', (B, r['cin'], r['cout'], h, h, 0))], rec.calls
+            assert rec.seen == [('modconv2d_winograd', (B, r['cin'], r['cout'], h, h, 0))], rec.seen
         else:
-            assert rec.calls == [(contraction, (B, r['cin'], r['cout'], h, h, 0))], rec.calls
+            assert rec.seen == [(contraction, (B, r['cin'], r['cout'], h, h, 0))], rec.seen
 
         if wino:
             assert torch.equal(mod(xd, latd, noise=nzd), y)                        # two calls, the same bits
@@ -348,7 +319,7 @@ def test_styled_conv_at_batch_8(r, precision, gen):
             for keep in (True, False):                       # keep_out=False is what the Generator asks for
                 with _observe() as rec:
                     act, rgb = mod.fused_with_rgb(xd, latd, nzd, to_rgb, rgb_lat.to(d), skip_up.to(d), keep_out=keep)
-                assert rec.calls == [('modconv2d', (B, r['cin'], r['cout'], res, res, 0))], rec.calls
+                assert rec.seen == [('modconv2d', (B, r['cin'], r['cout'], res, res, 0))], rec.seen
                 assert (act is not None) == keep and rgb.shape == (B, 3, res, res)
                 if keep:
                     _gates(tag + ' fused-rgb activation', act, refs)

@@ -6,27 +6,21 @@ import pytest
 import torch
 
 import cases
+import launches
 import synth
+from gpumem import dev
+from nets import load
 from parity import tol as _tol, window_check as _window_check
 
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device('cuda', 0)
-
-
-def _load(module, kind, seed):
-    module.load_state_dict(synth.state_dict(kind, module.state_dict(), seed=seed))
-    return module.to(dev())
 
 
 @pytest.mark.parametrize('c', cases.MODCONV_CASES, ids=lambda c: c['name'])
 def test_modulated_conv_golden(c, golden):
     import stylegan2
     g = golden('modules')
-    m = _load(stylegan2.ModulatedConv2d(c['cin'], c['cout'], c['k'], 512, demodulate=c['demod'], upsample=c['up']),
-              'generator', 1)
+    m = load(stylegan2.ModulatedConv2d(c['cin'], c['cout'], c['k'], 512, demodulate=c['demod'], upsample=c['up']),
+             'generator', 1, eval=False)          # here and below the modules stay in training mode, as built
     x = synth.tensor(c['name'] + '/x', (c['b'], c['cin'], c['h'], c['h'])).to(dev())
     w = synth.tensor(c['name'] + '/w', (c['b'], 512)).to(dev())
     ref = g[c['name'] + '/out']
@@ -354,7 +348,7 @@ def test_rgb_fusable_is_host_logic_and_unsupported_shapes_are_refused():
 def test_styled_conv_golden_fused_and_unfused(c, golden):
     import stylegan2
     g = golden('modules')
-    m = _load(stylegan2.StyledConv(c['cin'], c['cout'], 3, 512, upsample=c['up']), 'generator', 2)
+    m = load(stylegan2.StyledConv(c['cin'], c['cout'], 3, 512, upsample=c['up']), 'generator', 2, eval=False)
     oh = c['h'] * 2 if c['up'] else c['h']
     x = synth.tensor(c['name'] + '/x', (c['b'], c['cin'], c['h'], c['h'])).to(dev())
     w = synth.tensor(c['name'] + '/w', (c['b'], 512)).to(dev())
@@ -374,7 +368,7 @@ def test_styled_conv_golden_fused_and_unfused(c, golden):
 def test_to_rgb_golden(c, golden):
     import stylegan2
     g = golden('modules')
-    m = _load(stylegan2.ToRGB(c['cin'], 512, upsample=c['skip']), 'generator', 3)
+    m = load(stylegan2.ToRGB(c['cin'], 512, upsample=c['skip']), 'generator', 3, eval=False)
     x = synth.tensor(c['name'] + '/x', (c['b'], c['cin'], c['h'], c['h'])).to(dev())
     w = synth.tensor(c['name'] + '/w', (c['b'], 512)).to(dev())
     skip = synth.tensor(c['name'] + '/skip', (c['b'], 3, c['h'] // 2, c['h'] // 2)).to(dev()) if c['skip'] else None
@@ -543,7 +537,7 @@ def test_modconv_gradients_match_reference_formulation():
     import stylegan2
     from oracle import torch_oracle as T
     for up in (False, True):
-        m = _load(stylegan2.StyledConv(6, 10, 3, 512, upsample=up), 'generator', 11)
+        m = load(stylegan2.StyledConv(6, 10, 3, 512, upsample=up), 'generator', 11, eval=False)
         sd = {'m.' + k: v.detach().cpu().double() for k, v in m.state_dict().items()}
         x = synth.tensor(f'mcg/{up}/x', (2, 6, 5, 5))
         w = synth.tensor(f'mcg/{up}/w', (2, 512))
@@ -678,34 +672,17 @@ def test_create_graph_path_runs_on_hip_kernels():
     """With a graph requested, ModulatedConv2d's backward must go through the DenseConv family (this repo's kernel),
     not through F.conv2d: count the MFMA-kernel launches the observer sees during backward + double backward."""
     import stylegan2
-    from op import _native
-
-    class Count:
-        def __init__(self):
-            self.n = {}
-
-        def begin(self, name, info):
-            self.n[name] = self.n.get(name, 0) + 1
-            return None
-
-        def end(self, tok):
-            pass
-
-    m = _load(stylegan2.StyledConv(6, 10, 3, 512, upsample=True), 'generator', 11)
+    m = load(stylegan2.StyledConv(6, 10, 3, 512, upsample=True), 'generator', 11, eval=False)
     x = synth.tensor('cgp/x', (2, 6, 5, 5)).to(dev()).requires_grad_(True)
     w = synth.tensor('cgp/w', (2, 512)).to(dev()).requires_grad_(True)
     y = m(x, w, noise=synth.tensor('cgp/n', (2, 1, 10, 10)).to(dev()))
-    obs = Count()
-    _native.set_observer(obs)
-    try:
+    with launches.observed() as obs:
         gx, = torch.autograd.grad(y.sum(), x, create_graph=True)
-        first = obs.n.get('modconv2d', 0)
+        first = obs.count('modconv2d')
         gx.pow(2).sum().backward()
-        second = obs.n.get('modconv2d', 0) - first
-    finally:
-        _native.set_observer(None)
-    assert first >= 2, obs.n       # recomputed forward C + data gradient D on the MFMA kernel
-    assert second >= 2, obs.n      # their derivatives, again on the MFMA kernel
+        second = obs.count('modconv2d') - first
+    assert first >= 2, obs.names       # recomputed forward C + data gradient D on the MFMA kernel
+    assert second >= 2, obs.names      # their derivatives, again on the MFMA kernel
 
 
 @pytest.mark.parametrize('shape', [

@@ -9,12 +9,11 @@ import pytest
 import torch
 
 import synth
+from gpumem import dev
+from nets import load
+from parity import no_farther_than_reference
 
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device('cuda', 0)
 
 
 CASES = [
@@ -103,9 +102,7 @@ def test_bf16_generator_forward_within_stated_tolerance():
     max ~8, so the bound is taken relative to max|image|."""
     import stylegan2
     from op import _native
-    G = stylegan2.Generator(256, 512, 2)
-    G.load_state_dict(synth.state_dict('generator', G.state_dict(), seed=4))
-    G = G.to(dev()).eval()
+    G = load(stylegan2.Generator(256, 512, 2), 'generator', 4)
     lat = synth.tensor('bf/g/lat', (2, G.n_latent, 512)).to(dev())
     tsr = synth.tensor('bf/g/tsr', (2, 512, 4, 4)).to(dev())
     kw = dict(latent_styles=[lat], input_is_latent=True, use_external_input_tensor=True, external_input_tensor=tsr,
@@ -134,9 +131,7 @@ def test_inference_and_training_under_autocast_are_safe():
     autocast up to the bf16 rounding of the style MLP, finite gradients."""
     import stylegan2
     from op import _native
-    G = stylegan2.Generator(64, 512, 2)
-    G.load_state_dict(synth.state_dict('generator', G.state_dict(), seed=4))
-    G = G.to(dev()).eval()
+    G = load(stylegan2.Generator(64, 512, 2), 'generator', 4)
     lat = synth.tensor('ac/lat', (2, G.n_latent, 512)).to(dev())
     tsr = synth.tensor('ac/tsr', (2, 512, 4, 4)).to(dev())
     kw = dict(latent_styles=[lat], input_is_latent=True, use_external_input_tensor=True, randomize_noise=False)
@@ -203,9 +198,7 @@ def test_bf16x3_generator_meets_the_fp32_path_gates(golden):
     for c in cases.GENERATOR_CASES:
         if c['name'] not in ('g256_full', 'g1024_full'):
             continue
-        G = stylegan2.Generator(c['size'], 512, c['n_mlp'])
-        G.load_state_dict(synth.state_dict('generator', G.state_dict(), seed=4))
-        G = G.to(dev()).eval()
+        G = load(stylegan2.Generator(c['size'], 512, c['n_mlp']), 'generator', 4)
         lat = synth.tensor(c['name'] + '/latent', (c['b'], G.n_latent, 512)).to(dev())
         tsr = synth.tensor(c['name'] + '/tsr', (c['b'], 512, 4, 4)).to(dev())
         with torch.no_grad(), _native.modconv_precision('bf16x3'):
@@ -215,6 +208,5 @@ def test_bf16x3_generator_meets_the_fp32_path_gates(golden):
         r32, r64 = g32[c['name'] + '/sub'], g64[c['name'] + '/sub']
         mx = float(np.abs(r64).max())
         np.testing.assert_allclose(a, r32, atol=1e-4 * mx, rtol=1e-4)
-        e_hip, e_ref = np.abs(a - r64).max() / mx, np.abs(r32 - r64).max() / mx
-        assert e_hip <= 4 * e_ref + 2e-6, (c['name'], e_hip, e_ref)
+        no_farther_than_reference(a, r32, r64)
         del G

@@ -24,13 +24,10 @@ import torch
 import torch.nn.functional as F
 
 import synth
+from gpumem import dev, misaligned
 from parity import tol as _tol
 
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device('cuda', 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------- cases
@@ -148,14 +145,6 @@ def _chunks_per_block(cin, ks):
     return (chunks + ks - 1) // ks
 
 
-def _one_float_further(t):
-    flat = torch.empty(t.numel() + 1, dtype=torch.float32, device=t.device)
-    m = flat[1:].view_as(t)
-    m.copy_(t)
-    assert m.data_ptr() % 16 == 4 and m.is_contiguous()
-    return m
-
-
 def _act64(core, noise, nw, bias):
     pre = core
     if noise is not None:
@@ -184,7 +173,7 @@ def test_default_plain_tiles_vs_float64(shape, want):
     y = _native.modconv2d(xd, wt, sd, dm, 0)
     _gate(f'plain {shape}', tile, ks, y, core)
     assert torch.equal(_native.modconv2d(xd, wt, sd, dm, 0), y)                         # bit-reproducible
-    xm = _one_float_further(xd)
+    xm = misaligned(xd)
     assert torch.equal(_native.modconv2d(xm, wt, sd, dm, 0), y)                         # 4-byte staging path
     buf, p0, ps, rs = _native.aligned_rows_buffer(b, cout, h, w, 1, d)
     buf.fill_(float('nan'))

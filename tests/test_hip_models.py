@@ -1,26 +1,18 @@
 """GPU parity tests at model level: Generator / 3-encoder forward / Discriminator on the HIP path vs the golden
 vectors captured from the reference, and gradients (first order, R1- and path-length-style second order) vs
 autograd through the CPU oracle."""
-import types
-
 import numpy as np
 import pytest
 import torch
 
 import cases
+import launches
 import synth
+from gpumem import dev
+from nets import PinNoise, encoders, load
 from parity import img_close, no_farther_than_reference as _no_farther_than_reference, tol as _tol
 
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device('cuda', 0)
-
-
-def _load(module, kind, seed):
-    module.load_state_dict(synth.state_dict(kind, module.state_dict(), seed=seed))
-    return module.to(dev()).eval()
 
 
 def _fp64():
@@ -41,7 +33,7 @@ def test_generator_golden(c, golden):
     output (the reference's own fp32-vs-fp64 distance: 0.8e-6 .. 1.9e-6)."""
     import stylegan2
     g = golden('generator')
-    G = _load(stylegan2.Generator(c['size'], 512, c['n_mlp'], generator_net_shape=c['shape']), 'generator', 4)
+    G = load(stylegan2.Generator(c['size'], 512, c['n_mlp'], generator_net_shape=c['shape']), 'generator', 4)
     with torch.no_grad():
         if c['mode'] == 'latent':
             cin0 = c['shape'][0] if c['shape'] else 512
@@ -58,7 +50,7 @@ def test_generator_graph_path_equals_fused_path(golden):
     """With autograd enabled StyledConv runs conv / noise / act as three ops; the image must not change."""
     import stylegan2
     c = cases.GENERATOR_CASES[0]
-    G = _load(stylegan2.Generator(c['size'], 512, c['n_mlp'], generator_net_shape=c['shape']), 'generator', 4)
+    G = load(stylegan2.Generator(c['size'], 512, c['n_mlp'], generator_net_shape=c['shape']), 'generator', 4)
     lat = synth.tensor(c['name'] + '/latent', (c['b'], G.n_latent, 512)).to(dev())
     tsr = synth.tensor(c['name'] + '/tsr', (c['b'], 16, 4, 4)).to(dev())
     kw = dict(latent_styles=[lat], input_is_latent=True, use_external_input_tensor=True, external_input_tensor=tsr,
@@ -73,28 +65,6 @@ def test_generator_graph_path_equals_fused_path(golden):
     torch.testing.assert_close(rgbs[-1].detach(), a, atol=1e-5, rtol=1e-5)
 
 
-def _encoders(n_styles):
-    import resnet_encoder
-    from psp_encoder_model.encoders import psp_encoders
-    e_tsr = _load(resnet_encoder.resnet18(tensor_encoding=True, tensor_transform=False), 'resnet', 5)
-    e_w = _load(resnet_encoder.resnet18(tensor_encoding=False, tensor_transform=False), 'resnet', 6)
-    e_wp = _load(psp_encoders.GradualStyleEncoder(18, 'ir_se', types.SimpleNamespace(input_nc=3, n_styles=n_styles)),
-                 'psp', 7)
-    return e_tsr, e_w, e_wp
-
-
-class _PinNoise(torch.nn.Module):
-    """The reference's Forward_Inference_3_Encoder never passes noise; the golden run pinned
-    randomize_noise=False the same way."""
-
-    def __init__(self, g):
-        super().__init__()
-        self.module = g
-
-    def forward(self, **kw):
-        return self.module(randomize_noise=False, **kw)
-
-
 @pytest.mark.parametrize('c', cases.E2E_CASES, ids=lambda c: c['name'])
 def test_forward_inference_3_encoder_golden(c, golden):
     """(photo, render) -> image through encoders (MIOpen) + Generator (HIP kernels) vs the reference."""
@@ -102,8 +72,8 @@ def test_forward_inference_3_encoder_golden(c, golden):
     from Util.network_util import Forward_Inference_3_Encoder
     g = golden('e2e')
     n_latent = int(np.log2(c['size'])) * 2 - 2
-    e_tsr, e_w, e_wp = _encoders(n_latent)
-    G = _load(stylegan2.Generator(c['size'], 512, 8), 'generator', 4)
+    e_tsr, e_w, e_wp = encoders(n_latent)
+    G = load(stylegan2.Generator(c['size'], 512, 8), 'generator', 4)
     p = synth.tensor(c['name'] + '/photo', (c['b'], 3, 256, 256), dist='uniform').to(dev())
     r = synth.tensor(c['name'] + '/render', (c['b'], 3, 256, 256), dist='uniform').to(dev())
     # Tolerances = measured error x ~5 (profiles/r02_parity_errors.md).  Encoders (MIOpen convolutions, summation order
@@ -115,7 +85,7 @@ def test_forward_inference_3_encoder_golden(c, golden):
             out, ref = net(x).cpu().numpy(), g[f"{c['name']}/{key}"]
             np.testing.assert_allclose(out, ref, atol=5e-6 * np.abs(ref).max(), rtol=1e-4)
             _no_farther_than_reference(out, ref, f64[f"{c['name']}/{key}"])
-        img = Forward_Inference_3_Encoder(p, r, e_tsr, e_w, e_wp, _PinNoise(G), tsr_encode=c['tsr_encode'],
+        img = Forward_Inference_3_Encoder(p, r, e_tsr, e_w, e_wp, PinNoise(G), tsr_encode=c['tsr_encode'],
                                           sliced_layer=c['sliced_layer'], use_tanh=c['use_tanh'])
     _img_close(img, g, c['name'], c['stride'], rel=5e-5)
 
@@ -124,7 +94,7 @@ def test_forward_inference_3_encoder_golden(c, golden):
 def test_discriminator_golden(c, golden):
     import stylegan2
     g = golden('discriminator')
-    D = _load(stylegan2.Discriminator(c['size']), 'discriminator', 8)
+    D = load(stylegan2.Discriminator(c['size']), 'discriminator', 8)
     x = synth.tensor(c['name'] + '/x', (c['b'], 3, c['size'], c['size']), dist='uniform').to(dev())
     with torch.no_grad():
         y = D(x)
@@ -141,7 +111,7 @@ def test_generator_gradients_and_path_length_vs_oracle():
     import stylegan2
     from oracle import torch_oracle as T
     shape = [8, 8, 8, 8, 8, 8, 6, 6]
-    G = _load(stylegan2.Generator(32, 512, 1, generator_net_shape=shape), 'generator', 12)
+    G = load(stylegan2.Generator(32, 512, 1, generator_net_shape=shape), 'generator', 12)
     sd64 = {k: v.detach().cpu().double() for k, v in G.state_dict().items()}
     lat = synth.tensor('gg/lat', (2, G.n_latent, 512))
     tsr = synth.tensor('gg/tsr', (2, 8, 4, 4))
@@ -190,7 +160,7 @@ def test_discriminator_r1_penalty_vs_oracle():
     double-backward through upfirdn2d and fused_leaky_relu on the HIP path."""
     import stylegan2
     from oracle import torch_oracle as T
-    D = _load(stylegan2.Discriminator(16), 'discriminator', 13)
+    D = load(stylegan2.Discriminator(16), 'discriminator', 13)
     sd64 = {k: v.detach().cpu().double() for k, v in D.state_dict().items()}
     x = synth.tensor('r1/x', (4, 3, 16, 16), dist='uniform')
     wkey = 'convs.1.conv2.1.weight'
@@ -226,13 +196,13 @@ def test_overlapped_and_graphed_forward_equal_serial():
     from Util import streams
     from Util.network_util import Forward_Inference_3_Encoder
     from Util.hip_graph import GraphedForward
-    e_tsr, e_w, e_wp = _encoders(10)
-    G = _load(stylegan2.Generator(64, 512, 2), 'generator', 4)
+    e_tsr, e_w, e_wp = encoders(10)
+    G = load(stylegan2.Generator(64, 512, 2), 'generator', 4)
     p = synth.tensor('ovl/photo', (2, 3, 256, 256), dist='uniform').to(dev())
     r = synth.tensor('ovl/render', (2, 3, 256, 256), dist='uniform').to(dev())
     lat = synth.tensor('ovl/lat', (2, G.n_latent, 512)).to(dev())
     tsr = synth.tensor('ovl/tsr', (2, 512, 4, 4)).to(dev())
-    wrap = _PinNoise(G)
+    wrap = PinNoise(G)
 
     def gen(l, t):
         with torch.no_grad():
@@ -271,9 +241,9 @@ def test_pipelined_forward_matches_serial_for_partial_slices_and_tanh():
     import stylegan2
     from Util import streams
     from Util.network_util import Forward_Inference_3_Encoder
-    e_tsr, e_w, e_wp = _encoders(10)                               # 10 style heads
-    G = _load(stylegan2.Generator(32, 512, 2), 'generator', 21)    # n_latent = 8 < 10
-    wrap = _PinNoise(G)
+    e_tsr, e_w, e_wp = encoders(10)                               # 10 style heads
+    G = load(stylegan2.Generator(32, 512, 2), 'generator', 21)    # n_latent = 8 < 10
+    wrap = PinNoise(G)
     p = synth.tensor('pipe/photo', (3, 3, 256, 256), dist='uniform').to(dev())
     r = synth.tensor('pipe/render', (3, 3, 256, 256), dist='uniform').to(dev())
     for sliced, tanh in ((None, False), ([0, 3, 4], True), ([], False), (range(2, 20), True)):
@@ -299,11 +269,11 @@ def test_forward_through_data_parallel_wrappers_equals_bare_modules():
     import stylegan2
     from Miscellaneous import distributed as D
     from Util.network_util import Forward_Inference_3_Encoder
-    e_tsr, e_w, e_wp = _encoders(8)
-    G = _load(stylegan2.Generator(32, 512, 2), 'generator', 21)
+    e_tsr, e_w, e_wp = encoders(8)
+    G = load(stylegan2.Generator(32, 512, 2), 'generator', 21)
     p = synth.tensor('dpw/photo', (2, 3, 256, 256), dist='uniform').to(dev())
     r = synth.tensor('dpw/render', (2, 3, 256, 256), dist='uniform').to(dev())
-    bare = _PinNoise(G)
+    bare = PinNoise(G)
     wrapped = [D.data_parallel(m, dev()) for m in (e_tsr, e_w, e_wp)]
     assert all(hasattr(w, 'module') for w in wrapped)
     with torch.no_grad():
@@ -323,7 +293,7 @@ def test_full_path_is_bit_reproducible_once_encoder_outputs_are_fixed():
     from Util import streams
     from Util.network_util import Forward_Inference_3_Encoder
     from Util.streams import run_deferred, side_streams
-    G = _load(stylegan2.Generator(64, 512, 2), 'generator', 4)
+    G = load(stylegan2.Generator(64, 512, 2), 'generator', 4)
     n = G.n_latent
     tsr = synth.tensor('fix/tsr', (2, 512, 4, 4)).to(dev())
     wv = synth.tensor('fix/w', (2, 512)).to(dev())
@@ -349,7 +319,7 @@ def test_full_path_is_bit_reproducible_once_encoder_outputs_are_fixed():
 
     def fwd(sliced):
         with torch.no_grad():
-            return Forward_Inference_3_Encoder(x, x, *nets, _PinNoise(G), sliced_layer=sliced).clone()
+            return Forward_Inference_3_Encoder(x, x, *nets, PinNoise(G), sliced_layer=sliced).clone()
 
     for sliced in (None, [1, 4, 5]):
         try:
@@ -367,9 +337,7 @@ def test_placement_workspaces_do_not_change_results_or_leak(monkeypatch):
     layer called on its own never hands out a persistent tensor; selection happened for exactly the layers above 256 MiB."""
     import stylegan2
     from op import placement
-    G = stylegan2.Generator(256, 512, 2)
-    G.load_state_dict(synth.state_dict('generator', G.state_dict(), seed=4))
-    G = G.to(dev()).eval()
+    G = load(stylegan2.Generator(256, 512, 2), 'generator', 4)
     b = 32
     lat = synth.tensor('pl/lat', (b, G.n_latent, 512)).to(dev())
     lat2 = synth.tensor('pl/lat2', (b, G.n_latent, 512)).to(dev())
@@ -416,20 +384,6 @@ def _styled_up(blur_kernel, name):
     return sc.to(dev()).eval(), x.to(dev()), lat.to(dev()), noise.to(dev()), ref.numpy()
 
 
-class _Names:
-    """Launch observer that records what was begun."""
-    wants_paths = False
-
-    def __init__(self):
-        self.names = []
-
-    def begin(self, name, info):
-        self.names.append(name)
-
-    def end(self, tok):
-        pass
-
-
 def test_blur_the_fused_kernel_does_not_serve_inside_a_placement_scope(monkeypatch):
     """StyledConv(upsample=True, blur_kernel=[1,4,6,4,1]): the fused blur + noise + bias + act kernels take FIRs of at most
     4 taps (tests/test_abi_host.py), so this layer runs the two-pass form.  Inside placement.scope(), with an intermediate
@@ -444,15 +398,10 @@ def test_blur_the_fused_kernel_does_not_serve_inside_a_placement_scope(monkeypat
     monkeypatch.setattr(placement, 'MIN_BYTES', 1 << 20)
     monkeypatch.setattr(placement, 'ENABLED', True)
     placement.forget()
-    obs = _Names()
     with torch.no_grad():
         off = sc(x, lat, noise=noise)
-        _native_set(obs)
-        try:
-            with placement.scope():
-                on = sc(x, lat, noise=noise).clone()
-        finally:
-            _native_set(None)
+        with launches.observed() as obs, placement.scope():
+            on = sc(x, lat, noise=noise).clone()
     np.testing.assert_allclose(on.cpu().numpy(), ref, **_tol(ref))
     assert torch.equal(on, off)
     # no workspace was selected for a pair whose consumer has no kernel; the fused blur was asked once and declined, then
@@ -471,24 +420,15 @@ def test_default_blur_inside_a_placement_scope_keeps_its_two_launches(monkeypatc
     monkeypatch.setattr(placement, 'MIN_BYTES', 1 << 20)
     monkeypatch.setattr(placement, 'ENABLED', True)
     placement.forget()
-    obs = _Names()
     with torch.no_grad():
         off = sc(x, lat, noise=noise)
         with placement.scope():
             first = sc(x, lat, noise=noise).clone()
-            _native_set(obs)
-            try:
+            with launches.observed() as obs:
                 again = sc(x, lat, noise=noise)
-            finally:
-                _native_set(None)
     ws, = placement._STORE[sc].values()
     assert again.data_ptr() == ws.out.data_ptr()
     assert obs.names == ['modconv2d', 'upfirdn2d'], obs.names
     np.testing.assert_allclose(again.cpu().numpy(), ref, **_tol(ref))
     assert torch.equal(first, off) and torch.equal(again, off)
     placement.forget()
-
-
-def _native_set(obs):
-    from op import _native
-    _native.set_observer(obs)

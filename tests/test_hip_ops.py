@@ -6,13 +6,10 @@ import torch
 
 import cases
 import synth
+from gpumem import dev
 
 pytestmark = pytest.mark.gpu
 OP_TOL = dict(atol=1e-5, rtol=1e-5)   # SURVEY.md §8c / BASELINE.md §4: per-op fp32 tolerance
-
-
-def dev():
-    return torch.device('cuda', 0)
 
 
 def _run_ufd(x, k, c, force_path=-1):

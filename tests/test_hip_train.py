@@ -42,7 +42,6 @@ reference's own fp32-vs-fp64 differences have the same cause.  So:
 """
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -50,6 +49,8 @@ import torch
 
 import cases
 import synth
+from gpumem import dev
+from nets import PinNoise, encoders, load as _load         # PinNoise, _load: also read from here by tools/measure_parity.py
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,42 +59,14 @@ MARGIN, FLOOR, FLOOR_MIOPEN, FLOOR_NORM, FLOOR_SCALAR = 4.0, 5e-4, 4e-3, 5e-4, 8
 KINK_TENSORS, KINK_MAX, KINK_NORM, KINK_ELEMS = 6, 0.1, 2e-2, 3     # one flip shows in the weight AND the bias gradient of its layer
 
 
-def dev():
-    return torch.device('cuda', 0)
-
-
-def _load(module, kind, seed):
-    module.load_state_dict(synth.state_dict(kind, module.state_dict(), seed=seed))
-    return module.to(dev()).eval()
-
-
 def build_nets(size, with_d=False, n_mlp=8):
     import stylegan2
-    import resnet_encoder
-    from psp_encoder_model.encoders import psp_encoders
     n_latent = int(np.log2(size)) * 2 - 2
-    nets = dict(
-        e_tsr=_load(resnet_encoder.resnet18(tensor_encoding=True, tensor_transform=False), 'resnet', 5),
-        e_w=_load(resnet_encoder.resnet18(tensor_encoding=False, tensor_transform=False), 'resnet', 6),
-        e_wp=_load(psp_encoders.GradualStyleEncoder(18, 'ir_se', types.SimpleNamespace(input_nc=3, n_styles=n_latent)),
-                   'psp', 7),
-        g=_load(stylegan2.Generator(size, 512, n_mlp), 'generator', 4))
+    nets = dict(zip(('e_tsr', 'e_w', 'e_wp'), encoders(n_latent)),
+                g=_load(stylegan2.Generator(size, 512, n_mlp), 'generator', 4))
     if with_d:
         nets['d'] = _load(stylegan2.Discriminator(size), 'discriminator', 8)
     return nets
-
-
-class PinNoise(torch.nn.Module):
-    """Forward_Inference_3_Encoder never passes noise; the fixtures pinned randomize_noise=False.
-    `.module` is what the reference reads n_latent from (Util/network_util.py:317-318)."""
-
-    def __init__(self, g, call=None):
-        super().__init__()
-        self.module = g
-        self._call = [call if call is not None else g]      # in a list: not a registered submodule twice
-
-    def forward(self, **kw):
-        return self._call[0](randomize_noise=False, **kw)
 
 
 def check_grads(g, prefix, named_params, report=None, margin=MARGIN, floor=None, kinks=None, floor_norm=None):

@@ -19,14 +19,11 @@ import torch
 
 import cases
 import synth
+from gpumem import dev
 import ufd_cases as U
 
 pytestmark = pytest.mark.gpu
 F32 = 0
-
-
-def dev():
-    return torch.device('cuda', 0)
 
 
 def _tol(ref_max):

@@ -9,10 +9,7 @@ import pytest
 import torch
 
 import cases
-
-
-def dev():
-    return torch.device('cuda', 0)
+from gpumem import dev
 
 
 @pytest.fixture(scope='module')

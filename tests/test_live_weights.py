@@ -7,6 +7,8 @@ import pytest
 import torch
 
 import synth
+from gpumem import dev
+from nets import load
 
 
 def test_refresh_entry_layout_matches_library():
@@ -22,15 +24,9 @@ def test_refresh_entry_layout_matches_library():
     assert L.fmgan_weight_refresh_f32(None, 3, 10, None) == -1
 
 
-def dev():
-    return torch.device('cuda', 0)
-
-
 def _gen(size=32, shape=None, n_mlp=2, seed=31):
     import stylegan2
-    G = stylegan2.Generator(size, 512, n_mlp, generator_net_shape=shape)
-    G.load_state_dict(synth.state_dict('generator', G.state_dict(), seed=seed))
-    return G.to(dev()).eval()
+    return load(stylegan2.Generator(size, 512, n_mlp, generator_net_shape=shape), 'generator', seed)
 
 
 def _run(G, lat, tsr, **kw):
@@ -155,9 +151,7 @@ def test_ema_accumulate_reaches_the_next_inference_forward():
 def test_psp_heads_see_data_mutation():
     import types
     from psp_encoder_model.encoders import psp_encoders
-    e = psp_encoders.GradualStyleEncoder(18, 'ir_se', types.SimpleNamespace(input_nc=3, n_styles=4))
-    e.load_state_dict(synth.state_dict('psp', e.state_dict(), seed=7))
-    e = e.to(dev()).eval()
+    e = load(psp_encoders.GradualStyleEncoder(18, 'ir_se', types.SimpleNamespace(input_nc=3, n_styles=4)), 'psp', 7)
     p = synth.tensor('lw/photo', (1, 3, 256, 256), dist='uniform').to(dev())
     with torch.no_grad():
         a = e(p).clone()

@@ -25,15 +25,14 @@ import re
 import pytest
 import torch
 
+import launches
 import synth
+from gpumem import dev, misaligned_nhwc
+from nets import PinNoise, lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = 1e-10
 GRADS = (-0.75, 0.0, 1.5)
-
-
-def dev():
-    return torch.device('cuda', 0)
 
 
 def composite(f0, f1, w, eps=EPS):
@@ -63,32 +62,11 @@ def gate(what, e_kernel, e_fp32):
     assert e_kernel <= 2 * e_fp32 + 2e-6, (what, e_kernel, e_fp32)
 
 
-class Records:
-    wants_paths = False
-
-    def __init__(self):
-        self.seen = []
-
-    def begin(self, name, info):
-        self.seen.append((name, info))
-        return None
-
-    def end(self, tok):
-        pass
-
-    def lpips(self):
-        return [info for name, info in self.seen if name == 'lpips_distance']
-
-
 def observed(fn):
-    from op import _native
-    obs = Records()
-    _native.set_observer(obs)
-    try:
+    """(fn(), the infos of the lpips_distance launches during it)."""
+    with launches.observed() as rec:
         out = fn()
-    finally:
-        _native.set_observer(None)
-    return out, obs
+    return out, rec.infos('lpips_distance')
 
 
 def make_inputs(shape, zero_pixel=None):
@@ -129,16 +107,11 @@ def kernel_backward(c, need0, need1):
 
 
 # ------------------------------------------------------------------------------------------------------------- CPU
-def _lib():
-    from op import _native
-    return _native.lib()
-
-
 def test_blocks_is_host_logic():
     """fmgan_lpips_distance_blocks without a device: ceil(hw / pixels per block step) blocks per sample (16 pixels x
     4 / 2 / 1 / 1 per lane at C = 64 / 128 / 256 / 512), at most ceil(2048 / batch) (8 blocks per CU over the batch,
     256 CUs assumed without a device) and at most 1024; 0 where the kernel does not serve."""
-    L = _lib()
+    L = lib()
     assert L.fmgan_lpips_distance_blocks(8, 64, 1 << 20) == 2048 // 8
     assert L.fmgan_lpips_distance_blocks(8, 512, 128 * 128) == 2048 // 8
     assert L.fmgan_lpips_distance_blocks(1, 64, 1 << 20) == 1024                 # the cap
@@ -154,7 +127,7 @@ def test_blocks_is_host_logic():
 
 
 def test_statuses_before_any_hip_call():
-    L = _lib()
+    L = lib()
     fwd, bwd = L.fmgan_lpips_distance_f32, L.fmgan_lpips_distance_backward_f32
     p, odd = ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1004)
     assert fwd(None, None, None, None, 0, 64, 64, EPS, None) == 0                 # empty batch: nothing to do
@@ -178,7 +151,7 @@ def test_header_declares_the_entry_points():
     hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
     for name in ('fmgan_lpips_distance_blocks', 'fmgan_lpips_distance_f32', 'fmgan_lpips_distance_backward_f32'):
         assert re.search(r'\bint\s+' + name + r'\s*\(', hdr), name
-        assert hasattr(_lib(), name)
+        assert hasattr(lib(), name)
 
 
 def test_cpu_tensors_keep_the_composite():
@@ -191,7 +164,7 @@ def test_cpu_tensors_keep_the_composite():
     f0, f1 = (t.contiguous(memory_format=torch.channels_last) for t in (f0, f1))
     assert not lpips_distance_serves(f0, f1, w)
     _, obs = observed(lambda: lpips_distance(f0, f1, w))
-    assert obs.lpips() == []
+    assert obs == []
     assert torch.equal(lpips_distance(f0, f1, w), composite(f0, f1, w))
     with pytest.raises(RuntimeError):
         _native.lpips_distance(f0, f1, w)
@@ -211,7 +184,7 @@ IDS = ['x'.join(map(str, s)) for s in SHAPES]
 
 def _blocks(shape):
     n, c, h, w = shape
-    return _lib().fmgan_lpips_distance_blocks(n, c, h * w)
+    return lib().fmgan_lpips_distance_blocks(n, c, h * w)
 
 
 @pytest.mark.gpu
@@ -226,7 +199,7 @@ def test_forward_matches_fp64_composite(shape):
     assert lpips_distance_serves(c['f0'], c['f1'], c['w'])
     (d, obs) = observed(lambda: lpips_distance(c['f0'], c['f1'], c['w']))
     n, ch, h, w = shape
-    assert obs.lpips() == [(n, ch, h * w, 0)]
+    assert obs == [(n, ch, h * w, 0)]
     assert d.shape == (n, 1, 1, 1) and d.dtype == torch.float32
     gate(f'd {shape}', err(d, c['ref'][0]), err(c['f32'][0], c['ref'][0]))
     assert torch.equal(lpips_distance(c['f0'], c['f1'], c['w']), d)                       # run to run: the same bits
@@ -241,7 +214,7 @@ def test_backward_matches_fp64_autograd(shape):
     n, ch, h, w = shape
     for need0, need1 in ((False, True), (True, False), (True, True)):
         (out, obs) = observed(lambda: kernel_backward(c, need0, need1))
-        assert obs.lpips() == [(n, ch, h * w, 0), (n, ch, h * w, 1)]
+        assert obs == [(n, ch, h * w, 0), (n, ch, h * w, 1)]
         again = kernel_backward(c, need0, need1)
         for k, need in ((1, need0), (2, need1)):
             if not need:
@@ -274,16 +247,6 @@ def test_zero_norm_pixel_is_nan_there_and_nowhere_else():
     gate('grad_f0 zero-norm', err(g0, c['ref'][1]), err(c['f32'][1], c['ref'][1]))
 
 
-def _offset_by_one_float(t):
-    """The same values, NHWC-dense, starting 4 bytes past a 16-byte boundary."""
-    n, c, h, w = t.shape
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    v = buf[1:].view(n, h, w, c).permute(0, 3, 1, 2)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == 4 and v.permute(0, 2, 3, 1).is_contiguous()
-    return v
-
-
 @pytest.mark.gpu
 def test_unserved_calls_fall_back_to_the_composite():
     from op import _native
@@ -296,14 +259,14 @@ def test_unserved_calls_fall_back_to_the_composite():
     calls = {
         'nchw': (f0.contiguous(), f1.contiguous(), w),
         'c96': (f96, g96, w96),
-        'offset': (_offset_by_one_float(f0), f1, w),
+        'offset': (misaligned_nhwc(f0), f1, w),
         'bf16': (f0.bfloat16(), f1.bfloat16(), w.bfloat16()),
         'weight_grad': (f0, f1, w.clone().requires_grad_(True)),
     }
     for name, (a, b, ww) in calls.items():
         assert not lpips_distance_serves(a, b, ww), name
         (d, obs) = observed(lambda: lpips_distance(a, b, ww))
-        assert obs.lpips() == [], name
+        assert obs == [], name
         assert torch.equal(d, composite(a, b, ww)), name
     d = lpips_distance(*calls['weight_grad'])
     d.sum().backward()
@@ -368,10 +331,10 @@ def test_perceptual_loss_module_uses_the_kernel():
     pg, tg = nhwc(pred), nhwc(target)
     (on, obs) = observed(lambda: _module_run(mg, pg, tg, g.to(dev()), True))
     (off, obs_off) = observed(lambda: _module_run(mg, pg, tg, g.to(dev()), False))
-    assert obs_off.lpips() == []
+    assert obs_off == []
     hw = [64 * 64, 32 * 32, 16 * 16, 8 * 8, 4 * 4]
     fwd = [(2, c, p, 0) for c, p in zip((64, 128, 256, 512, 512), hw)]
-    assert obs.lpips()[:5] == fwd and sorted(obs.lpips()[5:]) == sorted((n, c, p, 1) for n, c, p, _ in fwd)
+    assert obs[:5] == fwd and sorted(obs[5:]) == sorted((n, c, p, 1) for n, c, p, _ in fwd)
     gate('PerceptualLoss d', err(on[0], ref[0]), err(off[0], ref[0]))
     gate('PerceptualLoss d/d image', err(on[1], ref[1]), err(off[1], ref[1]))
     import lpips
@@ -388,7 +351,7 @@ def test_perceptual_loss_module_uses_the_kernel():
         _, obs_train = observed(lambda: mg(pg, tg))
     finally:
         mg.eval()
-    assert obs_train.lpips() == []
+    assert obs_train == []
 
 
 def _rel_diffs(a, b):
@@ -429,7 +392,7 @@ def test_g_step_agrees_with_the_composite():
     photo, render, ref, _ = H.train_inputs()
     args = H.train_args()
     lp = _perceptual().to(dev()).to(memory_format=torch.channels_last)
-    G = H.PinNoise(nets['g'])
+    G = PinNoise(nets['g'])
     trained = [(k, n) for k in ('g', 'e_tsr', 'e_w', 'e_wp') for n in nets[k].named_parameters()]
 
     def step(fused):
@@ -442,7 +405,7 @@ def test_g_step_agrees_with_the_composite():
         finally:
             lpips.FUSED = old
         grads = {f'{k}.{name}': p.grad.detach().clone() for k, (name, p) in trained if p.grad is not None}
-        return float(ld['lpips'].detach()), grads, len(obs.lpips())
+        return float(ld['lpips'].detach()), grads, len(obs)
 
     step(False)                                  # the first call of each convolution picks its kernel: not compared
     offs = [step(False) for _ in range(3)]

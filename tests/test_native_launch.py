@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import launches
 import synth
 from parity import tol as _tol
 
@@ -19,12 +20,16 @@ def test_served_interprets_the_status():
     text = L.fmgan_status_string(einval).decode()
     assert text and text != L.fmgan_status_string(0).decode()
     for fn in (_native.served, _native.check):
-        with pytest.raises(RuntimeError) as e:
+        with pytest.raises(RuntimeError) as e, launches.observed() as rec:
+            assert _native._observer is rec
             fn(einval, 'some_launch')
         assert str(e.value) == f'some_launch: {text} (status {einval})'
+        assert isinstance(_native._observer, _native._NullObserver)         # back after a body that raised
 
 
 class _Recorder:
+    """Local, not launches.Recorder: this one tests the bracket itself (end() gets the token its begin() returned)."""
+
     def __init__(self):
         self.events = []
 
@@ -39,13 +44,8 @@ class _Recorder:
 
 def _recorded(fn):
     """(fn(), the events an observer saw during it); the null observer is back afterwards, whatever fn did."""
-    from op import _native
-    rec = _Recorder()
-    _native.set_observer(rec)
-    try:
+    with launches.observed(_Recorder()) as rec:
         return fn(), rec.events
-    finally:
-        _native.set_observer(None)
 
 
 @pytest.mark.gpu

@@ -4,26 +4,19 @@ the Generator cases are in tests/test_ppl_gpu.py."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import codeobj
 import ppl_cases as pc
 import synth
+from nets import lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, '3d-fm-gan_amd', 'csrc', 'libfmgan_hip.so')
-LLVM = '/opt/rocm/lib/llvm/bin'
 OK, EINVAL, EUNSUPPORTED, EOVERFLOW = 0, -1, -2, -4
-
-
-def _lib():
-    from op import _native
-    return _native.lib()
 
 
 # ------------------------------------------------------------------------------------------------ library and binding
@@ -32,7 +25,7 @@ def test_library_exports_the_pair_input_entry_points():
     counts (eight ints; five pointers, eight ints and the stream)."""
     hdr = open(os.path.join(ROOT, 'include', 'fmgan_hip.h')).read()
     hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    L = _lib()
+    L = lib()
     for name, pointers, ints in (('fmgan_lpips_pair_input_select', 0, 8), ('fmgan_lpips_pair_input_f32', 6, 8)):
         params = re.search(r'\b' + name + r'\s*\(([^()]*)\)\s*;', hdr).group(1).split(',')
         assert len(params) == pointers + ints and sum('*' in p for p in params) == pointers, name
@@ -47,7 +40,7 @@ def test_select_returns_a_kernel_id_or_the_launch_status():
     """fmgan_lpips_pair_input_select is the launch's plan with the launch left out: f for the vector form (ow % 4 == 0),
     8 + f for the bounded one, and for each refused argument class the status the launch itself returns (the launches here
     are refused before any HIP call: the pointers are placeholders)."""
-    L = _lib()
+    L = lib()
     sel = L.fmgan_lpips_pair_input_select
     fake = ctypes.c_void_p(0x1000)
 
@@ -106,7 +99,7 @@ def test_pair_input_geometry_is_the_references(size, crop, want):
     assert plan == want
     if plan is not None:
         (y0, x0, hc, wc), f = plan
-        assert _lib().fmgan_lpips_pair_input_select(2, size, size, y0, x0, hc, wc, f) == f
+        assert lib().fmgan_lpips_pair_input_select(2, size, size, y0, x0, hc, wc, f) == f
         assert (hc // f, wc // f) == ((256, 256) if factor > 1 else (hc, wc))
     for shape in ((3, 3, size, size), (0, 3, size, size), (4, 1, size, size), (4, 3, size, size // 2), (4, 3, size)):
         assert PI.pair_input_plan(shape, crop) is None, shape
@@ -236,27 +229,8 @@ def test_batch_schedule_and_value_error():
 @pytest.fixture(scope='module')
 def kernels(tmp_path_factory):
     """The notes of the pair-input kernels in the built library, read as tests/test_lpips_kernel_budget.py reads them."""
-    objdump, readelf = os.path.join(LLVM, 'llvm-objdump'), os.path.join(LLVM, 'llvm-readelf')
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip('llvm-objdump / llvm-readelf not found')
-    d = tmp_path_factory.mktemp('codeobj')
-    shutil.copy(LIB, d / 'lib.so')
-    subprocess.run([objdump, '--offloading', str(d / 'lib.so')], check=True, capture_output=True, cwd=d)
-    out = {}
-    for f in sorted(os.listdir(d)):
-        if not f.endswith('gfx950'):
-            continue
-        notes = subprocess.run([readelf, '--notes', str(d / f)], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split('- .agpr_count')[1:]:
-            name = re.search(r'\.name:\s+(\S+)', blk).group(1)
-            if 'lpips_pair_input' not in name:
-                continue
-
-            def num(key):
-                return int(re.search(key + r':\s+(\d+)', blk).group(1))
-            out[name] = {'vgpr': num(r'\.vgpr_count'), 'vgpr_spill': num(r'\.vgpr_spill_count'),
-                         'sgpr_spill': num(r'\.sgpr_spill_count'), 'scratch': num(r'\.private_segment_fixed_size')}
-    return out
+    notes = codeobj.kernel_notes(tmp_path_factory.mktemp('codeobj'))
+    return {name: k for name, k in notes.items() if 'lpips_pair_input' in name}
 
 
 def test_pair_input_kernels_have_no_spill_and_no_scratch(kernels):

@@ -6,31 +6,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import launches
+import nets
 import ppl_cases as pc
 import synth
-from test_hip_train import PinNoise, _load
+from gpumem import dev, guarded, guards_intact
+from nets import PinNoise, load, scaling
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64          # guard floats on each side of an output buffer
-SENTINEL = 12345.5
-
-
-def dev():
-    return torch.device('cuda', 0)
-
-
-def _guarded(shape):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * GUARD,), float('nan'), dtype=torch.float32, device=dev())
-    buf[:GUARD] = SENTINEL
-    buf[GUARD + n:] = SENTINEL
-    return buf, buf[GUARD:GUARD + n].view(shape)
-
-
-def _scaling():
-    import lpips
-    return lpips.ScalingLayer().to(dev())
 
 
 def expected(img, shift, scale, window, f):
@@ -75,12 +58,12 @@ def test_kernel_against_the_formula_bit_for_bit(shape, f, window):
     values = synth.tensor('ppl/kernel/' + 'x'.join(map(str, shape)), shape, dist='uniform').to(dev())
     img = torch.full(shape, float('nan'), dtype=torch.float32, device=dev())
     img[:, :, y0:y0 + hc, x0:x0 + wc] = values[:, :, y0:y0 + hc, x0:x0 + wc]
-    sl = _scaling()
+    sl = scaling()
     shift, scale = sl.shift.reshape(3), sl.scale.reshape(3)
     oh, ow = hc // f, wc // f
     kernel = L.fmgan_lpips_pair_input_select(n // 2, h, w, y0, x0, hc, wc, f)
     assert kernel == (f if ow % 4 == 0 else 8 + f)
-    (buf0, out0), (buf1, out1) = _guarded((n // 2, oh, ow, 3)), _guarded((n // 2, oh, ow, 3))
+    (buf0, out0), (buf1, out1) = guarded((n // 2, oh, ow, 3)), guarded((n // 2, oh, ow, 3))
     st = L.fmgan_lpips_pair_input_f32(_native.fp(img), _native.fp(shift), _native.fp(scale), out0.data_ptr(),
                                       out1.data_ptr(), n // 2, h, w, y0, x0, hc, wc, f,
                                       torch.cuda.current_stream().cuda_stream)
@@ -89,7 +72,7 @@ def test_kernel_against_the_formula_bit_for_bit(shape, f, window):
     want = expected(img, shift, scale, window, f)
     assert tuple(want.shape) == (n, 3, oh, ow) and bool(torch.isfinite(want).all())
     for buf, out, ref in ((buf0, out0, want[::2]), (buf1, out1, want[1::2])):
-        assert bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[-GUARD:] == SENTINEL).all())
+        assert guards_intact(buf)
         assert bool(torch.isfinite(out).all())
         assert torch.equal(out.permute(0, 3, 1, 2), ref)
     got = _native.lpips_pair_input(img, sl.shift, sl.scale, window, f)
@@ -105,7 +88,7 @@ def test_kernel_against_interpolate(size, f):
     bit-equal is printed."""
     from op import ppl_input as PI
     x = synth.tensor(f'ppl/interp/{size}', (2, 3, size, size), dist='uniform').to(dev())
-    sl = _scaling()
+    sl = scaling()
     sl.shift.zero_()
     sl.scale.fill_(1.0)
     assert PI.pair_input_serves(x) and PI.pair_input_plan(tuple(x.shape), False) == ((0, 0, size, size), f)
@@ -128,16 +111,13 @@ _generators = {}
 def _generator(size):
     import stylegan2
     if size not in _generators:
-        _generators[size] = _load(stylegan2.Generator(size, 512, 8), 'generator', 4)
+        _generators[size] = load(stylegan2.Generator(size, 512, 8), 'generator', 4)
     return _generators[size]
 
 
 @pytest.fixture(scope='module')
 def percept():
-    import lpips
-    p = lpips.PerceptualLoss(model='net-lin', net='vgg')
-    p.load_state_dict(pc.percept_state_dict(p.state_dict()))
-    return p.to(dev()).to(memory_format=torch.channels_last)
+    return nets.percept(dev())
 
 
 @pytest.mark.parametrize('fuse', [True, False], ids=['fused', 'composite'])
@@ -156,15 +136,10 @@ def test_generator_cases_golden(name, fuse, golden, percept):
     (y0, x0, hc, wc), f = plan
     assert f == {'g64': 1, 'g512': 2, 'g512_crop': 1}[name]
     assert _native.lib().fmgan_lpips_pair_input_select(c['batch'], c['size'], c['size'], y0, x0, hc, wc, f) == f
-    seen = []
-    _native.set_observer(type('Obs', (), {'wants_paths': False, 'begin': lambda self, n, i: seen.append(n),
-                                          'end': lambda self, t: None})())
-    try:
+    with launches.observed() as rec:
         d = P.PPL_Distances(gen, percept, c['n_sample'], c['batch'], c['eps'], c['latent_dim'], dev(),
                             sampler=pc.sampler(c), crop=c['crop'], fuse=fuse)
-    finally:
-        _native.set_observer(None)
-    assert seen.count('lpips_pair_input') == (c['n_sample'] // c['batch'] if fuse else 0)
+    assert rec.count('lpips_pair_input') == (c['n_sample'] // c['batch'] if fuse else 0)
     d32, d64 = g[name + '/dist'], g[name + '/dist64']
     assert tuple(d.shape) == d64.shape and d.dtype == torch.float32
     d = d.double().cpu().numpy()

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-import ppl_cases as pc
+import nets
 import projection_cases as pj
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,17 +20,9 @@ OK, EINVAL, EUNSUPPORTED, EOVERFLOW = 0, -1, -2, -4
 FLOOR = 2e-6
 
 
-def _lib():
-    from op import _native
-    return _native.lib()
-
-
 @pytest.fixture(scope='module')
 def percept():
-    import lpips
-    p = lpips.PerceptualLoss(model='net-lin', net='vgg')
-    p.load_state_dict(pc.percept_state_dict(p.state_dict()))
-    return p
+    return nets.percept()
 
 
 # ------------------------------------------------------------------------------------------------ library and binding
@@ -39,7 +31,7 @@ def test_library_exports_the_projection_entry_points():
     argument kinds in the header's order."""
     hdr = open(os.path.join(ROOT, 'include', 'fmgan_hip.h')).read()
     hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    L = _lib()
+    L = nets.lib()
     for name in ('fmgan_projection_loss_select', 'fmgan_projection_loss_blocks', 'fmgan_projection_loss_fwd_f32',
                  'fmgan_projection_loss_bwd_f32'):
         params = re.search(r'\b' + name + r'\s*\(([^()]*)\)\s*;', hdr).group(1).split(',')
@@ -55,7 +47,7 @@ def test_select_returns_the_plan_or_the_launch_status():
     """fmgan_projection_loss_select is the launches' plan with the launch left out: f for S = 256 f, f in {1, 2, 4}, and
     for each refused argument class the status both launches return (refused before any HIP call: the pointers are
     placeholders).  fmgan_projection_loss_blocks is 128 per sample where served and 0 elsewhere."""
-    L = _lib()
+    L = nets.lib()
     fake = ctypes.c_void_p(0x1000)
     for batch in (1, 3, 8):
         for f in (1, 2, 4):
@@ -81,7 +73,7 @@ def test_null_pointers_are_einval_before_the_plan():
     """x, target, partial (forward) and x, target, k, grad_x (backward) must be there; y needs shift and scale, g_y needs
     scale; mask, y and g_y may be NULL.  The shape is one the library declines, so nothing is ever launched: a NULL
     among the required pointers still gives FMGAN_EINVAL, everything else the plan's FMGAN_EUNSUPPORTED."""
-    L = _lib()
+    L = nets.lib()
     fake = ctypes.c_void_p(0x1000)
     shape = (1, 64, 64, 1)
     # forward: x, target, mask, shift, scale, partial, y

@@ -10,38 +10,17 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import ppl_cases as pc
+import launches
+import nets
 import projection_cases as pj
 import synth
-from test_hip_train import _load
+from gpumem import dev, guarded, guards_intact
+from nets import load, scaling
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64          # guard floats on each side of an output buffer
-SENTINEL = 12345.5
 FLOOR = 2e-6
 K = 0.37            # the backward's coefficient in the kernel tests
-
-
-def dev():
-    return torch.device('cuda', 0)
-
-
-def _guarded(shape):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * GUARD,), float('nan'), dtype=torch.float32, device=dev())
-    buf[:GUARD] = SENTINEL
-    buf[GUARD + n:] = SENTINEL
-    return buf, buf[GUARD:GUARD + n].view(shape)
-
-
-def _intact(buf):
-    return bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[-GUARD:] == SENTINEL).all())
-
-
-def _scaling():
-    import lpips
-    return lpips.ScalingLayer().to(dev())
 
 
 _inputs = {}
@@ -108,7 +87,7 @@ def test_forward_kernel(batch, size):
     L = _native.lib()
     x, t, mask, _ = kernel_inputs(batch, size)
     f = size // 256
-    sl = _scaling()
+    sl = scaling()
     shift, scale = sl.shift.reshape(3), sl.scale.reshape(3)
     assert L.fmgan_projection_loss_select(batch, size, size, f) == f
     blocks = L.fmgan_projection_loss_blocks(batch, size, size, f)
@@ -119,8 +98,8 @@ def test_forward_kernel(batch, size):
         sq = (x - t) ** 2 if m is None else (x - t) ** 2 * m
         want_sum = float(sq.double().sum())
         for with_y in (True, False):
-            pbuf, partial = _guarded((blocks,))
-            ybuf, y = _guarded((batch, 256, 256, 3))
+            pbuf, partial = guarded((blocks,))
+            ybuf, y = guarded((batch, 256, 256, 3))
             runs = []
             for _ in range(2):
                 st = L.fmgan_projection_loss_fwd_f32(_native.fp(x), _native.fp(t), _native.fp(m), _native.fp(shift),
@@ -129,7 +108,7 @@ def test_forward_kernel(batch, size):
                 assert st == 0, st
                 torch.cuda.synchronize()
                 runs.append(partial.clone())
-            assert _intact(pbuf) and _intact(ybuf) and bool(torch.isfinite(partial).all())
+            assert guards_intact(pbuf) and guards_intact(ybuf) and bool(torch.isfinite(partial).all())
             assert torch.equal(runs[0], runs[1])
             got_sum = float(partial.sum(dtype=torch.float64))
             rel = abs(got_sum - want_sum) / want_sum
@@ -159,7 +138,7 @@ def _float64_grad(x, t, m, g_y, sl, dtype):
     """grad_x of K/2 * sq_sum + <y, g_y> by autograd through the composite in `dtype`."""
     from op import projection_loss as PL
     xx = x.detach().to(dtype).clone().requires_grad_(True)
-    sl = _scaling().to(dtype)
+    sl = scaling().to(dtype)
     sq, y = PL.projection_stage_composite(xx, t.to(dtype), None if m is None else m.to(dtype), sl, g_y is not None)
     outs, grads = [sq], [torch.tensor(K / 2, dtype=dtype, device=x.device)]
     if g_y is not None:
@@ -177,7 +156,7 @@ def test_backward_kernel(batch, size):
     L = _native.lib()
     x, t, mask, g_y = kernel_inputs(batch, size)
     f = size // 256
-    sl = _scaling()
+    sl = scaling()
     scale = sl.scale.reshape(3)
     k = torch.tensor([K], dtype=torch.float32, device=dev())
     stream = torch.cuda.current_stream().cuda_stream
@@ -185,13 +164,13 @@ def test_backward_kernel(batch, size):
     for m in (None, mask):
         mse = k * (x - t) if m is None else (k * (x - t)) * m
         for g in (g_y, None):
-            gbuf, grad = _guarded((batch, 3, size, size))
+            gbuf, grad = guarded((batch, 3, size, size))
             st = L.fmgan_projection_loss_bwd_f32(_native.fp(x), _native.fp(t), _native.fp(m), _native.fp(g),
                                                  _native.fp(k), _native.fp(scale), grad.data_ptr(), batch, size, size, f,
                                                  stream)
             assert st == 0, st
             torch.cuda.synchronize()
-            assert _intact(gbuf) and bool(torch.isfinite(grad).all())
+            assert guards_intact(gbuf) and bool(torch.isfinite(grad).all())
             g64 = _float64_grad(x, t, m, g, sl, torch.float64)
             g32 = _float64_grad(x, t, m, g, sl, torch.float32)
             top = float(g64.abs().max())
@@ -226,7 +205,7 @@ def test_mask_multiplies_so_a_nan_under_a_zero_of_the_mask_leaks():
     assert int(hole.sum()) > 1000
     rows, cols = torch.nonzero(hole, as_tuple=True)
     t[0, 1, rows[:50], cols[:50]] = float('nan')
-    sl = _scaling()
+    sl = scaling()
     for stage in (PL.projection_stage, PL.projection_stage_composite):
         xx = x.clone().requires_grad_(True)
         sq, y = stage(xx, t, mask, sl, True)
@@ -242,7 +221,7 @@ def test_stage_autograd_and_double_backward():
     (grad_y None); a second differentiation raises; a target that wants a gradient is not served."""
     from op import _native, projection_loss as PL
     x, t, mask, g_y = kernel_inputs(3, 512)
-    sl = _scaling()
+    sl = scaling()
     assert PL.projection_stage_serves(x, t, mask, sl) and not PL.projection_stage_serves(x, t.clone().requires_grad_(), mask, sl)
     assert not PL.projection_stage_serves(x[:, :, ::2], t[:, :, ::2], None, sl)
     xx = x.clone().requires_grad_(True)
@@ -264,26 +243,12 @@ def test_stage_autograd_and_double_backward():
 # ------------------------------------------------------------------------------------------------ the criterion
 @pytest.fixture(scope='module')
 def percept():
-    import lpips
-    p = lpips.PerceptualLoss(model='net-lin', net='vgg')
-    p.load_state_dict(pc.percept_state_dict(p.state_dict()))
-    return p.to(dev()).to(memory_format=torch.channels_last)
+    return nets.percept(dev())
 
 
-class _Launches:
-    wants_paths = False
-
-    def __init__(self):
-        self.seen = []
-
-    def begin(self, name, info):
-        self.seen.append((name, info))
-
-    def end(self, token):
-        pass
-
-    def stage(self, direction):
-        return sum(1 for n, i in self.seen if n == 'projection_loss' and i[-1] == direction)
+def _stages(rec):
+    """(forward, backward) launches of the image stage: the direction is the last item of the launch's info."""
+    return tuple(sum(1 for i in rec.infos('projection_loss') if i[-1] == direction) for direction in (0, 1))
 
 
 SERVED = ['c256_mse', 'c256_mse_mask', 'c256_lpips', 'c256_mix', 'c512_mse_mask', 'c512_lpips']
@@ -312,7 +277,6 @@ def test_criterion_cases_fused_and_composite(name, golden, percept, monkeypatch)
     is off (no trunk: both forms are deterministic); LPIPS on exactly where the reference had it on; fused, every call is one forward and one
     backward stage launch, unfused none."""
     from Evaluation.image_projection import project
-    from op import _native
     c = pj.CRITERION_BY_NAME[name]
     g = golden('projection')
     s = c['stride']
@@ -325,14 +289,10 @@ def test_criterion_cases_fused_and_composite(name, golden, percept, monkeypatch)
             k = f'{name}/{i}/'
             output, target, mask = (None if v is None else v.to(dev()) for v in pj.criterion_inputs(c, i))
             output.requires_grad_(True)
-            obs = _Launches()
-            _native.set_observer(obs)
-            try:
+            with launches.observed() as rec:
                 loss = crit(output, {'target': target, 'mask': mask})
                 loss.backward()
-            finally:
-                _native.set_observer(None)
-            assert (obs.stage(0), obs.stage(1)) == ((1, 1) if fuse else (0, 0))
+            assert _stages(rec) == ((1, 1) if fuse else (0, 0))
             assert crit.use_lpips == bool(g[k + 'use_lpips'])
             gate, ggate = _criterion_gates(c, g, i)
             err = abs(float(loss.detach()) - float(g[k + 'loss64']))
@@ -364,7 +324,7 @@ _generators = {}
 def _generator(size):
     import stylegan2
     if size not in _generators:
-        _generators[size] = _load(stylegan2.Generator(size, pj.LATENT_DIM, 2, channel_multiplier=1), 'generator', 4)
+        _generators[size] = load(stylegan2.Generator(size, pj.LATENT_DIM, 2, channel_multiplier=1), 'generator', 4)
         _generators[size].requires_grad_(False)
     return _generators[size]
 
@@ -384,23 +344,20 @@ def test_generator_trajectories(name, golden, percept):
     reference's own fp32 figure + DISPLACEMENT_FLOOR = 4.09e-3, twice the largest
     difference measured between two HIP runs of one case: 2.05e-3).  The target goes through the trunk once; g256_w runs the fused
     stage once per step and direction, g64 (upsampled) the composite."""
-    from op import _native
     from test_projection import _run_trajectory
     c = pj.TRAJECTORY_BY_NAME[name]
     g = golden('projection')
     gen = _generator(c['size'])
     trunk = []
     hook = percept.net.net.register_forward_hook(lambda m, i, o: trunk.append(1))
-    obs = _Launches()
-    _native.set_observer(obs)
     try:
-        history, last, disp, crit = _run_trajectory(c, gen, percept, device=dev())
+        with launches.observed() as rec:
+            history, last, disp, crit = _run_trajectory(c, gen, percept, device=dev())
     finally:
-        _native.set_observer(None)
         hook.remove()
     steps = c['iterations'] + 1
     assert len(trunk) == steps + 1
-    assert (obs.stage(0), obs.stage(1)) == ((steps, steps) if c['size'] == 256 else (0, 0))
+    assert _stages(rec) == ((steps, steps) if c['size'] == 256 else (0, 0))
     losses = np.array([float(l) for _, l in history])
     l32, l64 = g[name + '/loss'], g[name + '/loss64']
     gate = 4 * np.abs(l32 - l64) + FLOOR * np.abs(l64)

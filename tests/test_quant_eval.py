@@ -2,21 +2,15 @@
 identity similarity against the reference's values, the loop logic of the two score functions on stand-in networks, the
 host logic of the library's two entry points, and the register budget of the kernel."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import codeobj
 import quant_eval_cases as qc
 import synth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, '3d-fm-gan_amd', 'csrc', 'libfmgan_hip.so')
-LLVM = '/opt/rocm/lib/llvm/bin'
 
 
 def _face_model():
@@ -258,30 +252,9 @@ def test_face_input_host_logic():
 # ------------------------------------------------------------------------------------------------ register budget
 @pytest.fixture(scope='module')
 def kernels(tmp_path_factory):
-    objdump, readelf = os.path.join(LLVM, 'llvm-objdump'), os.path.join(LLVM, 'llvm-readelf')
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip('llvm-objdump / llvm-readelf not found')
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    d = tmp_path_factory.mktemp('codeobj')
-    shutil.copy(LIB, d / 'lib.so')
-    subprocess.run([objdump, '--offloading', str(d / 'lib.so')], check=True, capture_output=True, cwd=d)
-    out = {}
-    for f in sorted(os.listdir(d)):
-        if not f.endswith('gfx950'):
-            continue
-        notes = subprocess.run([readelf, '--notes', str(d / f)], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split('- .agpr_count')[1:]:
-            name = re.search(r'\.name:\s+(\S+)', blk).group(1)
-            if 'face_input_f32' not in name:
-                continue
-
-            def num(key):
-                return int(re.search(key + r':\s+(\d+)', blk).group(1))
-            out[name] = {'vgpr': num(r'\.vgpr_count'), 'vgpr_spill': num(r'\.vgpr_spill_count'),
-                         'sgpr_spill': num(r'\.sgpr_spill_count'), 'scratch': num(r'\.private_segment_fixed_size')}
-    return out
+    """The notes of the face-input kernels; codeobj.kernel_notes builds the library first if a fresh checkout has none."""
+    notes = codeobj.kernel_notes(tmp_path_factory.mktemp('codeobj'))
+    return {name: k for name, k in notes.items() if 'face_input_f32' in name}
 
 
 def test_face_input_kernel_budget(kernels):

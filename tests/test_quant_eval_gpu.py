@@ -8,16 +8,14 @@ import torch
 
 import quant_eval_cases as qc
 import synth
-from test_hip_train import PinNoise, build_nets, train_args
+from gpumem import dev
+from nets import PinNoise
+from test_hip_train import build_nets, train_args
 
 pytestmark = pytest.mark.gpu
 
 # Floors (absolute) of the cosine-similarity and stand-in-distance gates: see test_scores_golden.
 COS_FLOOR, DIST_FLOOR = 5e-7, 6.6e-5
-
-
-def dev():
-    return torch.device('cuda', 0)
 
 
 @pytest.fixture(scope='module')

@@ -12,21 +12,11 @@ import torch
 import cases
 import reanimate_cases
 import synth
+from gpumem import dev, guarded, guards_intact
+from nets import encoders, load
 from parity import img_close
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64          # guard floats on each side of an output buffer
-SENTINEL = 12345.5
-
-
-def dev():
-    return torch.device('cuda', 0)
-
-
-def _load(module, kind, seed):
-    module.load_state_dict(synth.state_dict(kind, module.state_dict(), seed=seed))
-    return module.to(dev()).eval()
 
 
 # ------------------------------------------------------------------------------------------------ bank kernels alone
@@ -49,17 +39,6 @@ def _bank_layers(style_dim, slicing):
     return layers
 
 
-def _guarded(n):
-    buf = torch.full((n + 2 * GUARD,), float('nan'), dtype=torch.float32, device=dev())
-    buf[:GUARD] = SENTINEL
-    buf[GUARD + n:] = SENTINEL
-    return buf, buf[GUARD:GUARD + n]
-
-
-def _guards_intact(buf, n):
-    return bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[GUARD + n:] == SENTINEL).all())
-
-
 @pytest.mark.parametrize('slicing', ['mixed', 'all', 'none'])
 @pytest.mark.parametrize('shared', [True, False], ids=['P1', 'PT'])
 @pytest.mark.parametrize('T', [1, 3, 65])
@@ -78,15 +57,15 @@ def test_bank_kernels_equal_the_per_layer_launches(style_dim, T, shared, slicing
     wp = synth.tensor(f'bank/wp/{T}', (1 if shared else T, n_styles, style_dim)).to(dev())
     ns, nd = T * table.style_floats, T * table.demod_floats
     assert table.style_floats == sum(c for c, _ in BANK_SHAPES) + 64 and table.demod_floats == sum(o for _, o in BANK_SHAPES)
-    sbuf, styles = _guarded(ns)
-    dbuf, demod = _guarded(nd)
+    sbuf, styles = guarded(ns)
+    dbuf, demod = guarded(nd)
     table.run(w, wp, styles, demod)
     first = (styles.clone(), demod.clone())
-    assert _guards_intact(sbuf, ns) and _guards_intact(dbuf, nd)
+    assert guards_intact(sbuf) and guards_intact(dbuf)
     assert not torch.isnan(styles).any() and not torch.isnan(demod).any()
     table.run(w, wp, styles, demod)
     assert torch.equal(styles, first[0]) and torch.equal(demod, first[1])
-    assert _guards_intact(sbuf, ns) and _guards_intact(dbuf, nd)
+    assert guards_intact(sbuf) and guards_intact(dbuf)
     views = table.views(T, styles, demod)
     for l, (s, d) in zip(layers, views):
         x = (w * wp[:, l['col']]) if l['sliced'] else w
@@ -108,7 +87,7 @@ def test_bank_kernels_equal_the_per_layer_launches(style_dim, T, shared, slicing
 def _narrow_g():
     import stylegan2
     c = cases.GENERATOR_CASES[0]
-    return _load(stylegan2.Generator(c['size'], 512, c['n_mlp'], generator_net_shape=c['shape']), 'generator', 4)
+    return load(stylegan2.Generator(c['size'], 512, c['n_mlp'], generator_net_shape=c['shape']), 'generator', 4)
 
 
 def _codes(G, T, P, cin0, tag):
@@ -213,7 +192,7 @@ def test_generator_comod_bits_full_256():
     """Generator(256, 512, 8) at T = 2: a Winograd layer (16^2..128^2 x >= 256 channels) and the fused RGB epilogue at
     the last resolution are on the path."""
     import stylegan2
-    G = _load(stylegan2.Generator(256, 512, 8), 'generator', 4)
+    G = load(stylegan2.Generator(256, 512, 8), 'generator', 4)
     with torch.no_grad():
         assert stylegan2.winograd_pays(2, 512, 512, 32, 32)
         assert G.convs[-1].rgb_fusable((2, 0, 256, 256), torch.empty(1, device=dev()))
@@ -275,21 +254,10 @@ def test_comod_reads_live_weights_and_survives_deepcopy():
 
 
 # ------------------------------------------------------------------------------------------------ reference parity
-def _encoders(n_styles):
-    import types
-    import resnet_encoder
-    from psp_encoder_model.encoders import psp_encoders
-    e_tsr = _load(resnet_encoder.resnet18(tensor_encoding=True, tensor_transform=False), 'resnet', 5)
-    e_w = _load(resnet_encoder.resnet18(tensor_encoding=False, tensor_transform=False), 'resnet', 6)
-    e_wp = _load(psp_encoders.GradualStyleEncoder(18, 'ir_se', types.SimpleNamespace(input_nc=3, n_styles=n_styles)),
-                 'psp', 7)
-    return e_tsr, e_w, e_wp
-
-
 @pytest.fixture(scope='module')
 def nets256():
     import stylegan2
-    return _encoders(14) + (_load(stylegan2.Generator(256, 512, 8), 'generator', 4),)
+    return encoders(14) + (load(stylegan2.Generator(256, 512, 8), 'generator', 4),)
 
 
 def _gate(img, g, c):

@@ -10,21 +10,17 @@ import torch
 
 import reanimate_cases
 import synth
+from nets import lib
 from test_oracle_golden import _img_close, _sd_from_manifest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ('fmgan_style_bank_entry_bytes', 'fmgan_style_bank_f32', 'fmgan_demod_bank_f32')
 
 
-def _lib():
-    from op import _native
-    return _native.lib()
-
-
 def test_style_bank_symbols_are_declared_and_exported():
     hdr = open(os.path.join(ROOT, 'include', 'fmgan_hip.h')).read()
     hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    L = _lib()
+    L = lib()
     for n in SYMBOLS:
         assert re.search(r'\b%s\s*\(' % n, hdr), f'{n} is not declared in include/fmgan_hip.h'
         assert hasattr(L, n), f'{n} is not exported'
@@ -35,14 +31,14 @@ def test_style_bank_symbols_are_declared_and_exported():
 
 def test_style_bank_entry_layout_is_pinned():
     from op import style_bank
-    assert _lib().fmgan_style_bank_entry_bytes() == style_bank._ENTRY.itemsize
+    assert lib().fmgan_style_bank_entry_bytes() == style_bank._ENTRY.itemsize
     style_bank._check_layout()
     # pointers first, then the 64-bit offsets, then the 32-bit fields: no padding anywhere
     assert style_bank._ENTRY.itemsize == sum(style_bank._ENTRY[n].itemsize for n in style_bank._ENTRY.names)
 
 
 def test_style_bank_refuses_bad_arguments_without_gpu():
-    L = _lib()
+    L = lib()
     p = 4096    # any non-null address: every check below fails before a pointer is used or a HIP call is made
     ok = dict(table=p, n=3, w=p, wplus=p, wb=1, batch=3, d=512, out=p)
 
