@@ -26,7 +26,7 @@ Reference behaviour kept on purpose:
     and never uses it (its loop passes batch_size to every batch);
   * Get_PPL_Score does not divide by eps^2 (only the script half does: normalize=True);
   * n_sample < batch_size is a ValueError here (no batch at all: the reference fails inside numpy's percentile).
-Out of scope: Z-space sampling with slerp, FID, image projection.
+Out of scope: Z-space sampling with slerp (FID: Evaluation/fid.py; image projection: Evaluation/image_projection/).
 """
 import numpy as np
 import torch

@@ -15,9 +15,12 @@ What is different, on purpose:
     Forward_Inference_Reanimate, and computes the photo's identity feature once per batch; the reference runs all three
     encoders for every render;
   * only the 3-encoder scheme is provided (ValueError for the 2-encoder tuple, as Reanimate_Frames);
-  * FID needs Inception weights and an FFHQ statistics file, the heat-map and landmark scores need the third-party
-    `face_alignment` package: none of them is shipped.  `inception_model` and `fa_model` must be None, and those three
-    entries of the tuple are None.
+  * the FID of the edited outputs is computed when the caller brings both an `inception_model` (Evaluation/inception.py
+    with loaded weights) and `fid_stats` (the real images' statistics: a dict or the path of a pickle with `mean` and
+    `cov`); neither is shipped, and an `inception_model` without `fid_stats` is refused.  The features of a batch's outputs
+    go into running moments on the device (op/fid_stats.py);
+  * the heat-map and landmark scores need the third-party `face_alignment` package, which is absent: `fa_model` must be
+    None, and those two entries of the tuple are None.
 EVAL_FUSE = False (or FMGAN_NO_EVAL_FUSE=1) keeps the composite metric stage and the reference's loop structure
 (Forward_Inference_3_Encoder per render, target features per call): the baseline of profiles/quant_eval.md.
 """
@@ -28,9 +31,13 @@ import torch
 import torch.nn.functional as F
 
 from op.eval_scores import face_input
+from op.fid_stats import Feature_Statistics
 from op.face_region import face_region_scores
 from Util.network_util import (Encode_Photo, Forward_Inference_3_Encoder, Forward_Inference_Reanimate,
                                MODULATION_ENCODING)
+
+from . import fid
+from .calc_inception import features_of
 
 EVAL_FUSE = os.environ.get('FMGAN_NO_EVAL_FUSE', '0') != '1'
 
@@ -117,28 +124,31 @@ class _NoiseArgs:
 
 
 def Edit_Scores(eval_loader, device, generative_model, eval_models, info_print=False, tsr_encode=MODULATION_ENCODING[1],
-                sliced_layer=None, use_tanh=False, noise=None, randomize_noise=True):
+                sliced_layer=None, use_tanh=False, noise=None, randomize_noise=True, fid_stats=None):
     """Per-sample editing scores as device tensors: dict(cos, face_diff).  eval_loader yields [photo, render_1, ...,
-    render_n] batches; eval_models = (face_rec_model, inception_model, fa_model) with the last two None.  Order of both
+    render_n] batches; eval_models = (face_rec_model, inception_model, fa_model) with fa_model None.  Order of both
     lists: batch by batch, render-major within a batch (all samples of render 1, then render 2, ...), as the reference
-    appends them.  noise / randomize_noise go to the generator (its own defaults when not given)."""
+    appends them.  noise / randomize_noise go to the generator (its own defaults when not given).  With an inception_model
+    and fid_stats (the real statistics) the dict also holds `fid_state`: the Feature_Statistics of every output's features
+    (a batch's outputs concatenated, one pass through the model)."""
     E_Tsr, E_W, E_W_Plus, g_ema = _three_encoders(generative_model)
     face_rec_model, inception_model, fa_model = eval_models
-    if inception_model is not None:
-        raise ValueError('Edit_Scores: inception_model must be None: FID needs Inception weights and the FFHQ statistics '
-                         'file, which are not shipped')
+    if inception_model is not None and fid_stats is None:
+        raise ValueError('Edit_Scores: inception_model without fid_stats: FID needs Inception weights and the FFHQ '
+                         'statistics file, which are not shipped; pass both, or inception_model=None')
     if fa_model is not None:
         raise ValueError('Edit_Scores: fa_model must be None: the heat-map and landmark scores need the face_alignment '
                          'package, which is absent')
     if tsr_encode not in MODULATION_ENCODING:
         raise ValueError(f'tsr_encode must be one of {MODULATION_ENCODING}')
-    cos, face_diff = [], []
+    cos, face_diff, fid_state = [], [], None
     with torch.no_grad():
         for idx, img_tensor_list in enumerate(eval_loader):
             if info_print:
                 print('Batch: ' + str(idx))
             p_input = img_tensor_list[0].to(device)
             renders = [r.to(device) for r in img_tensor_list[1:]]
+            outputs = []
             if EVAL_FUSE:
                 code = Encode_Photo(p_input, E_Tsr, E_W_Plus, tsr_encode)
                 target_feature = face_rec_model(_gray(p_input))
@@ -148,6 +158,7 @@ def Edit_Scores(eval_loader, device, generative_model, eval_models, info_print=F
                     _same_size('render and output', r_input, g_output)
                     face_diff.append(face_region_scores(r_input, g_output))
                     cos.append(F.cosine_similarity(face_rec_model(_gray(g_output)), target_feature))
+                    outputs.append(g_output)
             else:
                 g = g_ema if noise is None and randomize_noise else _NoiseArgs(g_ema, noise, randomize_noise)
                 g_output_list = []
@@ -158,15 +169,31 @@ def Edit_Scores(eval_loader, device, generative_model, eval_models, info_print=F
                     g_output_list.append(g_output)
                     face_diff.append(face_region_scores(r_input, g_output))
                 cos += Compute_Face_Identity_Similarity(g_output_list, p_input, face_rec_model)
+                outputs = g_output_list
+            if inception_model is not None and outputs:
+                feat = features_of(inception_model, torch.cat(outputs), fid.FID_FUSE)
+                if fid_state is None:
+                    fid_state = Feature_Statistics(feat.shape[1], feat.device, fuse=fid.FID_FUSE)
+                fid_state.update(feat)
     if not cos:
         raise ValueError('Edit_Scores: the loader yielded no render')
-    return {'cos': torch.cat(cos), 'face_diff': torch.cat(face_diff)}
+    scores = {'cos': torch.cat(cos), 'face_diff': torch.cat(face_diff)}
+    if fid_state is not None:
+        scores['fid_state'] = fid_state
+    return scores
 
 
 def Get_Edit_Score(eval_loader, device, generative_model, eval_models, info_print=False, **kwargs):
     """(mean cosine similarity, fid, heat-map score, landmark score, mean face difference): the reference's 5-tuple, with
-    None for the three scores this build does not provide."""
+    None for the scores not computed: the heat-map and landmark scores always, the FID unless eval_models brings an
+    inception_model and `fid_stats` (the real images' statistics: a dict or a pickle path with `mean` / `cov`) is given."""
+    real = None
+    if eval_models[1] is not None and kwargs.get('fid_stats') is not None:
+        real = fid.load_real_stats(kwargs['fid_stats'])          # before the loop: a wrong path fails at once
     s = Edit_Scores(eval_loader, device, generative_model, eval_models, info_print, **kwargs)
     if info_print:
         print('Cosine Similarity Len: ' + str(len(s['cos'])) + ' FaceDiff Len: ' + str(len(s['face_diff'])))
-    return _mean(s['cos']), None, None, None, _mean(s['face_diff'])
+    fid_score = None
+    if 'fid_state' in s:
+        fid_score = fid.calc_fid(*s['fid_state'].finish(), *real)
+    return _mean(s['cos']), fid_score, None, None, _mean(s['face_diff'])

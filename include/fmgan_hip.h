@@ -296,6 +296,57 @@ int fmgan_projection_loss_bwd_f32(const float *x, const float *target, const flo
                                   void *stream);
 
 /*
+ * Running feature statistics of the FID (Evaluation/fid.py; op/fid_stats.py): first and second moments of the Inception
+ * features, accumulated on the device in float64, batch by batch; doubles travel by pointer.
+ *   State over d features: shift [d] f64 (fixed before the first update), sum [d] f64, outer [d, d] f64 row-major of which
+ *   only the elements with i <= j are meaningful (the others are never read or written); the sample count is the caller's.
+ *   update: feat [b, d] contiguous f32 row-major;  y[r, c] = (double)feat[r, c] - shift[c]  (one rounding),
+ *             sum[c]      = sum[c]      + ((g0 + g1) + g2) + g3,  g_k = y[k, c] + y[k+4, c] + y[k+8, c] + ... in row order,
+ *             outer[i][j] = outer[i][j] + P_ij  for i <= j,       P_ij = sum_r y[r, i] * y[r, j] on the fp64 matrix
+ *           instruction (v_mfma_f64_16x16x4_f64): rows in order, four per instruction, starting from 0; rows beyond b are
+ *           exact zeros.  Accumulation is in place; every element is read, added to and written by one lane: no atomics,
+ *           and the bits do not depend on the grid.  Only 16 x 16 tiles on or above the diagonal are computed.
+ *   finish: n the number of samples accumulated;  mean[i] = shift[i] + sum[i] / n;
+ *           cov[i][j] = cov[j][i] = (outer[i][j] - (sum[i] * sum[j]) / n) / (n - 1)  for i <= j, in this order, no fused
+ *           multiply-add, n converted to double: cov [d, d] f64 is exactly symmetric.  Any d.
+ * No allocation, no synchronisation, no global state; the kernels run on `stream`.  Naturally aligned pointers suffice.
+ * fmgan_fid_stats_select is update's plan with the launch left out: the positive kernel id 1 exactly when the launch with
+ * these arguments runs, otherwise the status it returns: FMGAN_EINVAL for b <= 0 or d <= 0 (the launch also for a NULL
+ * pointer), FMGAN_EUNSUPPORTED for d % 16 != 0 (the caller then evaluates the composite), FMGAN_EOVERFLOW for d > 2^21
+ * (block indices are ints, element offsets 64-bit).  finish: FMGAN_EINVAL for n < 2, d <= 0 or a NULL pointer,
+ * FMGAN_EOVERFLOW for d > 16 * 65535.
+ */
+int fmgan_fid_stats_select(int b, int d);
+int fmgan_fid_stats_update_f32(const float *feat, const double *shift, double *sum, double *outer, int b, int d,
+                               void *stream);
+int fmgan_fid_stats_finish_f64(const double *sum, const double *outer, const double *shift, long long n, double *mean,
+                               double *cov, int d, void *stream);
+
+/*
+ * Input stage of the FID's Inception network (Evaluation/inception.py): from the Generator's image batch to the
+ * channels_last input of the first convolution, one launch, only tap pixels read.
+ *   img [batch, 3, s, s] contiguous f32 NCHW, s in {256, 512, 1024, 299};  out [batch, 299, 299, 3] dense: the NHWC storage
+ *   of a [batch, 3, 299, 299] channels_last tensor.
+ *   v = bilinear interpolation to 299 x 299 with align_corners = false by aten's fp32 rule, per axis and output index d:
+ *         scale = (float)s / 299.f;  src = max(fmaf(scale, d + 0.5f, -0.5f), 0.f)  (ONE rounding: aten's kernels are
+ *         compiled with the multiply and subtract contracted);  i0 = (int)src;  i1 = i0 + (i0 < s - 1);
+ *         l1 = src - i0;  l0 = 1.f - l1;
+ *       with (y0, y1, h0, h1) those of the output row and (x0, x1, w0, w1) those of the output column,
+ *         v = h0 * (w0 * img[y0, x0] + w1 * img[y0, x1]) + h1 * (w0 * img[y1, x0] + w1 * img[y1, x1]),
+ *       every product and sum rounded, in exactly this association, no fused multiply-add.  A tap of weight 0 is read and
+ *       multiplied (its NaN reaches the output), as in aten.  s = 299: v = img, nothing is multiplied.
+ *   out[n, y, x, c] = normalize ? 2 * v - 1 : v  (2 * v is exact: one rounding).
+ * No allocation, no synchronisation, no global state; the kernel runs on `stream`.  Dword-aligned pointers suffice.
+ * fmgan_inception_input_select is the launch's plan with the launch left out: a positive kernel id exactly when the launch
+ * with these arguments runs that kernel (1: resampling, 2: s = 299, layout change only), otherwise the status the launch
+ * returns: FMGAN_EINVAL for a non-positive argument (the launch also for a NULL pointer), FMGAN_EUNSUPPORTED for h != w
+ * or h outside {256, 512, 1024, 299} (the caller then evaluates the composite), FMGAN_EOVERFLOW when batch * blocks per
+ * sample exceeds the grid's 2^31 - 1 (element offsets are 64-bit).
+ */
+int fmgan_inception_input_select(int batch, int h, int w);
+int fmgan_inception_input_f32(const float *img, float *out, int batch, int h, int w, int normalize, void *stream);
+
+/*
  * Inference glue of the pSp encoder's IR / IR-SE units (psp_encoder_model/encoders/helpers.py): what runs between the
  * MIOpen convolutions of a unit.  All tensors f32 in NHWC storage ([batch, h, w, channels]); a BatchNorm2d in eval mode is
  * given as its four [channels] vectors and eps and is evaluated in-kernel on every launch as
