@@ -2,11 +2,21 @@
 //   in : uint8 HWC image batch -> float CHW in [-1,1]   == transforms.ToTensor() + Normalize(0.5, 0.5)
 //        (train_3_encoder.py:233-239; Resize(size) is the identity for the 256^2 datasets the reference uses)
 //   out: float CHW in [-1,1] -> uint8 HWC               == tensor2im (Evaluation/visual_eval.py:24-38)
+//        the same into square slots of uint8 canvases (sample sheets, video triptychs): tiles_to_canvas_k below
 // Both are HBM-bound layout changes: one pass, 3 channels gathered/scattered per pixel, rounding identical to
 // the reference's numpy/torch arithmetic so the tests can demand bit equality.
-#include "common.h"
+#include <climits>
+
+#include "lpips_input.h"
 
 namespace {
+
+// (uint8)((clip(v, -1, 1) + cent) * factor): tensor2im's arithmetic (astype(np.uint8): truncation), the one definition
+__device__ __forceinline__ unsigned int f32_to_u8(float v, float cent, float factor) {
+  v = fminf(fmaxf(v, -1.0f), 1.0f);
+  v = __fmul_rn(__fadd_rn(v, cent), factor);
+  return (unsigned int)(unsigned char)(int)v;
+}
 
 // out[b,c,y,x] = ((in[b,y,x,c] / 255) - mean) / std   with the reference's operation order (div, sub, div)
 __global__ __launch_bounds__(256) void u8hwc_to_f32chw(const unsigned char* __restrict__ in, float* __restrict__ out,
@@ -34,10 +44,7 @@ __global__ __launch_bounds__(256) void f32chw_to_u8hwc(const float* __restrict__
     unsigned char* dst = out + p * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      float v = src[(long long)c * hw];
-      v = fminf(fmaxf(v, -1.0f), 1.0f);
-      v = __fmul_rn(__fadd_rn(v, cent), factor);
-      dst[c] = (unsigned char)(int)v;
+      dst[c] = (unsigned char)f32_to_u8(src[(long long)c * hw], cent, factor);
     }
   }
 }
@@ -188,6 +195,97 @@ __global__ __launch_bounds__(256) void resize_bilinear_u8_fast(const unsigned ch
   }
 }
 
+// ---- float tiles into uint8 canvases: canvas[slot.canvas, y0 + y, x0 + x, c] = f32_to_u8(v), v the tile's pixel (F = 1)
+// or its bilinear reduction by F = 2 / 4 (lpips_input.h: the four centre taps of the F x F cell, columns first).
+// A lane owns CV_PIX = 4 adjacent output pixels of one row of one tile: 12 contiguous canvas bytes.  Its source per
+// channel and tap row is 4 / 8 contiguous floats at F = 1 / 2 and four 2-float pieces at F = 4 (dword alignment only:
+// rows of `src` floats); lanes of a wave own consecutive units of a row, so their loads cover one contiguous run.
+// The canvas row pitch 3 * canvas_w and x0 are arbitrary: where the 12 bytes start inside a dword is known per lane at
+// run time only.  cv_store puts the bytes up to the next dword boundary one by one, the whole dwords between as dwords
+// (re-aligned with a 64-bit shift) and the rest one by one; two lanes never write the same byte, and a dword store
+// lies wholly inside its lane's 12 bytes.  VEC (tile % 4 == 0): no edge path; otherwise loads are guarded per pixel
+// and the last unit of a row stores its 3 / 6 / 9 bytes singly.  A slot that does not lie inside its canvas is skipped.
+constexpr int CV_THREADS = 256;
+constexpr int CV_PIX = LPIPS_IN_PIX;
+typedef unsigned int cv_u32 __attribute__((may_alias));
+
+__device__ __forceinline__ void cv_store(unsigned char* dst, const unsigned int (&w)[3], int nbytes) {
+  const int mis = (int)(reinterpret_cast<uintptr_t>(dst) & 3);
+  if (nbytes == 3 * CV_PIX) {
+    if (mis == 0) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) reinterpret_cast<cv_u32*>(dst)[q] = w[q];
+      return;
+    }
+    const int lead = 4 - mis;                               // 1..3 bytes up to the boundary, then 8, then `mis`
+    for (int b = 0; b < lead; ++b) dst[b] = (unsigned char)(w[0] >> (8 * b));
+    const unsigned long long lo = ((unsigned long long)w[1] << 32) | w[0], hi = ((unsigned long long)w[2] << 32) | w[1];
+    cv_u32* mid = reinterpret_cast<cv_u32*>(dst + lead);
+    mid[0] = (unsigned int)(lo >> (8 * lead));
+    mid[1] = (unsigned int)(hi >> (8 * lead));
+    for (int b = 0; b < mis; ++b) dst[lead + 8 + b] = (unsigned char)(w[2] >> (8 * (lead + b)));
+    return;
+  }
+  for (int b = 0; b < nbytes; ++b) dst[b] = (unsigned char)(w[b >> 2] >> (8 * (b & 3)));
+}
+
+template <int F, bool VEC>
+__global__ __launch_bounds__(CV_THREADS) void tiles_to_canvas_k(const float* __restrict__ in, unsigned char* canvas,
+                                                                const int* __restrict__ slots, int src, int tile,
+                                                                int n_canvas, int canvas_h, int canvas_w, int units_x,
+                                                                int units, int gx, float cent, float factor) {
+  constexpr int O = lpips_in_first_tap(F);
+  const int i = blockIdx.x / gx, blk = blockIdx.x % gx;
+  const int u = blk * CV_THREADS + threadIdx.x;
+  if (u >= units) return;
+  const int cv = slots[3 * i], y0 = slots[3 * i + 1], x0 = slots[3 * i + 2];
+  if (cv < 0 || cv >= n_canvas || y0 < 0 || x0 < 0 || y0 > canvas_h - tile || x0 > canvas_w - tile) return;
+  const int oy = u / units_x, ox = (u % units_x) * CV_PIX;
+  const int valid = VEC ? CV_PIX : min(CV_PIX, tile - ox);
+  const long long hw = (long long)src * src;
+  const float* s = in + (long long)i * 3 * hw + (long long)(F * oy + O) * src + (F * ox + O);
+  float v[3][CV_PIX];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* r0 = s + c * hw;
+    const float* r1 = r0 + src;                      // read at F > 1 only
+    if constexpr (VEC && F == 1) {
+      lpips_in_load<CV_PIX>(r0, v[c]);
+    } else if constexpr (VEC && F == 2) {
+      float a[F * CV_PIX], b[F * CV_PIX];
+      lpips_in_load<F * CV_PIX>(r0, a);
+      lpips_in_load<F * CV_PIX>(r1, b);
+#pragma unroll
+      for (int j = 0; j < CV_PIX; ++j) v[c][j] = lpips_in_quad(a[F * j], a[F * j + 1], b[F * j], b[F * j + 1]);
+    } else if constexpr (VEC) {
+      f32x2_u a[CV_PIX], b[CV_PIX];
+#pragma unroll
+      for (int j = 0; j < CV_PIX; ++j) {
+        a[j] = *reinterpret_cast<const f32x2_u*>(r0 + F * j);
+        b[j] = *reinterpret_cast<const f32x2_u*>(r1 + F * j);
+      }
+#pragma unroll
+      for (int j = 0; j < CV_PIX; ++j) v[c][j] = lpips_in_quad(a[j].x, a[j].y, b[j].x, b[j].y);
+    } else {
+#pragma unroll
+      for (int j = 0; j < CV_PIX; ++j) {
+        v[c][j] = 0.f;
+        if (j < valid) v[c][j] = F == 1 ? r0[j] : lpips_in_quad(r0[F * j], r0[F * j + 1], r1[F * j], r1[F * j + 1]);
+      }
+    }
+  }
+  unsigned int w[3] = {0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < CV_PIX; ++j)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int b = 3 * j + c;
+      w[b >> 2] |= f32_to_u8(v[c][j], cent, factor) << (8 * (b & 3));
+    }
+  unsigned char* dst = canvas + (((long long)cv * canvas_h + y0 + oy) * canvas_w + x0 + ox) * 3;
+  cv_store(dst, w, 3 * valid);
+}
+
 inline unsigned grid_for(long long n) {
   long long b = (n + 255) / 256;
   const long long cap = (long long)FMGAN_NUM_CU * 32;
@@ -253,5 +351,33 @@ extern "C" int fmgan_tensor_to_images(const float* in, unsigned char* out, int b
   const long long pixels = (long long)batch * h * w;
   hipLaunchKernelGGL(f32chw_to_u8hwc, dim3(grid_for(pixels)), dim3(256), 0, (hipStream_t)stream, in, out, pixels, h * w,
                      cent, factor);
+  return fmgan_check_launch();
+}
+
+extern "C" int fmgan_tiles_to_canvas(const float* in, unsigned char* canvas, const int* slots, int n, int src, int tile,
+                                     int n_canvas, int canvas_h, int canvas_w, float cent, float factor, void* stream) {
+  if (n < 0 || src <= 0 || tile <= 0 || n_canvas <= 0 || canvas_h <= 0 || canvas_w <= 0) return FMGAN_EINVAL;
+  const int f = src / tile;
+  if (src % tile != 0 || !(f == 1 || f == 2 || f == 4)) return FMGAN_EINVAL;
+  if (n == 0) return FMGAN_OK;
+  if (!in || !canvas || !slots) return FMGAN_EINVAL;
+  // element and byte offsets are long long; pixel, unit and block indices are ints
+  const long long hw = (long long)src * src;
+  if (hw > 0x7fffffffLL - CV_THREADS * CV_PIX) return FMGAN_EOVERFLOW;
+  if (3 * hw > LLONG_MAX / n) return FMGAN_EOVERFLOW;
+  if ((long long)canvas_h * canvas_w > LLONG_MAX / 3 / n_canvas) return FMGAN_EOVERFLOW;
+  const int units_x = (tile + CV_PIX - 1) / CV_PIX, units = tile * units_x;
+  const int gx = (units + CV_THREADS - 1) / CV_THREADS;
+  if ((long long)gx * n > 0x7fffffffLL) return FMGAN_EOVERFLOW;        // grid.x
+  const dim3 grid((unsigned)((long long)gx * n)), block(CV_THREADS);
+  hipStream_t s = (hipStream_t)stream;
+#define CV_GO(F, VEC)                                                                                              \
+  hipLaunchKernelGGL((tiles_to_canvas_k<F, VEC>), grid, block, 0, s, in, canvas, slots, src, tile, n_canvas, canvas_h, \
+                     canvas_w, units_x, units, gx, cent, factor)
+  const bool vec = tile % CV_PIX == 0;
+  if (f == 1) { if (vec) CV_GO(1, true); else CV_GO(1, false); }
+  else if (f == 2) { if (vec) CV_GO(2, true); else CV_GO(2, false); }
+  else { if (vec) CV_GO(4, true); else CV_GO(4, false); }
+#undef CV_GO
   return fmgan_check_launch();
 }

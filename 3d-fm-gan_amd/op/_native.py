@@ -117,6 +117,7 @@ def lib():
     _sig(L.fmgan_resize_plan, [i] * 4 + [vp, ll])
     _sig(L.fmgan_resize_bilinear_u8, [vp] * 4 + [i] * 5 + [f, f, vp])
     _sig(L.fmgan_tensor_to_images, [vp, vp, i, i, i, f, f, vp])
+    _sig(L.fmgan_tiles_to_canvas, [vp, vp, ctypes.POINTER(i)] + [i] * 6 + [f, f, vp])
     _sig(L.fmgan_torgb_f32, [vp] * 6 + [i] * 4 + [f, vp])
     _sig(L.fmgan_torgb_backward_splits, [i] * 3)
     _sig(L.fmgan_torgb_backward_f32, [vp] * 6 + [i] * 4 + [f, vp])
@@ -1234,3 +1235,29 @@ def tensor_to_images(tensor, cent=1.0, factor=255.0 / 2.0):
     with on_device(x) as stream:
         check(lib().fmgan_tensor_to_images(ptr(x), ptr(out), b, h, w, float(cent), float(factor), stream), 'tensor_to_images')
     return out
+
+
+def tiles_to_canvas(src, canvas, slots, tile, cent=1.0, factor=255.0 / 2.0):
+    """float32 [n,3,s,s] tiles into square slots of the uint8 canvas batch [C,H,W,3], in place, one launch
+    (csrc/image_io.hip): slots int32 [n,3] ON src's DEVICE, one (canvas, y0, x0) per tile; s = tile, 2*tile or 4*tile (the
+    tile is reduced by aten's bilinear rule).  The raw entry: op/canvas.py checks the layout on the host beforehand; the
+    kernel skips a slot that does not lie inside its canvas.  Tensors of another dtype, device or layout are refused."""
+    if src.ndim != 4 or src.shape[1] != 3 or src.shape[2] != src.shape[3] or canvas.ndim != 4 or canvas.shape[3] != 3 \
+            or slots.ndim != 2 or tuple(slots.shape) != (src.shape[0], 3):
+        raise ValueError(f'tiles_to_canvas: src {tuple(src.shape)}, canvas {tuple(canvas.shape)}, slots '
+                         f'{tuple(slots.shape)}: expected [n, 3, s, s], [C, H, W, 3] and [n, 3]')
+    require_f32_gpu('tiles_to_canvas', ((src, 'src'),))
+    for t, name, dtype in ((canvas, 'canvas', torch.uint8), (slots, 'slots', torch.int32)):
+        require_gpu(t, name)
+        if t.dtype != dtype or not t.is_contiguous() or t.device != src.device:
+            raise RuntimeError(f'tiles_to_canvas: {name} must be a contiguous {dtype} tensor on src\'s device, got '
+                               f'{t.dtype} on {t.device} with strides {t.stride()}')
+    n, _, s, _ = src.shape
+    nc, ch, cw, _ = canvas.shape
+    if n == 0:
+        return canvas
+    with launching(src, 'tiles_to_canvas', (n, s, int(tile), nc, ch, cw)) as stream:
+        st = lib().fmgan_tiles_to_canvas(fp(src), ptr(canvas), ctypes.cast(slots.data_ptr(), ctypes.POINTER(ctypes.c_int)),
+                                         n, s, int(tile), nc, ch, cw, float(cent), float(factor), stream)
+    check(st, 'tiles_to_canvas')
+    return canvas

@@ -46,14 +46,17 @@ from Util.training_util import (Face_Identity_Loss, Face_Regional_Loss, L1_Loss,
 
 
 def default_args(**over):
-    """The fields of `args` the step functions read, with train_3_encoder_hyperparams.py:23-68 defaults."""
+    """The fields of `args` the step functions and Sample_Eval_Save_Ckpt read, with train_3_encoder_hyperparams.py:23-79
+    defaults."""
     a = types.SimpleNamespace(
         tsr_encode=MODULATION_ENCODING[0], w_plus_sliced_layer=None, use_tanh=False,
         tsr_train=True, w_train=True, w_plus_train=True,
         lr=0.001, rec_batch=16, r1=10, d_reg_every=16, use_g_reg=True, g_reg_every=4, generator_path_reg_weight=2,
         path_reg_batch_shrink=2, l1_loss_lambda=3, lpips_loss_lambda=3, ep_lpips_l1_weight_shrink=10,
         face_id_loss_lambda=30, face_id_loss_type='MSE', grad_sync='ddp',
-        ds_freq=2, ex_ds_freq=3, rec_face_reg_loss_lambda=0, ds_face_reg_loss_lambda=20, ep_face_reg_loss_lambda=100)
+        ds_freq=2, ex_ds_freq=3, rec_face_reg_loss_lambda=0, ds_face_reg_loss_lambda=20, ep_face_reg_loss_lambda=100,
+        val_sample_freq=1000, model_save_freq=10000, n_real_eval_faces=2, n_syn_eval_faces=2,      # :73-79
+        val_sample_tile=256)        # this build's: side of the sample sheet's tiles (the output's size for a Generator below 256)
     for k, v in over.items():
         setattr(a, k, v)
     return a
@@ -379,3 +382,139 @@ class Trainer:
                 for m, f in zip(net.modules(), flags):
                     m.training = f
         return scores
+
+    # ------------------------------------------------------------------ the rest of Sample_Eval_Save_Ckpt (:667-753)
+    def _generative_model(self):
+        b = self.bare
+        return b['E_Tsr'], b['E_W'], b['E_W_Plus'], self.g_ema
+
+    def sample(self, visual_eval_samples, **sheet_kwargs):
+        """The qualitative half (train_3_encoder.py:678-706): Batch_Eval_Sheet of `visual_eval_samples` (the flat list
+        of the sample pickers, VAL_SET_LEN images per set) with the bare encoders, g_ema and the args' tsr_encode /
+        w_plus_sliced_layer / use_tanh, under no_grad: a uint8 [H, W, 3] tensor on the GPU.  sheet_kwargs: tile, gap,
+        margin, background, noise, randomize_noise.  Every module's training flag is restored, as evaluate() does."""
+        from Evaluation.visual_eval import Batch_Eval_Sheet
+        a = self.args
+        generative_model = self._generative_model()
+        was_training = [[m.training for m in net.modules()] for net in generative_model]
+        try:
+            for net in generative_model:
+                net.eval()
+            with torch.no_grad():
+                return Batch_Eval_Sheet(visual_eval_samples, generative_model, tsr_encode=a.tsr_encode,
+                                        sliced_layer=a.w_plus_sliced_layer, use_tanh=a.use_tanh, **sheet_kwargs)
+        finally:
+            for net, flags in zip(generative_model, was_training):
+                for m, f in zip(net.modules(), flags):
+                    m.training = f
+
+    def checkpoint(self):
+        """The reference's checkpoint dict (train_3_encoder.py:737-750: 14 keys, state dicts of the bare modules, None
+        for an absent D_edit) plus one key of this build, 'trainer' = {iter_idx, ds_count, mean_path_length}: the three
+        counters the reference loses on resume."""
+        a, b = self.args, self.bare
+        d_edit = b.get('D_edit')
+        mpl = self.mean_path_length
+        return {
+            'g': b['G'].state_dict(),
+            'e_tsr': b['E_Tsr'].state_dict(),
+            'e_W': b['E_W'].state_dict(),
+            'e_W_Plus': b['E_W_Plus'].state_dict(),
+            'd': b['D'].state_dict(),
+            'd_edit': d_edit.state_dict() if d_edit is not None else None,
+            'g_ema': self.g_ema.state_dict(),
+            'g_enc_optim': self.g_enc_optim.state_dict(),
+            'd_optim': self.d_optim.state_dict(),
+            'd_edit_optim': self.d_edit_optim.state_dict() if self.d_edit_optim is not None else None,
+            'co_mod': getattr(a, 'co_mod', True),
+            'use_tanh': a.use_tanh,
+            'tsr_encode': a.tsr_encode,
+            'sliced_layer': a.w_plus_sliced_layer,
+            'trainer': {'iter_idx': self.iter_idx, 'ds_count': self.ds_count,
+                        'mean_path_length': mpl.detach().clone() if torch.is_tensor(mpl) else mpl},
+        }
+
+    def save_checkpoint(self, ckpt_dir):
+        """Writes ckpt_dir/{iter:06d}.pt for the iteration just finished (self.iter_idx - 1), on rank 0 only; returns
+        the path on every rank."""
+        import os
+        path = os.path.join(ckpt_dir, f'{str(self.iter_idx - 1).zfill(6)}.pt')
+        if D_.get_rank() == 0:
+            os.makedirs(ckpt_dir, exist_ok=True)
+            torch.save(self.checkpoint(), path)
+        return path
+
+    def load_checkpoint(self, path_or_dict):
+        """Resume from a checkpoint file or dict, this build's or the reference's.  The networks and g_ema are loaded
+        through the bare modules, in place, so DDP- or Replica-wrapped networks see the loaded parameters; the
+        optimisers through Optimizer_Initilization(..., ckpt=...) over those same parameters.  The counters come from
+        'trainer' when present; otherwise by the reference's rule (train_3_encoder.py:438): iter_idx =
+        int(path[-9:-3]) + 1, ds_count = 0, mean_path_length = 0.  No derived weight survives a forward here (LiveWeights
+        re-reads the parameters at every call), so nothing else needs invalidating."""
+        import copy
+        b = self.bare
+        path = None
+        if isinstance(path_or_dict, dict):
+            ckpt = path_or_dict
+        else:
+            path = str(path_or_dict)
+            # to the host first: load_state_dict copies into the live tensors wherever they are, and Adam's step counts
+            # stay host tensors, as the optimisers keep them
+            ckpt = torch.load(path, map_location='cpu', weights_only=False)
+        for key, name in (('g', 'G'), ('e_tsr', 'E_Tsr'), ('e_W', 'E_W'), ('e_W_Plus', 'E_W_Plus'), ('d', 'D')):
+            b[name].load_state_dict(ckpt[key])
+        if b.get('D_edit') is not None and ckpt.get('d_edit') is not None:
+            b['D_edit'].load_state_dict(ckpt['d_edit'])
+        self.g_ema.load_state_dict(ckpt['g_ema'])
+        args = copy.copy(self.args)
+        args.load_train_state = True
+        self.g_enc_optim, self.d_optim, self.d_edit_optim = Optimizer_Initilization(
+            args, b['G'], b['E_Tsr'], b['E_W'], b['E_W_Plus'], b['D'], b.get('D_edit'),
+            ckpt=ckpt if ckpt.get('d_edit_optim') is not None else {k: v for k, v in ckpt.items() if k != 'd_edit_optim'})
+        state = ckpt.get('trainer')
+        if state is not None:
+            self.iter_idx, self.ds_count = int(state['iter_idx']), int(state['ds_count'])
+            mpl = state['mean_path_length']
+            device = self.device if self.device is not None else next(b['G'].parameters()).device
+            self.mean_path_length = mpl.detach().to(device, copy=True) if torch.is_tensor(mpl) else mpl
+        else:
+            if path is None:
+                raise ValueError('load_checkpoint: a dict without the \'trainer\' key carries no iteration; pass the '
+                                 'file path (the reference reads the iteration from the name, {iter:06d}.pt)')
+            self.iter_idx, self.ds_count, self.mean_path_length = int(path[-9:-3]) + 1, 0, 0
+        return ckpt
+
+    def Sample_Eval_Save_Ckpt(self, sample_dir, ckpt_dir, visual_eval_samples=None, rec_eval_loader=None,
+                              edit_eval_loader=None, log=None):
+        """What train() does after every iteration (train_3_encoder.py:667-753), for the iteration just finished, i =
+        self.iter_idx - 1: when i % args.val_sample_freq == 0 (and samples were given) the sheet, at tiles of
+        args.val_sample_tile, to sample_dir/{i:06d}.png; when i % args.model_save_freq == 0 and i > 0, evaluate() on the given loaders, the
+        reference's log text to `log` (a file object), and save_checkpoint(ckpt_dir).  Files are written on rank 0.
+        Returns (png path or None, scores or None, checkpoint path or None)."""
+        import os
+        a = self.args
+        i = self.iter_idx - 1
+        png = scores = ckpt = None
+        if i % a.val_sample_freq == 0 and visual_eval_samples is not None:
+            sheet = self.sample(visual_eval_samples, tile=getattr(a, 'val_sample_tile', 256))
+            png = os.path.join(sample_dir, f'{str(i).zfill(6)}.png')
+            if D_.get_rank() == 0:
+                from PIL import Image
+                os.makedirs(sample_dir, exist_ok=True)
+                Image.fromarray(sheet.cpu().numpy()).save(png)
+        if i % a.model_save_freq == 0 and i > 0:
+            if rec_eval_loader is not None or edit_eval_loader is not None:
+                scores = self.evaluate(rec_eval_loader, edit_eval_loader)
+                if log is not None:
+                    log.write('\n' + 'Reconstruction Quantitative Evaluation: ' + '\n' +
+                              'Cosine Similarity: ' + str(scores['cos_score']) + '\n' +
+                              'LPIPS Score: ' + str(scores['lpips_score']) + '\n' +
+                              'L1 Score: ' + str(scores['l1_score']) + '\n')
+                    log.write('\n' + 'Edit Quantitative Evaluation: ' + '\n' +
+                              'Edit Cosine Similarity: ' + str(scores['cos_score_edit']) + '\n' +
+                              'FID: ' + str(scores['fid']) + '\n' +
+                              'Heat Map: ' + str(scores['hmap_score']) + '\n' +
+                              'Land Mark: ' + str(scores['lmark_score']) + '\n' +
+                              'Face Regional: ' + str(scores['face_reg_score']) + '\n\n')
+            ckpt = self.save_checkpoint(ckpt_dir)
+        return png, scores, ckpt

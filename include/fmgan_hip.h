@@ -706,6 +706,15 @@ int fmgan_torgb_backward_f32(const float *x, const float *grad_out, const float 
  *       == transforms.ToTensor() + Normalize(mean, std) (train_3_encoder.py:233-239; Resize: fmgan_resize_* below)
  *   fmgan_tensor_to_images: in f32 [batch,3,h,w] -> out uint8 [batch,h,w,3] = (uint8)((clip(in,-1,1) + cent) * factor)
  *       == tensor2im (Evaluation/visual_eval.py:24-38), for every image of the batch.
+ *   fmgan_tiles_to_canvas: the same conversion into square slots of uint8 canvases, one launch for n tiles:
+ *       in f32 [n,3,src,src], canvas uint8 [n_canvas,canvas_h,canvas_w,3], slots int32 [n,3] ON THE DEVICE, one
+ *       (canvas, y0, x0) per tile;  canvas[slots[i].canvas, y0+y, x0+x, c] = (uint8)(int)((clip(v,-1,1) + cent) * factor)
+ *       with v = pixel (y,x) of tile i reduced from src to tile by f = src/tile in {1,2,4}: the pixel itself (f = 1: the
+ *       bits of fmgan_tensor_to_images), else aten's bilinear rule at align_corners=False, the four centre taps of the
+ *       f x f cell: 0.5*(0.5*a + 0.5*b) + 0.5*(0.5*c + 0.5*d), columns first, no fused multiply-add.  Only the tiles'
+ *       pixels are written; every other byte of the canvas keeps its value.  A tile whose slot does not lie wholly
+ *       inside its canvas (or names no canvas) is skipped.  FMGAN_EINVAL: non-positive sizes, null pointers, src not
+ *       tile, 2*tile or 4*tile; n == 0: FMGAN_OK; FMGAN_EOVERFLOW beyond the 32-bit pixel / grid indices.
  */
 /*
  * transforms.Resize(size) of the same pipeline (train_3_encoder.py:233-239) = PIL.Image.resize(BILINEAR), whose
@@ -733,6 +742,8 @@ int fmgan_images_to_tensor(const unsigned char *in, float *out, int batch, int h
                            float mean, float stdv, void *stream);
 int fmgan_tensor_to_images(const float *in, unsigned char *out, int batch, int h, int w,
                            float cent, float factor, void *stream);
+int fmgan_tiles_to_canvas(const float *in, unsigned char *canvas, const int *slots, int n, int src, int tile,
+                          int n_canvas, int canvas_h, int canvas_w, float cent, float factor, void *stream);
 
 #ifdef __cplusplus
 }

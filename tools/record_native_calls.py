@@ -8,7 +8,8 @@ entry points with the same arguments in the same order, bracketed by the same (n
 GPU.  After the first _native.lib() the module's `_lib` cache is replaced by a proxy that forwards each call and appends
     ["call", symbol, [args]]
 to one list: integers and floats as they are; a pointer argument (by the entry point's argtypes) as "null", as its address
-& 15 when it is an address, or as "host" for a ctypes object (byref out-parameters, host arrays).  An observer appends
+& 15 when it is an address (also one cast to a ctypes pointer), or as "host" for any other ctypes object (byref
+out-parameters, host arrays).  An observer appends
     ["begin", name, info]  /  ["end"]
 to the same list, and the callable given as `latent_columns=` appends ["column", i] at each fetch.  Needs a GPU; uses nothing but the package (tools/ and tests/ helpers only for deterministic inputs).
 """
@@ -37,6 +38,8 @@ def _plain(arg, ctype):
         return arg
     if isinstance(arg, ctypes.c_void_p):
         arg = arg.value
+    elif isinstance(arg, ctypes._Pointer):          # an address cast to POINTER(c_int): the device slots of tiles_to_canvas
+        arg = ctypes.cast(arg, ctypes.c_void_p).value
     if arg is None or arg == 0:
         return 'null'
     return arg & 15 if isinstance(arg, int) else 'host'
@@ -198,6 +201,9 @@ def small_ops(d):
     _native.resize_images(imgs, 12, 10)
     _native.resize_images(imgs, 12, 10, to_tensor=True)
     _native.tensor_to_images(t('img/f32', (2, 3, 12, 10), d, dist='uniform'))
+    from op.canvas import tiles_to_canvas
+    canvas = torch.zeros((2, 9, 23, 3), dtype=torch.uint8, device=d)
+    tiles_to_canvas(t('img/tiles', (3, 3, 12, 12), d, dist='uniform'), canvas, [(1, 2, 1), (0, 0, 8), (1, 1, 16)], 6)
 
 
 def main():
