@@ -19,8 +19,11 @@ What is different, on purpose:
     with loaded weights) and `fid_stats` (the real images' statistics: a dict or the path of a pickle with `mean` and
     `cov`); neither is shipped, and an `inception_model` without `fid_stats` is refused.  The features of a batch's outputs
     go into running moments on the device (op/fid_stats.py);
-  * the heat-map and landmark scores need the third-party `face_alignment` package, which is absent: `fa_model` must be
-    None, and those two entries of the tuple are None.
+  * the heat-map and landmark scores are computed when `eval_models` brings an `fa_model`: the caller's face_alignment
+    model, anything with `face_detector` and `face_alignment_net` (Util/landmark_util.py; the package itself is not
+    shipped).  Crops, distance and landmark decode run on their own kernels (op/landmark.py) and the per-sample values
+    stay on the device; the landmarks come from the device decode, not from the package's numpy `get_preds_fromhm`.
+    Without an `fa_model` those two entries of the tuple are None.
 EVAL_FUSE = False (or FMGAN_NO_EVAL_FUSE=1) keeps the composite metric stage and the reference's loop structure
 (Forward_Inference_3_Encoder per render, target features per call): the baseline of profiles/quant_eval.md.
 """
@@ -33,6 +36,8 @@ import torch.nn.functional as F
 from op.eval_scores import face_input
 from op.fid_stats import Feature_Statistics
 from op.face_region import face_region_scores
+from op.landmark import heatmap_distance
+from Util.landmark_util import Get_HeatMap_Landmark_PyTorch
 from Util.network_util import (Encode_Photo, Forward_Inference_3_Encoder, Forward_Inference_Reanimate,
                                MODULATION_ENCODING)
 
@@ -125,10 +130,11 @@ class _NoiseArgs:
 
 def Edit_Scores(eval_loader, device, generative_model, eval_models, info_print=False, tsr_encode=MODULATION_ENCODING[1],
                 sliced_layer=None, use_tanh=False, noise=None, randomize_noise=True, fid_stats=None):
-    """Per-sample editing scores as device tensors: dict(cos, face_diff).  eval_loader yields [photo, render_1, ...,
-    render_n] batches; eval_models = (face_rec_model, inception_model, fa_model) with fa_model None.  Order of both
-    lists: batch by batch, render-major within a batch (all samples of render 1, then render 2, ...), as the reference
-    appends them.  noise / randomize_noise go to the generator (its own defaults when not given).  With an inception_model
+    """Per-sample editing scores as device tensors: dict(cos, face_diff), and with an fa_model also hmap (sum of squared
+    heat-map differences of render and output) and lmark (mean squared landmark difference in the image's frame).
+    eval_loader yields [photo, render_1, ..., render_n] batches; eval_models = (face_rec_model, inception_model,
+    fa_model), fa_model None or the caller's alignment model (Util/landmark_util.py).  Order of every list: batch by
+    batch, render-major within a batch (all samples of render 1, then render 2, ...), as the reference appends them.  noise / randomize_noise go to the generator (its own defaults when not given).  With an inception_model
     and fid_stats (the real statistics) the dict also holds `fid_state`: the Feature_Statistics of every output's features
     (a batch's outputs concatenated, one pass through the model)."""
     E_Tsr, E_W, E_W_Plus, g_ema = _three_encoders(generative_model)
@@ -136,12 +142,13 @@ def Edit_Scores(eval_loader, device, generative_model, eval_models, info_print=F
     if inception_model is not None and fid_stats is None:
         raise ValueError('Edit_Scores: inception_model without fid_stats: FID needs Inception weights and the FFHQ '
                          'statistics file, which are not shipped; pass both, or inception_model=None')
-    if fa_model is not None:
-        raise ValueError('Edit_Scores: fa_model must be None: the heat-map and landmark scores need the face_alignment '
-                         'package, which is absent')
+    if fa_model is not None and not (hasattr(fa_model, 'face_detector') and hasattr(fa_model, 'face_alignment_net')):
+        raise ValueError('Edit_Scores: fa_model must be None or a face_alignment.FaceAlignment (anything with '
+                         '`face_detector` and `face_alignment_net`): the heat-map and landmark scores run the caller\'s '
+                         'two networks')
     if tsr_encode not in MODULATION_ENCODING:
         raise ValueError(f'tsr_encode must be one of {MODULATION_ENCODING}')
-    cos, face_diff, fid_state = [], [], None
+    cos, face_diff, hmap, lmark, fid_state = [], [], [], [], None
     with torch.no_grad():
         for idx, img_tensor_list in enumerate(eval_loader):
             if info_print:
@@ -170,6 +177,12 @@ def Edit_Scores(eval_loader, device, generative_model, eval_models, info_print=F
                     face_diff.append(face_region_scores(r_input, g_output))
                 cos += Compute_Face_Identity_Similarity(g_output_list, p_input, face_rec_model)
                 outputs = g_output_list
+            if fa_model is not None:
+                for r_input, g_output in zip(renders, outputs):
+                    heatmap_g, landmark_g = Get_HeatMap_Landmark_PyTorch(g_output, fa_model, device)
+                    heatmap_r, landmark_r = Get_HeatMap_Landmark_PyTorch(r_input, fa_model, device)
+                    hmap.append(heatmap_distance(heatmap_r, heatmap_g))
+                    lmark.append(torch.mean(torch.square(landmark_r - landmark_g), dim=(1, 2)))
             if inception_model is not None and outputs:
                 feat = features_of(inception_model, torch.cat(outputs), fid.FID_FUSE)
                 if fid_state is None:
@@ -178,6 +191,8 @@ def Edit_Scores(eval_loader, device, generative_model, eval_models, info_print=F
     if not cos:
         raise ValueError('Edit_Scores: the loader yielded no render')
     scores = {'cos': torch.cat(cos), 'face_diff': torch.cat(face_diff)}
+    if fa_model is not None:
+        scores['hmap'], scores['lmark'] = torch.cat(hmap), torch.cat(lmark)
     if fid_state is not None:
         scores['fid_state'] = fid_state
     return scores
@@ -185,8 +200,8 @@ def Edit_Scores(eval_loader, device, generative_model, eval_models, info_print=F
 
 def Get_Edit_Score(eval_loader, device, generative_model, eval_models, info_print=False, **kwargs):
     """(mean cosine similarity, fid, heat-map score, landmark score, mean face difference): the reference's 5-tuple, with
-    None for the scores not computed: the heat-map and landmark scores always, the FID unless eval_models brings an
-    inception_model and `fid_stats` (the real images' statistics: a dict or a pickle path with `mean` / `cov`) is given."""
+    None for the scores not computed: the heat-map and landmark scores unless eval_models brings an fa_model, the FID
+    unless it brings an inception_model and `fid_stats` (the real images' statistics: a dict or a pickle path with `mean` / `cov`) is given."""
     real = None
     if eval_models[1] is not None and kwargs.get('fid_stats') is not None:
         real = fid.load_real_stats(kwargs['fid_stats'])          # before the loop: a wrong path fails at once
@@ -196,4 +211,6 @@ def Get_Edit_Score(eval_loader, device, generative_model, eval_models, info_prin
     fid_score = None
     if 'fid_state' in s:
         fid_score = fid.calc_fid(*s['fid_state'].finish(), *real)
-    return _mean(s['cos']), fid_score, None, None, _mean(s['face_diff'])
+    hmap_score = _mean(s['hmap']) if 'hmap' in s else None
+    lmark_score = _mean(s['lmark']) if 'lmark' in s else None
+    return _mean(s['cos']), fid_score, hmap_score, lmark_score, _mean(s['face_diff'])

@@ -5,8 +5,8 @@ regulariser, the L1 reconstruction loss, the wrappers of the perceptual (LPIPS) 
 (Util/training_util.py:115-127, 131-205), and the face-regional loss of the dual-supervision iterations
 (Util/training_util.py:228-256; one HIP kernel per direction, op/face_region.py).  R1 and path length differentiate
 *through* a first derivative, i.e. they exercise the double-backward of the HIP ops (upfirdn2d, fused_bias_act) and of
-the modulated conv.  Only the landmark heat-map term is left out: it needs `face_alignment`, a third-party package that
-is absent offline.
+the modulated conv.  The landmark heat-map term (Util/training_util.py:206-222) is Heat_Map_Loss: the caller brings the
+detector and the alignment network, the crops and the distance run on their own HIP kernels (op/landmark.py).
 """
 import math
 
@@ -16,6 +16,9 @@ from torch.nn import functional as F
 
 from op import _native
 from op.face_region import face_region_loss
+from op.landmark import heatmap_distance
+
+from .landmark_util import Get_HeatMap_PyTorch
 
 
 def d_logistic_loss(real_pred, fake_pred):
@@ -104,6 +107,18 @@ def Face_Regional_Loss(r_img, g_img, device=None):
     reference's signature; the term runs where the tensors are.  Render and image must have the same shape (ValueError
     otherwise: the reference broadcasts there, e.g. 256^2 renders against 1024^2 outputs)."""
     return face_region_loss(r_img, g_img)
+
+
+def Heat_Map_Loss(g_output, r_input, fa, device=None):
+    """Face alignment loss on the heat maps of the output images and of the renders (training_util.py:206-222):
+    mean over the batch of sum((heatmap_r - heatmap_g)^2).  g_output, r_input [N, 3, H, W] in [-1, 1]; fa: the alignment
+    model (Util/landmark_util.py).  Two Get_HeatMap_PyTorch calls, as in the reference; the render's runs under no_grad
+    (renders are data), the output's is differentiable through the alignment network and the crop.  `device` is kept for
+    the reference's signature."""
+    with torch.no_grad():
+        heatmap_r, _, _ = Get_HeatMap_PyTorch(r_input, fa, device)
+    heatmap_g, _, _ = Get_HeatMap_PyTorch(g_output, fa, device)
+    return torch.mean(heatmap_distance(heatmap_r, heatmap_g))
 
 
 def requires_grad(model, flag=True):

@@ -17,28 +17,12 @@
 // of lpips_input.h's fixed-offset vector loads applies: a lane owns one output pixel, loads its 4 taps of 3 channels as
 // scalars (adjacent lanes: adjacent or near-adjacent addresses of one source row) and writes 12 contiguous bytes, a wave
 // 768.  grid.x = samples * blocks per sample, one pixel per lane, no loop, no shared memory.
-#include "common.h"
+#include "bilinear_tap.h"
 
 namespace {
 
 constexpr int II_THREADS = 256;
 constexpr int II_OUT = 299;
-
-struct IiTap {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ IiTap ii_tap(float scale, int d, int s) {
-  float src = __fmaf_rn(scale, (float)d + 0.5f, -0.5f);
-  src = src < 0.f ? 0.f : src;
-  IiTap t;
-  t.i0 = (int)src;
-  t.i1 = t.i0 + (t.i0 < s - 1 ? 1 : 0);
-  t.l1 = __fsub_rn(src, (float)t.i0);
-  t.l0 = __fsub_rn(1.f, t.l1);
-  return t;
-}
 
 template <bool COPY>
 __global__ __launch_bounds__(II_THREADS) void inception_input_f32(const float* __restrict__ img, float* __restrict__ out,
@@ -54,7 +38,7 @@ __global__ __launch_bounds__(II_THREADS) void inception_input_f32(const float* _
 #pragma unroll
     for (int c = 0; c < 3; ++c) v[c] = src[c * hw + (long long)oy * s + ox];
   } else {
-    const IiTap ty = ii_tap(scale, oy, s), tx = ii_tap(scale, ox, s);
+    const BilinearTap ty = bilinear_tap(scale, oy, s), tx = bilinear_tap(scale, ox, s);
     const float* r0 = src + (long long)ty.i0 * s;
     const float* r1 = src + (long long)ty.i1 * s;
 #pragma unroll

@@ -76,6 +76,14 @@ def lib():
     _sig(L.fmgan_fid_stats_finish_f64, [vp] * 3 + [ll, vp, vp, i, vp])
     _sig(L.fmgan_inception_input_select, [i] * 3)
     _sig(L.fmgan_inception_input_f32, [vp, vp] + [i] * 4 + [vp])
+    _sig(L.fmgan_face_crop_select, [i] * 4)
+    _sig(L.fmgan_face_crop_fwd_f32, [vp] * 3 + [i] * 4 + [vp])
+    _sig(L.fmgan_face_crop_bwd_f32, [vp] * 3 + [i] * 4 + [vp])
+    _sig(L.fmgan_detector_input_f32, [vp, vp, i, ll, vp])
+    _sig(L.fmgan_heatmap_distance_blocks, [i, ll])
+    _sig(L.fmgan_heatmap_distance_fwd_f32, [vp] * 3 + [i, ll, vp])
+    _sig(L.fmgan_heatmap_distance_bwd_f32, [vp] * 5 + [i, ll, vp])
+    _sig(L.fmgan_landmark_decode_f32, [vp] * 5 + [i] * 4 + [vp])
     _sig(L.fmgan_lpips_distance_blocks, [i] * 3)
     _sig(L.fmgan_lpips_distance_f32, [vp] * 4 + [i, i, i, f, vp])
     _sig(L.fmgan_lpips_distance_backward_f32, [vp] * 6 + [i, i, i, f, vp])
@@ -656,6 +664,143 @@ def projection_loss_bwd(x, target, mask, g_y, k, scale):
         st = lib().fmgan_projection_loss_bwd_f32(fp(x), fp(target), fp(mask), pg, pk, fp(scale), fp(grad_x), b, h, w, f,
                                                  stream)
     return grad_x if served(st, 'projection_loss_bwd') else None
+
+
+# ----------------------------------------------------------------------------- landmark stages (csrc/landmark.hip)
+HEATMAP_SIZE = 64                         # the side of the alignment network's heat maps (the decode kernel's only size)
+
+
+def _box_ptr(box, n, device, what):
+    """data_ptr of the [n, 4] int32 box tensor on `device` (ux, uy, bx, by per sample), read by the crop kernels."""
+    if tuple(box.shape) != (n, 4):
+        raise ValueError(f'{what}: box {tuple(box.shape)}: expected [{n}, 4] (ux, uy, bx, by per sample)')
+    if box.dtype != torch.int32 or box.device != device or not box.is_contiguous():
+        raise RuntimeError(f'{what}: box must be a contiguous int32 tensor on {device}, got {box.dtype} on {box.device}')
+    return box.data_ptr()
+
+
+def face_crop_serves(n, h, w, r):
+    """Do the crop kernels take [n, 3, h, w] images and r x r crops (host logic, nothing runs)?"""
+    return n > 0 and lib().fmgan_face_crop_select(int(n), int(h), int(w), int(r)) > 0
+
+
+def face_crop_fwd(img, box, r):
+    """Face crop in one launch for the batch (csrc/landmark.hip): img [N, 3, H, W] f32 contiguous in [-1, 1], box [N, 4]
+    int32 on img's device -> [N, 3, r, r] in [0, 1]: Get_HeatMap_PyTorch's scaling, Crop_PyTorch and the division by
+    255.  None when the library declines the sizes."""
+    if img.ndim != 4 or img.shape[1] != 3:
+        raise ValueError(f'face_crop: img {tuple(img.shape)}: expected [N, 3, H, W]')
+    require_f32_gpu('face_crop', ((img, 'img'),))
+    n, _, h, w = img.shape
+    r = int(r)
+    pb = _box_ptr(box, n, img.device, 'face_crop')
+    if not face_crop_serves(n, h, w, r):
+        return None
+    with launching(img, 'face_crop', (n, h, w, r, 0)) as stream:
+        out = torch.empty((n, 3, r, r), dtype=torch.float32, device=img.device)
+        st = lib().fmgan_face_crop_fwd_f32(fp(img), pb, fp(out), n, h, w, r, stream)
+    return out if served(st, 'face_crop_fwd') else None
+
+
+def face_crop_bwd(grad_out, box, h, w):
+    """Gradient of face_crop_fwd with respect to img in one launch: grad_out [N, 3, r, r] f32 contiguous -> [N, 3, h, w],
+    exactly 0 outside the crops, bit-reproducible (gather, fixed order).  None when the library declines the sizes."""
+    if grad_out.ndim != 4 or grad_out.shape[1] != 3 or grad_out.shape[2] != grad_out.shape[3]:
+        raise ValueError(f'face_crop_bwd: grad_out {tuple(grad_out.shape)}: expected [N, 3, r, r]')
+    require_f32_gpu('face_crop_bwd', ((grad_out, 'grad_out'),))
+    n, _, r, _ = grad_out.shape
+    h, w = int(h), int(w)
+    pb = _box_ptr(box, n, grad_out.device, 'face_crop_bwd')
+    if not face_crop_serves(n, h, w, r):
+        return None
+    with launching(grad_out, 'face_crop', (n, h, w, r, 1)) as stream:
+        grad_img = torch.empty((n, 3, h, w), dtype=torch.float32, device=grad_out.device)
+        st = lib().fmgan_face_crop_bwd_f32(fp(grad_out), pb, fp(grad_img), n, h, w, r, stream)
+    return grad_img if served(st, 'face_crop_bwd') else None
+
+
+def detector_input(img):
+    """The face detector's input in one launch: img [N, 3, H, W] f32 contiguous in [-1, 1] ->
+    ((img + 1) * 255 / 2).flip(1) - (104, 117, 123).  None for an empty batch."""
+    if img.ndim != 4 or img.shape[1] != 3:
+        raise ValueError(f'detector_input: img {tuple(img.shape)}: expected [N, 3, H, W]')
+    require_f32_gpu('detector_input', ((img, 'img'),))
+    n, _, h, w = img.shape
+    if n == 0 or h * w == 0:
+        return None
+    with launching(img, 'detector_input', (n, h, w)) as stream:
+        out = torch.empty_like(img)
+        st = lib().fmgan_detector_input_f32(fp(img), fp(out), n, h * w, stream)
+    check(st, 'detector_input')
+    return out
+
+
+def _heatmap_distance_shape(a, b):
+    if a.ndim < 2 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f'heatmap_distance: {tuple(a.shape)} and {tuple(b.shape)}: expected two [N, ...] tensors of one '
+                         f'shape')
+    require_f32_gpu('heatmap_distance', ((a, 'a'), (b, 'b')))
+    n = a.shape[0]
+    return n, (a.numel() // n if n else 0)
+
+
+def heatmap_distance_serves(n, m):
+    """Do the distance kernels take n samples of m elements (host logic, nothing runs)?"""
+    return n > 0 and lib().fmgan_heatmap_distance_blocks(int(n), int(m)) > 0
+
+
+def heatmap_distance_fwd(a, b):
+    """Per-sample squared distance in one launch: a, b [N, ...] f32 contiguous of one shape -> partial [N, blocks] f32,
+    fixed-order sums of (a - b)^2 over 4096 elements each (bit-reproducible; add with sum(1, dtype=float64)).  None when
+    the library declines (a sample's element count no multiple of 4)."""
+    n, m = _heatmap_distance_shape(a, b)
+    blocks = lib().fmgan_heatmap_distance_blocks(n, m) if n else 0
+    if blocks <= 0:
+        return None
+    with launching(a, 'heatmap_distance', (n, m, 0)) as stream:
+        partial = torch.empty((n, blocks), dtype=torch.float32, device=a.device)
+        st = lib().fmgan_heatmap_distance_fwd_f32(fp(a), fp(b), fp(partial), n, m, stream)
+    return partial if served(st, 'heatmap_distance_fwd') else None
+
+
+def heatmap_distance_bwd(a, b, grad, need_a, need_b):
+    """Gradients of the distance in one launch: grad [N] f32 ON THE DEVICE is the upstream gradient, read by the kernel
+    (no .item()).  Returns (grad_a or None, grad_b or None) as need_a / need_b ask; None (alone) when not served."""
+    n, m = _heatmap_distance_shape(a, b)
+    if not (need_a or need_b):
+        return None, None
+    g = grad.reshape(-1)
+    if g.numel() != n:
+        raise ValueError(f'heatmap_distance_bwd: grad must hold one element per sample ({n}), got {tuple(grad.shape)}')
+    g = g.to(device=a.device, dtype=torch.float32).contiguous()
+    if not heatmap_distance_serves(n, m):
+        return None
+    with launching(a, 'heatmap_distance', (n, m, 1)) as stream:
+        ga = torch.empty_like(a) if need_a else None
+        gb = torch.empty_like(b) if need_b else None
+        st = lib().fmgan_heatmap_distance_bwd_f32(fp(a), fp(b), fp(g), fp(ga), fp(gb), n, m, stream)
+    return (ga, gb) if served(st, 'heatmap_distance_bwd') else None
+
+
+def landmark_decode(hm, center=None, scale=None):
+    """_get_preds_fromhm_torch in one launch, one wave per map: hm [B, C, 64, 64] f32 contiguous, center [B, 2] and scale
+    [B] f32 on hm's device (both or neither) -> (preds, preds_orig), each [B, C, 2].  None when the library declines
+    (maps of another size)."""
+    if hm.ndim != 4 or (center is None) != (scale is None) or \
+            (center is not None and (tuple(center.shape) != (hm.shape[0], 2) or tuple(scale.shape) != (hm.shape[0],))):
+        raise ValueError(f'landmark_decode: hm {tuple(hm.shape)}, center '
+                         f'{None if center is None else tuple(center.shape)}, scale '
+                         f'{None if scale is None else tuple(scale.shape)}: expected [B, C, H, W], and [B, 2] with [B] '
+                         f'or neither')
+    require_f32_gpu('landmark_decode', ((hm, 'hm'), (center, 'center'), (scale, 'scale')))
+    b, c, h, w = hm.shape
+    if b * c == 0 or (h, w) != (HEATMAP_SIZE, HEATMAP_SIZE):
+        return None
+    with launching(hm, 'landmark_decode', (b, c)) as stream:
+        preds = torch.empty((b, c, 2), dtype=torch.float32, device=hm.device)
+        preds_orig = torch.empty_like(preds)
+        st = lib().fmgan_landmark_decode_f32(fp(hm), fp(center), fp(scale), fp(preds), fp(preds_orig), b, c, h, w, stream)
+    return (preds, preds_orig) if served(st, 'landmark_decode') else None
 
 
 def nhwc_dense(t):

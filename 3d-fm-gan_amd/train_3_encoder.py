@@ -26,9 +26,10 @@ What is different, on purpose:
     rec/ds/ep = 0/20/100, train_3_encoder_hyperparams.py:69-71) is plain tensor arithmetic and runs on its own HIP
     kernel (op/face_region.py); it needs renders of the output's size, so at 1024^2 outputs from 256^2 renders a
     dual-supervision iteration raises ValueError (the reference broadcasts there; resampling is not provided).  The
-    landmark heat-map term (:538-542) needs the third-party `face_alignment` package (absent; its weight is 0 in the
-    reference's setting, train_3_encoder_hyperparams.py:66-68) and is not provided; `extra_losses` takes any further
-    (name, weight, fn(output, reference) -> scalar) terms.
+    landmark heat-map term (:538-542) is computed when `fa_model` (the caller's face_alignment model: detector and
+    alignment network) is passed and iter_idx > args.hmap_iter_thres, with weight args.hmap_loss_lambda (0 and inf in
+    the reference's setting, train_3_encoder_hyperparams.py:66-68); its crops and distance run on their own HIP kernels
+    (op/landmark.py).  `extra_losses` takes any further (name, weight, fn(output, reference) -> scalar) terms.
   * the schedule is opt-in: Trainer.step(...) without flags is a reconstruction iteration, exactly as before;
     Trainer.train_iteration(...) draws the flags and the batch as train() does.
 """
@@ -41,7 +42,7 @@ from torch import nn, optim
 import dataset
 from Miscellaneous import distributed as D_
 from Util.network_util import Forward_Inference_3_Encoder, MODULATION_ENCODING
-from Util.training_util import (Face_Identity_Loss, Face_Regional_Loss, L1_Loss, LPIPS_Loss, accumulate,
+from Util.training_util import (Face_Identity_Loss, Face_Regional_Loss, Heat_Map_Loss, L1_Loss, LPIPS_Loss, accumulate,
                                 d_logistic_loss, d_r1_loss, g_nonsaturating_loss, requires_grad)
 
 
@@ -54,6 +55,7 @@ def default_args(**over):
         lr=0.001, rec_batch=16, r1=10, d_reg_every=16, use_g_reg=True, g_reg_every=4, generator_path_reg_weight=2,
         path_reg_batch_shrink=2, l1_loss_lambda=3, lpips_loss_lambda=3, ep_lpips_l1_weight_shrink=10,
         face_id_loss_lambda=30, face_id_loss_type='MSE', grad_sync='ddp',
+        hmap_loss_lambda=0, hmap_iter_thres=np.inf,                                                # :66-68
         ds_freq=2, ex_ds_freq=3, rec_face_reg_loss_lambda=0, ds_face_reg_loss_lambda=20, ep_face_reg_loss_lambda=100,
         val_sample_freq=1000, model_save_freq=10000, n_real_eval_faces=2, n_syn_eval_faces=2,      # :73-79
         val_sample_tile=256)        # this build's: side of the sample sheet's tiles (the output's size for a Generator below 256)
@@ -183,9 +185,11 @@ def G_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, D, g_input, r_input, g_ref, args, l
                     lpips_model=None, face_rec_model=None, fa_model=None, iter_idx=0, extreme_ds_flag=False,
                     ds_flag=False, extra_losses=()):
     """Update G and the encoders on the adversarial + reconstruction losses (train_3_encoder.py:495-558; the
-    reference's argument order).  lpips_model / face_rec_model = None leaves that term out.  The face-regional term
-    is added last, with face_reg_lambda(args, ds_flag, extreme_ds_flag); at weight 0 (reconstruction batches) it is not
-    computed and loss_dict['face_reg'] is a zero, which is what the reference's 0 * term contributes."""
+    reference's argument order).  lpips_model / face_rec_model = None leaves that term out.  The heat-map term is
+    added when fa_model is given and iter_idx > args.hmap_iter_thres; otherwise loss_dict['hmap'] is a zero, as in the
+    reference (:538-542).  The face-regional term is added last, with face_reg_lambda(args, ds_flag,
+    extreme_ds_flag); at weight 0 (reconstruction batches) it is not computed and loss_dict['face_reg'] is a zero,
+    which is what the reference's 0 * term contributes."""
     requires_grad(G, True)
     requires_grad(E_Tsr, args.tsr_train)
     requires_grad(E_W, args.w_train)
@@ -211,6 +215,11 @@ def G_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, D, g_input, r_input, g_ref, args, l
     for name, weight, fn in extra_losses:
         loss_dict[name] = weight * fn(g_output, g_ref)
         total_loss = total_loss + loss_dict[name]
+    if fa_model is not None and iter_idx > getattr(args, 'hmap_iter_thres', np.inf):
+        loss_dict['hmap'] = getattr(args, 'hmap_loss_lambda', 0) * Heat_Map_Loss(g_output, r_input, fa_model)
+        total_loss = total_loss + loss_dict['hmap']
+    else:
+        loss_dict['hmap'] = torch.zeros((), device=g_output.device)
     face_reg_loss_lambda = face_reg_lambda(args, ds_flag, extreme_ds_flag)
     if face_reg_loss_lambda:
         loss_dict['face_reg'] = face_reg_loss_lambda * Face_Regional_Loss(r_input, g_output)
@@ -271,10 +280,10 @@ class Trainer:
     dual-supervision iterations (bare modules on this rank's device; BatchNorm of the encoders in eval mode, SURVEY
     F13).  grad_sync: 'ddp' wraps them in DistributedDataParallel, 'flat' in Replica + gather_grad."""
 
-    def __init__(self, nets, args, device=None, g_ema=None, lpips_model=None, face_rec_model=None):
+    def __init__(self, nets, args, device=None, g_ema=None, lpips_model=None, face_rec_model=None, fa_model=None):
         import copy
         self.args = args
-        self.lpips_model, self.face_rec_model = lpips_model, face_rec_model
+        self.lpips_model, self.face_rec_model, self.fa_model = lpips_model, face_rec_model, fa_model
         ddp = getattr(args, 'grad_sync', 'ddp') == 'ddp'
         self.bare = dict(nets)
         self.g_ema = g_ema if g_ema is not None else copy.deepcopy(nets['G']).eval().requires_grad_(False)
@@ -325,7 +334,7 @@ class Trainer:
         if self.iter_idx % a.d_reg_every == 0:
             ld['r1'] = D_Reg_BackProp(g_ref, Dn, a, d_optim)
         G_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, Dn, g_input, r_input, g_ref, a, ld, self.g_enc_optim,
-                        self.lpips_model, self.face_rec_model, None, self.iter_idx, extreme_ds_flag, ds_flag)
+                        self.lpips_model, self.face_rec_model, self.fa_model, self.iter_idx, extreme_ds_flag, ds_flag)
         if self.iter_idx % a.g_reg_every == 0 and a.use_g_reg:
             ld['g_reg'], _, self.mean_path_length = G_Reg_BackProp(G, E_Tsr, E_W, E_W_Plus, g_input, r_input, a,
                                                                    self.mean_path_length, self.g_enc_optim, ppl_choice)
@@ -351,8 +360,9 @@ class Trainer:
         rec_eval_loader ((photo, render) batches) and Get_Edit_Score on edit_eval_loader ([photo, render_1, ..] batches),
         with the bare encoders, g_ema, self.face_rec_model and self.lpips_model, under no_grad.  Returns a dict with the
         reference's log names: cos_score, lpips_score, l1_score (reconstruction), cos_score_edit, fid, hmap_score,
-        lmark_score, face_reg_score (editing); the scores of a loader that was not given, and the three this build does
-        not provide, are None.  kwargs go to Get_Edit_Score (noise, randomize_noise).  Parameters, their requires_grad
+        lmark_score, face_reg_score (editing); the scores of a loader that was not given are None, and so are the FID
+        and, for a Trainer built without fa_model, hmap_score and lmark_score.  kwargs go to Get_Edit_Score (noise,
+        randomize_noise).  Parameters, their requires_grad
         and the modules' training flags, the optimisers, the counters and mean_path_length are left as they are."""
         from Evaluation.quant_eval import Get_Edit_Score, Get_Recon_Score
         a, b = self.args, self.bare
@@ -376,7 +386,8 @@ class Trainer:
                 if edit_eval_loader is not None:
                     (scores['cos_score_edit'], scores['fid'], scores['hmap_score'], scores['lmark_score'],
                      scores['face_reg_score']) = Get_Edit_Score(edit_eval_loader, device, generative_model,
-                                                                (self.face_rec_model, None, None), **fwd, **kwargs)
+                                                                (self.face_rec_model, None, self.fa_model), **fwd,
+                                                                **kwargs)
         finally:
             for net, flags in zip(generative_model, was_training):
                 for m, f in zip(net.modules(), flags):

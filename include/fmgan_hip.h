@@ -347,6 +347,51 @@ int fmgan_inception_input_select(int batch, int h, int w);
 int fmgan_inception_input_f32(const float *img, float *out, int batch, int h, int w, int normalize, void *stream);
 
 /*
+ * Tensor work around the landmark networks (Util/landmark_util.py; Util/training_util.py Heat_Map_Loss): face crop forward
+ * and backward, the detector's input, the heat-map distance forward and backward, the landmark decode.  One launch each,
+ * f32, no atomics: the same input gives the same bits.  All tensors contiguous.
+ *   face crop: img [batch, 3, h, w] NCHW in [-1, 1];  box: DEVICE pointer to [batch, 4] 32-bit ints (ux, uy, bx, by), read
+ *     by the kernel;  out [batch, 3, r, r].  Per sample the canvas has hc = by - uy rows and wc = bx - ux columns,
+ *       canvas[c, y, x] = ((img[c, y + uy, x + ux] + 1) * 255) * 0.5  where 0 <= y + uy < h and 0 <= x + ux < w, else 0,
+ *       out = bilinear(canvas -> r x r, align_corners = false) / 255  (correctly rounded division),
+ *     taps and weights per axis by the fp32 rule stated for fmgan_inception_input_f32 with scale = (float)hc / (float)r
+ *     (wc for columns), v = h0 * (w0 * a + w1 * b) + h1 * (w0 * c + w1 * d), every product and sum rounded.  The canvas is
+ *     never stored; any ratio, up or down (two taps per axis, no antialiasing).  A box with a side outside [1, 2^24]
+ *     gives a zero crop and a zero gradient.  Every read of img is bounds-tested whatever the box holds.
+ *     backward: grad_img[n, c, y, x] = ((sum of (hk * wk) * (grad_out[n, c, oy, ox] / 255)) * 0.5) * 255 over the output
+ *     pixels and taps that name canvas pixel (y - uy, x - ux), output rows, then columns, then the row tap, then the
+ *     column tap ascending; the taps are found with the forward's own function.  Exactly 0 outside the crop.
+ *   fmgan_face_crop_select: the launches' plan with the launch left out: 1 when they run, FMGAN_EINVAL for a non-positive
+ *     argument (the launches also for a NULL pointer), FMGAN_EOVERFLOW for h, w or r above 2^15 or a grid above 2^31 - 1.
+ *   detector input: out[n, c] = ((img[n, 2 - c] + 1) * 255) * 0.5 - mean[c], mean = (104, 117, 123), planes of hw elements.
+ *   heat-map distance: a, b [batch, m], m % 4 == 0 (else FMGAN_EUNSUPPORTED: the caller evaluates the composite).
+ *     forward : partial[n * blocks + i], blocks = fmgan_heatmap_distance_blocks(batch, m) (0 where the launch does not
+ *               run): the sum of (a - b)^2 over elements [4096 i, 4096 (i + 1)) of sample n; per-lane serial fma, wave
+ *               butterfly, waves in order.  The caller adds a sample's partials (in float64).
+ *     backward: grad_a = (2 * g[n]) * (a - b), grad_b = -grad_a; either may be NULL (not wanted), not both.  g: DEVICE
+ *               pointer to [batch] floats, the upstream gradient (no host copy, no synchronisation).
+ *   landmark decode (_get_preds_fromhm_torch): hm [batch, channels, 64, 64] (another size: FMGAN_EUNSUPPORTED), one wave
+ *     per map.  idx = argmax over the 4096 values, the smallest index on a tie, NaN above every number;
+ *     px = idx % 64, py = idx / 64;  (x, y) = (px + 1, py + 1), plus 0.25 * sign(hm[py][px + 1] - hm[py][px - 1]) and
+ *     0.25 * sign(hm[py + 1][px] - hm[py - 1][px]) where 0 < px, py < 63 (sign(0) = 0), minus 0.5:
+ *     preds[b, c] = (x, y).  center [batch, 2], scale [batch]: DEVICE pointers, both or neither; with them
+ *     preds_orig[b, c] = trunc((p - 64 * (-center / hs + 0.5)) * hs / 64), hs = 200 * scale[b], per coordinate, in this
+ *     association, no fused multiply-add; without them zeros.  preds, preds_orig [batch, channels, 2].
+ * No allocation, no synchronisation, no global state; the kernels run on `stream`.  Dword-aligned pointers suffice.
+ */
+int fmgan_face_crop_select(int batch, int h, int w, int r);
+int fmgan_face_crop_fwd_f32(const float *img, const void *box, float *out, int batch, int h, int w, int r, void *stream);
+int fmgan_face_crop_bwd_f32(const float *grad_out, const void *box, float *grad_img, int batch, int h, int w, int r,
+                            void *stream);
+int fmgan_detector_input_f32(const float *img, float *out, int batch, long long hw, void *stream);
+int fmgan_heatmap_distance_blocks(int batch, long long m);
+int fmgan_heatmap_distance_fwd_f32(const float *a, const float *b, float *partial, int batch, long long m, void *stream);
+int fmgan_heatmap_distance_bwd_f32(const float *a, const float *b, const float *g, float *grad_a, float *grad_b, int batch,
+                                   long long m, void *stream);
+int fmgan_landmark_decode_f32(const float *hm, const float *center, const float *scale, float *preds, float *preds_orig,
+                              int batch, int channels, int h, int w, void *stream);
+
+/*
  * Inference glue of the pSp encoder's IR / IR-SE units (psp_encoder_model/encoders/helpers.py): what runs between the
  * MIOpen convolutions of a unit.  All tensors f32 in NHWC storage ([batch, h, w, channels]); a BatchNorm2d in eval mode is
  * given as its four [channels] vectors and eps and is evaluated in-kernel on every launch as
