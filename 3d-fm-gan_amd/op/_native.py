@@ -126,6 +126,7 @@ def lib():
     _sig(L.fmgan_resize_bilinear_u8, [vp] * 4 + [i] * 5 + [f, f, vp])
     _sig(L.fmgan_tensor_to_images, [vp, vp, i, i, i, f, f, vp])
     _sig(L.fmgan_tiles_to_canvas, [vp, vp, ctypes.POINTER(i)] + [i] * 6 + [f, f, vp])
+    _sig(L.fmgan_bank_gather, [vp] * 4 + [i] * 6 + [vp, ll, vp, ll, ll, i, i, ctypes.POINTER(i), i, vp, f, f, i, vp])
     _sig(L.fmgan_torgb_f32, [vp] * 6 + [i] * 4 + [f, vp])
     _sig(L.fmgan_torgb_backward_splits, [i] * 3)
     _sig(L.fmgan_torgb_backward_f32, [vp] * 6 + [i] * 4 + [f, vp])
@@ -1406,3 +1407,57 @@ def tiles_to_canvas(src, canvas, slots, tile, cent=1.0, factor=255.0 / 2.0):
                                          n, s, int(tile), nc, ch, cw, float(cent), float(factor), stream)
     check(st, 'tiles_to_canvas')
     return canvas
+
+
+BANK_GATHER_BANKS, BANK_GATHER_GROUPS = 4, 8      # csrc/image_bank.hip: BG_MAX_BANKS, BG_MAX_GROUPS
+
+
+def bank_gather(banks, index_a, index_b, offset, members, stride, groups, mean=0.5, std=0.5, out=None,
+                pixels_per_lane=0):
+    """out[s] = ((bank[k_s][i_s] / 255) - mean) / std in one launch (csrc/image_bank.hip): `banks` up to 4 uint8
+    [N_k,H,W,3] GPU tensors of one H x W (contiguous; a view into a larger storage is fine), index_a / index_b int32 GPU
+    tensors (index_b may be None), `groups` a sequence of (bank, source, swap, mul, add); returns float32
+    [len(groups) * members, 3, H, W], group after group.  The raw entry: op/image_bank.py checks index ranges and the
+    pairing on the host beforehand; the kernel skips a slot whose bank, position or image index is out of range.
+    Tensors of another dtype, device or layout are refused.  members == 0: an empty tensor, no launch."""
+    banks = list(banks)
+    groups = [tuple(int(v) for v in g) for g in groups]
+    if not 1 <= len(banks) <= BANK_GATHER_BANKS or not 1 <= len(groups) <= BANK_GATHER_GROUPS \
+            or any(len(g) != 5 for g in groups):
+        raise ValueError(f'bank_gather: {len(banks)} banks and {len(groups)} groups: 1..{BANK_GATHER_BANKS} banks and '
+                         f'1..{BANK_GATHER_GROUPS} groups of (bank, source, swap, mul, add)')
+    first = banks[0]
+    for k, t in enumerate(banks):
+        require_gpu(t, f'banks[{k}]')
+        if t.dtype != torch.uint8 or t.ndim != 4 or t.shape[3] != 3 or not t.is_contiguous() or t.device != first.device:
+            raise RuntimeError(f'bank_gather: banks[{k}] must be a contiguous uint8 [N,H,W,3] tensor on banks[0]\'s '
+                               f'device, got {t.dtype} {tuple(t.shape)} on {t.device} with strides {t.stride()}')
+        if tuple(t.shape[1:3]) != tuple(first.shape[1:3]):
+            raise ValueError(f'bank_gather: banks[{k}] holds {tuple(t.shape[1:3])} images, banks[0] '
+                             f'{tuple(first.shape[1:3])}')
+    for t, name in ((index_a, 'index_a'), (index_b, 'index_b')):
+        if t is None and name == 'index_b':
+            continue
+        require_gpu(t, name)
+        if t.dtype != torch.int32 or t.ndim != 1 or not t.is_contiguous() or t.device != first.device:
+            raise RuntimeError(f'bank_gather: {name} must be a contiguous int32 vector on the banks\' device')
+    h, w = int(first.shape[1]), int(first.shape[2])
+    members, n = int(members), int(members) * len(groups)
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=torch.float32, device=first.device)
+    else:
+        require_f32_gpu('bank_gather', ((out, 'out'),))
+        if tuple(out.shape) != (n, 3, h, w) or out.device != first.device:
+            raise ValueError(f'bank_gather: out {tuple(out.shape)} on {out.device}, expected {(n, 3, h, w)} on '
+                             f'{first.device}')
+    if n == 0:
+        return out
+    ptrs = [ptr(t) for t in banks] + [None] * (BANK_GATHER_BANKS - len(banks))
+    counts = [int(t.shape[0]) for t in banks] + [0] * (BANK_GATHER_BANKS - len(banks))
+    table = (ctypes.c_int * (5 * len(groups)))(*[v for g in groups for v in g])
+    with launching(first, 'bank_gather', (n, h, w, len(groups), int(stride))) as stream:
+        st = lib().fmgan_bank_gather(*ptrs, *counts, h, w, ptr(index_a), int(index_a.numel()), ptr(index_b),
+                                     0 if index_b is None else int(index_b.numel()), int(offset), members, int(stride),
+                                     table, len(groups), fp(out), float(mean), float(std), int(pixels_per_lane), stream)
+    check(st, 'bank_gather')
+    return out

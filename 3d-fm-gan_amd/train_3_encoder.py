@@ -58,7 +58,13 @@ def default_args(**over):
         hmap_loss_lambda=0, hmap_iter_thres=np.inf,                                                # :66-68
         ds_freq=2, ex_ds_freq=3, rec_face_reg_loss_lambda=0, ds_face_reg_loss_lambda=20, ep_face_reg_loss_lambda=100,
         val_sample_freq=1000, model_save_freq=10000, n_real_eval_faces=2, n_syn_eval_faces=2,      # :73-79
-        val_sample_tile=256)        # this build's: side of the sample sheet's tiles (the output's size for a Generator below 256)
+        val_sample_tile=256,        # this build's: side of the sample sheet's tiles (the output's size for a Generator below 256)
+        # what Dataset_DataLoader_Setup reads (:20-23, :47-52, :74-76); the reference's defaults are its authors' folders
+        size=256, synface_dir=None, extreme_pose_dir=None, ffhq_train_img_dir=None, quant_eval_img_dir=None,
+        visual_real_img_dir=None, rec_dataset_type='FFHQ', ds_dataset_type='Synthetic', ds_batch=16,
+        quant_eval_batch_size=64,
+        num_workers=8,              # this build's: worker processes per DataLoader of the non-resident path (at most 16)
+        bank_cache_dir=None)        # this build's: folder the decoded banks are kept in as .npy (None: decode every run)
     for k, v in over.items():
         setattr(a, k, v)
     return a
@@ -93,6 +99,149 @@ def Module_Fix_Setup(args, device):
         lpips_model = lpips_model.to(memory_format=torch.channels_last)
         face_rec_model = face_rec_model.to(memory_format=torch.channels_last)
     return lpips_model, face_rec_model
+
+
+class sample_data:
+    """The endless batch stream of train() (train_3_encoder.py:203-206): `while True: for batch in loader: yield batch`.
+    An object, not a generator, so that a loader that assembles training triples itself (dataset.BankLoader) keeps its
+    training_batch() behind it, with the same roll-over into the next epoch; iter(loader) is first called when the
+    first batch is asked for, as a generator would."""
+
+    def __init__(self, loader):
+        self.loader = loader
+        self._it = None
+
+    def __iter__(self):
+        return self
+
+    def _rolling(self, take):
+        if self._it is None:
+            self._it = iter(self.loader)
+        try:
+            return take()
+        except StopIteration:
+            self._it = iter(self.loader)
+            try:
+                return take()
+            except StopIteration:
+                raise RuntimeError('sample_data: the loader yields no batch') from None
+
+    def __next__(self):
+        return self._rolling(lambda: next(self._it))
+
+    def __getattr__(self, name):
+        # only where the loader has it: dataset.Data_Loading asks with hasattr
+        if name == 'training_batch' and hasattr(self.__dict__.get('loader'), 'training_batch'):
+            return lambda **kw: self._rolling(lambda: self.loader.training_batch(**kw))
+        raise AttributeError(name)
+
+
+def Visual_Evaluation_Setup(args, synface_dataset, extreme_pose_dataset, transform, device=None):
+    """The sample sets of the visual validation (train_3_encoder.py:213-223): synthetic, extreme-pose, then real."""
+    import os
+    from Evaluation.visual_eval import Get_Real_Img_Val_Sample, Get_Syn_Img_Val_Sample
+    device = device if device is not None else args.device
+    real_img_list = [os.path.join(args.visual_real_img_dir, f) for f in os.listdir(args.visual_real_img_dir)]
+    real_img_eval_samples = Get_Real_Img_Val_Sample(real_img_list, transform, args.n_real_eval_faces, device)
+    syn_img_eval_samples = Get_Syn_Img_Val_Sample(synface_dataset, args.n_syn_eval_faces, device)
+    ep_img_eval_samples = Get_Syn_Img_Val_Sample(extreme_pose_dataset, args.n_syn_eval_faces, device)
+    return syn_img_eval_samples + ep_img_eval_samples + real_img_eval_samples
+
+
+N_IMG_PER_ID = 7        # images per identity of the synthetic trees (train_3_encoder.py:271,277)
+
+
+def Dataset_DataLoader_Setup(args, device=None, resident=True):
+    """Datasets and loaders of train() (train_3_encoder.py:226-308), the reference's 9-tuple:
+    (transform, synface_dataset, extreme_pose_dataset, rec / ds / ep / pure-FFHQ training streams, rec_eval_loader,
+    edit_eval_loader), with its batch sizes, shuffling and samplers.
+
+    resident=True: every dataset is decoded once into uint8 banks on `device` (dataset.Resident; kept under
+    args.bank_cache_dir when set; folders that several datasets read are decoded once), the loaders are
+    dataset.BankLoaders and the two datasets returned are the Residents, which index like the datasets they hold.
+    resident=False: torch DataLoaders over the datasets with dataset.Transform and args.num_workers workers (at most
+    16).  A folder argument that is None leaves its loaders None.  With more than one rank each rank keeps the whole
+    bank and its samplers draw from torch.Generator().manual_seed(args.seed + rank); a single rank draws from torch's
+    global generator, as the reference does."""
+    import os
+    from torch.utils import data
+    size = args.size
+    transform = dataset.Transform(size)
+    device = torch.device(device if device is not None else getattr(args, 'device', 'cuda'))
+    generator = None
+    if D_.get_world_size() > 1:
+        generator = torch.Generator()
+        generator.manual_seed(int(getattr(args, 'seed', 0)) + D_.get_rank())
+    workers = max(0, min(int(getattr(args, 'num_workers', 8)), 16))
+    share = {}
+
+    def held(ds, name):
+        if not resident:
+            return ds
+        cache = getattr(args, 'bank_cache_dir', None)
+        if cache is not None:
+            os.makedirs(cache, exist_ok=True)
+            cache = os.path.join(cache, f'{name}_{size}')
+        return dataset.Resident(ds, size, device, cache=cache, share=share, workers=max(1, workers))
+
+    def loader(ds, batch_size, shuffle=False, sampler=None):
+        if ds is None:
+            return None
+        if not resident:
+            return data.DataLoader(ds, batch_size=batch_size, shuffle=shuffle if sampler is None else None,
+                                   sampler=sampler, num_workers=workers, generator=generator)
+        if sampler is None:
+            sampler = data.RandomSampler(ds, generator=generator) if shuffle else data.SequentialSampler(ds)
+        return dataset.BankLoader(ds, batch_size, sampler)
+
+    def stream(ld):
+        return None if ld is None else sample_data(ld)
+
+    def sub(root, name):
+        return None if root is None else os.path.join(root, name)
+
+    train_dir, eval_dir = args.ffhq_train_img_dir, args.quant_eval_img_dir
+    if train_dir is None and 'FFHQ' in (args.rec_dataset_type, args.ds_dataset_type):
+        raise ValueError('Dataset_DataLoader_Setup: an FFHQ dataset type needs args.ffhq_train_img_dir')
+    synface_dataset = held(dataset.Synthetic_Dataset(args.synface_dir, transform), 'synface')
+    extreme_pose_dataset = held(dataset.Synthetic_Dataset(args.extreme_pose_dir, transform), 'extreme_pose')
+
+    if args.rec_dataset_type == 'FFHQ':
+        recon_dataset = held(dataset.FFHQ_Dataset_Reconstruction(sub(train_dir, 'img'), sub(train_dir, 'render_img'),
+                                                                 transform), 'ffhq_train_rec')
+    elif args.rec_dataset_type == 'Synthetic':
+        recon_dataset = synface_dataset
+    else:
+        raise ValueError(f'rec_dataset_type {args.rec_dataset_type!r}: \'FFHQ\' or \'Synthetic\'')
+    rec_train_loader = loader(recon_dataset, args.rec_batch, shuffle=True)
+
+    if args.ds_dataset_type == 'FFHQ':
+        edit_train = held(dataset.FFHQ_Dataset_Editing(sub(train_dir, 'img'), sub(train_dir, 'edit_render_img'), transform,
+                                                       train=True, render_image_folder=sub(train_dir, 'render_img')),
+                          'ffhq_train_edit')
+        ds_train_loader = loader(edit_train, args.ds_batch // 2, shuffle=True)
+    elif args.ds_dataset_type == 'Synthetic':
+        ds_sampler = dataset.DualSupervisionSampler(synface_dataset, N_IMG_PER_ID, generator=generator)
+        ds_train_loader = loader(synface_dataset, args.ds_batch, sampler=ds_sampler)
+    else:
+        raise ValueError(f'ds_dataset_type {args.ds_dataset_type!r}: \'FFHQ\' or \'Synthetic\'')
+    ep_sampler = dataset.ExtremePoseDualSupervisionSampler(extreme_pose_dataset, N_IMG_PER_ID, generator=generator)
+    ep_train_loader = loader(extreme_pose_dataset, args.ds_batch * 2, sampler=ep_sampler)
+
+    pure_ffhq_loader = None
+    if train_dir is not None:
+        pure_ffhq_loader = loader(held(dataset.FFHQ_Dataset(sub(train_dir, 'img'), transform), 'ffhq_train'),
+                                  args.ds_batch // 2, shuffle=True)
+    rec_eval_loader = edit_eval_loader = None
+    if eval_dir is not None:
+        rec_eval = held(dataset.FFHQ_Dataset_Reconstruction(sub(eval_dir, 'img'), sub(eval_dir, 'render_img'), transform),
+                        'ffhq_eval_rec')
+        rec_eval_loader = loader(rec_eval, args.quant_eval_batch_size)
+        edit_eval = held(dataset.FFHQ_Dataset_Editing(sub(eval_dir, 'img'), sub(eval_dir, 'edit_render_img'), transform,
+                                                      train=False), 'ffhq_eval_edit')
+        edit_eval_loader = loader(edit_eval, args.quant_eval_batch_size // 4)
+    return (transform, synface_dataset, extreme_pose_dataset, stream(rec_train_loader), stream(ds_train_loader),
+            stream(ep_train_loader), stream(pure_ffhq_loader), rec_eval_loader, edit_eval_loader)
 
 
 def Optimizer_Initilization(args, G, E_Tsr, E_W, E_W_Plus, D, D_edit=None, ckpt=None):

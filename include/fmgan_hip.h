@@ -790,6 +790,29 @@ int fmgan_tensor_to_images(const float *in, unsigned char *out, int batch, int h
 int fmgan_tiles_to_canvas(const float *in, unsigned char *canvas, const int *slots, int n, int src, int tile,
                           int n_canvas, int canvas_h, int canvas_w, float cent, float factor, void *stream);
 
+/*
+ * Batches out of device-resident image banks (csrc/image_bank.hip), one launch:
+ *   out[s] = ((bank[k_s][i_s] / 255) - mean) / stdv      uint8 [h,w,3] -> f32 [3,h,w], the bits of fmgan_images_to_tensor
+ * Up to 4 banks uint8 [count_k,h,w,3] of one h x w (a bank with count 0 is absent).  out is f32
+ * [n_groups*members,3,h,w]: n_groups (1..8) groups of `members` images.  `groups` is a HOST array of 5 ints per group,
+ * {bank, source, swap, mul, add}, passed to the kernel by value; member j of the group reads
+ *   b = j*stride;  pos = offset + (b ^ swap);  i = index[source][pos]*mul + add;  image i of bank `bank`
+ * index_a / index_b: DEVICE int32 arrays of len_a / len_b entries (source 0 / 1; index_b may be NULL), the epoch's
+ * index list and, where an item needs one, its drawn partners; offset: the batch's first position.  swap 0/1 pairs
+ * position b with b ^ 1 (Swap_List_Pair), stride 1/2 keeps every member or the even ones.  A slot whose bank id,
+ * position or image index is out of range is skipped, its source never read and its output left as it was.
+ * Vector path (a lane owns pixels_per_lane = 4 or 16 consecutive pixels; 0 = the measured default): bank bases aligned
+ * to 4 / 16 bytes, h*w % 4 / 16 == 0 and out 16-byte aligned; otherwise one pixel per lane.  All offsets are 64-bit.
+ * members == 0: FMGAN_OK without a launch.  FMGAN_EINVAL: non-positive sizes, n_groups outside 1..8, stride not 1 or
+ * 2, swap not 0 or 1, negative counts / lengths / offset, stdv == 0, pixels_per_lane not 0, 4 or 16, null groups / out
+ * / index_a; FMGAN_EOVERFLOW beyond the 32-bit pixel / slot / grid indices.
+ */
+int fmgan_bank_gather(const void *bank0, const void *bank1, const void *bank2, const void *bank3,
+                      int count0, int count1, int count2, int count3, int h, int w,
+                      const void *index_a, long long len_a, const void *index_b, long long len_b,
+                      long long offset, int members, int stride, const int *groups, int n_groups,
+                      float *out, float mean, float stdv, int pixels_per_lane, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
