@@ -29,6 +29,8 @@
 //     the MFMA launch far less.
 // Shapes it serves: cin % 16 == 0, cout % 32 == 0, position grid at least 32 wide; everything else returns
 // FMGAN_EUNSUPPORTED and the caller keeps the fp32 kernel (the 4^2..16^2 layers: < 3 % of the FLOPs at B=8).
+// One instantiation of the split-operand contraction IS on the default inference path: conv3x3s2_mfma_bf16x3 below, the
+// first convolution of the pSp encoder's fine style heads.
 #include <type_traits>
 #include "common.h"
 
@@ -45,6 +47,7 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {   // RNE; lo
   return r;
 }
 __device__ __forceinline__ float bf16_to_f32(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
+constexpr float BF16_MAX = 3.3895313892515355e38f;      // 0x7f7f: the largest finite bf16
 
 // ------------------------------------------------------------------ weight prep
 // From the fp32 MFMA layout wt[k][tap][m] = scale * W (fmgan_modconv_weight_prep_f32, any kind: k = the conv's input
@@ -406,11 +409,23 @@ __global__ __launch_bounds__(256) void modconv_weight_to_bf16x3(const float* __r
       const int k = c * 16 + hh * 8 + jp * 2 + e;
       v[e] = (m < M && k < K) ? wt[((long long)k * ktaps + t) * M + m] : 0.f;
     }
-    const unsigned h01 = pack_bf16(v[0], v[1]);
-    const float r0 = v[0] - __uint_as_float(h01 << 16), r1 = v[1] - __uint_as_float(h01 & 0xffff0000u);
-    const unsigned m01 = pack_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(m01 << 16), s1 = r1 - __uint_as_float(m01 & 0xffff0000u);
-    const unsigned l01 = pack_bf16(s0, s1);
+    // Safe on special values: a finite weight beyond the largest bf16 (RNE would round it to Inf) gets the largest bf16
+    // as its high piece — the residual is still exact in fp32 and splits into mid + lo; Inf and NaN stay in the high
+    // piece alone (mid = lo = 0, not Inf - Inf); +-0 gives three zeros.
+    unsigned piece[3][2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const float x = v[e];
+      const bool fin = (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u;
+      const float xc = fin ? __builtin_amdgcn_fmed3f(x, -BF16_MAX, BF16_MAX) : x;
+      const unsigned hb = pack_bf16(xc, 0.f) & 0xffffu;
+      const float r = fin ? x - bf16_to_f32((unsigned short)hb) : 0.f;
+      const unsigned mb = pack_bf16(r, 0.f) & 0xffffu;
+      const float s = r - bf16_to_f32((unsigned short)mb);
+      piece[0][e] = hb; piece[1][e] = mb; piece[2][e] = pack_bf16(s, 0.f) & 0xffffu;
+    }
+    const unsigned h01 = piece[0][0] | (piece[0][1] << 16), m01 = piece[1][0] | (piece[1][1] << 16);
+    const unsigned l01 = piece[2][0] | (piece[2][1] << 16);
     const long long base = (long long)c * 3 * per_piece + (idx - (long long)c * per_piece);
     wtb[base] = h01; wtb[base + per_piece] = m01; wtb[base + 2 * per_piece] = l01;
   }
@@ -686,6 +701,299 @@ __global__ __launch_bounds__(256, 2) void modconv_mfma_bf16x3(const BFParams p) 
   }
 }
 
+// ------------------------------------------------------------------ plain 3x3 / stride 2 / pad 1 conv, split operands
+// The first convolution of a pSp style head (psp_encoders.py GradualStyleBlock): out = LeakyReLU(conv(in, W) + bias), NCHW
+// in, NCHW or NHWC out (the MIOpen tail of the head reads NHWC), no style and no demodulation (nothing to multiply: compiled out), the six-product contraction of
+// modconv_mfma_bf16x3 above with a fixed summation order (no split-K, no atomics: two calls give the same bits).
+//   * tile: 64 output channels x (4 rows x 32 columns) output positions per block; waves 2 x 2: wave (wm, wn) holds
+//     channels 32*wm.. and rows 2*wn, 2*wn+1.  A 256-position tile as above would need a 17 x 65 input patch (106 KB in
+//     three pieces): one block per CU.  This one keeps 9 x 65 = 55 KB and two blocks per CU, and 512 blocks at the heads'
+//     shape (512 -> 512, 64^2 -> 32^2, B = 8).
+//   * patch: input rows 2*y0-1 .. 2*y0+7, columns 2*x0-1 .. 2*x0+63 (origin -1 = the pad; outside the image the loads
+//     are parked out of range and read zeros), laid out per row as [even patch columns (33)][odd (32)] so that the 32
+//     lanes of a tap (input columns 2*x + kx - 1: a stride of two) read consecutive 16-byte slots as the plain mode does;
+//   * weights: NOT through LDS.  Each wave fetches its own 32 rows of the prepared image (modconv_weight_to_bf16x3) one
+//     tap ahead with one 16-byte buffer load per piece — the image is laid out as the MFMA operand, consecutive lanes on
+//     consecutive slots — which leaves the LDS to the patch.
+//   * special values: a finite activation beyond the largest bf16 is clamped for its high piece (the residual goes to
+//     mid + lo, still exact).  Inf or NaN cannot be split — (Inf, 0, 0) times a finite (bh, 0, 0) would give Inf*0 —
+//     so a block that meets one among ITS operands (patch or weight rows; found while staging, no extra pass) recomputes
+//     its tile with plain fp32 FMAs in a fixed order: the non-finite outputs are those of the fp32 products.
+struct S2Params {
+  const float* in; const unsigned short* wt; const float* bias; float* out;
+  int batch, cin, cout, h, w, oh, ow;
+  int tiles_x, tiles_y, o_tiles, mp;
+  float alpha;
+  int out_nhwc;                                          // 0: out[b][o][y][x]; 1: out[b][y][x][o] (channels_last storage)
+};
+
+struct S2Tile {
+  static constexpr int BM = 64, TH = 4, TW = 32;
+  static constexpr int PH = 2 * (TH - 1) + 3, PWP = 2 * (TW - 1) + 3, EVEN = (PWP + 1) / 2;
+  static constexpr int PLANE = PH * PWP;
+  static constexpr size_t LDS = (size_t)(3 * 2 * PLANE) * 16;
+};
+
+// the launch's plan; false when the shape is not served (32-bit buffer ranges, grid size)
+bool s2_plan(S2Params& p) {
+  if (p.batch <= 0 || p.cin <= 0 || p.cout <= 0 || p.h <= 0 || p.w <= 0) return false;
+  p.oh = (p.h - 1) / 2 + 1; p.ow = (p.w - 1) / 2 + 1;
+  p.mp = (p.cout + 31) / 32 * 32;
+  p.tiles_x = (p.ow + S2Tile::TW - 1) / S2Tile::TW;
+  p.tiles_y = (p.oh + S2Tile::TH - 1) / S2Tile::TH;
+  p.o_tiles = (p.cout + S2Tile::BM - 1) / S2Tile::BM;
+  if ((long long)p.cin * p.h * p.w * 4 >= 0xFFFFFFF0LL) return false;                      // one sample's input
+  if ((long long)((p.cin + 15) / 16) * 54 * p.mp * 16 >= 0xFFFFFFF0LL) return false;       // the weight image
+  if ((long long)p.o_tiles * p.tiles_x * p.tiles_y * p.batch > 0x7fffffffLL) return false;
+  if ((long long)p.batch * p.cout * p.oh * p.ow > (1LL << 40)) return false;
+  return true;
+}
+
+__global__ __launch_bounds__(256, 2) void conv3x3s2_mfma_bf16x3(const S2Params p) {
+  using Tile = S2Tile;
+  constexpr int BM = Tile::BM, TH = Tile::TH, TW = Tile::TW, PWP = Tile::PWP, EVEN = Tile::EVEN, PLANE = Tile::PLANE;
+  constexpr int RNP = 2;
+  constexpr int NU = (PLANE + 255) / 256;
+  extern __shared__ u32x4 smem_q[];
+  u32x4* Xs = smem_q;                                   // [3 pieces][2 k-halves][PLANE]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, khalf = lane >> 5, wm = wave & 1, wn = wave >> 1;
+  unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+  const int o_tile = lb % p.o_tiles; lb /= p.o_tiles;
+  const int tx_i = lb % p.tiles_x; lb /= p.tiles_x;
+  const int ty_i = lb % p.tiles_y;
+  const int b = lb / p.tiles_y;
+  const int o0 = o_tile * BM, x0 = tx_i * TW, y0 = ty_i * TH;
+  const int hw = p.h * p.w;
+  const float* in_b = p.in + (long long)b * p.cin * hw;
+
+  // Two accumulators per position row: the hi*hi products in one, the five correction products (2^-8 and 2^-16 of
+  // them) in the other, added once at the end — the corrections are then rounded at their own magnitude, and the main
+  // chain is one step per (chunk, tap) instead of six.
+  f32x16 acc[RNP], acc_lo[RNP];
+#pragma unroll
+  for (int g = 0; g < RNP; ++g)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[g][r] = 0.f; acc_lo[g][r] = 0.f; }
+
+  constexpr unsigned PARK = 0xFFFFFFF0u;
+  const unsigned x_bytes = (unsigned)((long long)p.cin * hw * 4);
+  const unsigned mp16 = (unsigned)p.mp * 16u;
+  const unsigned w_bytes = (unsigned)((p.cin + 15) >> 4) * 54u * mp16;
+  const auto rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in_b), 0, x_bytes, 0x00020000);
+  const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(p.wt), 0, w_bytes, 0x00020000);
+  unsigned xvo[NU];
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const int q = tid + 256 * u;                         // the LDS slot: row r, then even patch columns, then odd
+    const int r = q / PWP, t = q - r * PWP;
+    const int c = t < EVEN ? 2 * t : 2 * (t - EVEN) + 1;
+    const int y = 2 * y0 + r - 1, x = 2 * x0 + c - 1;
+    xvo[u] = (q < PLANE && y >= 0 && y < p.h && x >= 0 && x < p.w) ? (unsigned)(y * p.w + x) * 4u : PARK;
+  }
+  const int arow = o0 + wm * 32 + l31;                   // this lane's weight row (a 32-row group lies wholly inside mp or not)
+  const unsigned avo = arow < p.mp ? (unsigned)(khalf * p.mp + arow) * 16u : PARK;
+
+  float xv[NU][16];
+  auto issue_x = [&](int i0, int kc) {                   // channel i0 + kc of the patch (past cin: channel 0, dropped in commit_x)
+    const unsigned soff = i0 + kc < p.cin ? (unsigned)((i0 + kc) * hw * 4) : 0u;
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      xv[u][kc] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_x, xvo[u], soff, 0));
+  };
+  float xflag = 0.f;                                     // NaN once an activation of this block's patch is Inf or NaN
+  auto commit_x = [&](int i0) {
+    if (i0 + 16 > p.cin) {                               // the partial last chunk: zeros past cin
+#pragma unroll
+      for (int kc = 0; kc < 16; ++kc)
+        if (i0 + kc >= p.cin) {
+#pragma unroll
+          for (int u = 0; u < NU; ++u) xv[u][kc] = 0.f;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int q = tid + 256 * u;
+      if (q < PLANE) {
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          u32x4 ph, pm, pl;
+          unsigned* qh = reinterpret_cast<unsigned*>(&ph);
+          unsigned* qm = reinterpret_cast<unsigned*>(&pm);
+          unsigned* ql = reinterpret_cast<unsigned*>(&pl);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float v0 = xv[u][8 * hh + 2 * e], v1 = xv[u][8 * hh + 2 * e + 1];
+            xflag = __builtin_fmaf(v0, 0.f, xflag);
+            xflag = __builtin_fmaf(v1, 0.f, xflag);
+            const unsigned h01 = pack_bf16(__builtin_amdgcn_fmed3f(v0, -BF16_MAX, BF16_MAX),
+                                           __builtin_amdgcn_fmed3f(v1, -BF16_MAX, BF16_MAX));
+            const float r0 = v0 - __uint_as_float(h01 << 16), r1 = v1 - __uint_as_float(h01 & 0xffff0000u);
+            const unsigned m01 = pack_bf16(r0, r1);
+            const float s0 = r0 - __uint_as_float(m01 << 16), s1 = r1 - __uint_as_float(m01 & 0xffff0000u);
+            qh[e] = h01; qm[e] = m01; ql[e] = pack_bf16(s0, s1);
+          }
+          Xs[(0 * 2 + hh) * PLANE + q] = ph;
+          Xs[(1 * 2 + hh) * PLANE + q] = pm;
+          Xs[(2 * 2 + hh) * PLANE + q] = pl;
+        }
+      }
+    }
+  };
+
+  int pbase[RNP];
+#pragma unroll
+  for (int g = 0; g < RNP; ++g) pbase[g] = khalf * PLANE + 2 * (wn * RNP + g) * PWP + l31;
+
+  struct Ops { u32x4 a[3]; bf16x8 b[3][RNP]; };
+  auto fetch_a = [&](Ops& o, unsigned soff_chunk, int t) {
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc)
+      o.a[pc] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, avo, soff_chunk + (unsigned)(pc * 18 + t * 2) * mp16, 0));
+  };
+  auto fetch_b = [&](Ops& o, int t) {
+    const int ky = t / 3, kx = t - 3 * ky;
+    const int off = ky * PWP + (kx & 1) * EVEN + (kx >> 1);     // patch column 2*l31 + kx
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc)
+#pragma unroll
+      for (int g = 0; g < RNP; ++g) o.b[pc][g] = __builtin_bit_cast(bf16x8, Xs[pc * 2 * PLANE + pbase[g] + off]);
+  };
+  unsigned wflag = 0;                                    // bits 15 / 31 once a high weight piece of this wave's rows is Inf or NaN
+  constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};     // the six products, smallest first
+
+  const int chunks = (p.cin + 15) >> 4;
+#pragma unroll
+  for (int kc = 0; kc < 16; ++kc) issue_x(0, kc);
+  for (int ch = 0; ch < chunks; ++ch) {
+    const unsigned soff_chunk = (unsigned)ch * 54u * mp16;
+    Ops ops[2];
+    fetch_a(ops[0], soff_chunk, 0);        // in flight over the split
+    __syncthreads();                       // every wave is done reading the previous chunk's patch
+    commit_x(16 * ch);
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    fetch_b(ops[0], 0);
+    const int i0n = ch + 1 < chunks ? 16 * (ch + 1) : 0;       // (the last chunk loads chunk 0 again, unused: no branch)
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      __builtin_amdgcn_sched_barrier(0);
+      if (t + 1 < 9) {
+        // in this order: the wait for tap t's weights then leaves this tap's and the previous tap's patch loads in flight
+        fetch_a(ops[(t + 1) & 1], soff_chunk, t + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        issue_x(i0n, 2 * t); issue_x(i0n, 2 * t + 1);          // the next chunk's patch, two channels per tap
+        fetch_b(ops[(t + 1) & 1], t + 1);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      const Ops& o = ops[t & 1];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wflag |= ((o.a[0][e] & 0x7f807f80u) + 0x00800080u) & 0x80008000u;
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int q = 0; q < 6; ++q)
+#pragma unroll
+        for (int g = 0; g < RNP; ++g) {
+          f32x16& dst = q == 5 ? acc[g] : acc_lo[g];
+          dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, o.a[PA[q]]), o.b[PB[q]][g], dst, 0, 0, 0);
+        }
+      __builtin_amdgcn_s_setprio(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int g = 0; g < RNP; ++g)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[g][r] = __fadd_rn(acc[g][r], acc_lo[g][r]);
+
+  float* out_b = p.out + (long long)b * p.cout * p.oh * p.ow;
+  const float alpha = p.alpha;
+  const long long ost_o = p.out_nhwc ? 1 : (long long)p.oh * p.ow, ost_p = p.out_nhwc ? p.cout : 1;   // channel / position strides
+  if (__syncthreads_or((xflag != xflag) | (wflag != 0u))) {
+    // Inf / NaN among this block's operands: the tile again as fp32 products.  Thread = one position x 32 channels.
+    const int pp = tid & 127, oy = y0 + (pp >> 5), ox = x0 + (pp & 31);
+    if (oy >= p.oh || ox >= p.ow) return;
+    for (int oo = 0; oo < 32; ++oo) {
+      const int o = o0 + (tid >> 7) * 32 + oo;
+      if (o >= p.cout) return;
+      float s = 0.f;
+      for (int i = 0; i < p.cin; ++i) {
+        const long long slot0 = (long long)(i >> 4) * 54 * p.mp;
+        const int hh = (i >> 3) & 1, j = i & 7;
+        for (int t = 0; t < 9; ++t) {
+          const int y = 2 * oy + t / 3 - 1, x = 2 * ox + t % 3 - 1;
+          const float xin = (y >= 0 && y < p.h && x >= 0 && x < p.w) ? in_b[(long long)i * hw + y * p.w + x] : 0.f;
+          float wv = 0.f;
+#pragma unroll
+          for (int pc = 0; pc < 3; ++pc)     // hi + mid + lo is the fp32 weight again, exactly
+            wv += bf16_to_f32(p.wt[((slot0 + (long long)(pc * 18 + t * 2 + hh) * p.mp + o) << 3) + j]);
+          s = __builtin_fmaf(wv, xin, s);
+        }
+      }
+      const float v = __fadd_rn(s, p.bias ? p.bias[o] : 0.f);
+      out_b[o * ost_o + ((long long)oy * p.ow + ox) * ost_p] = v > 0.f ? v : v * alpha;
+    }
+    return;
+  }
+
+  // ---- epilogue: bias, LeakyReLU (fused_leaky_relu's order with scale 1); NCHW: 32 lanes on 32 consecutive x; NHWC: a
+  // lane's four consecutive channels (r & 3) as one 16-byte store, the two k-halves and four row groups of a position
+  // filling 128 consecutive bytes
+  const int orow = o0 + wm * 32 + 4 * khalf;            // row r of the 32-row group adds (r&3) + 8*(r>>2)
+  float bias_r[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) bias_r[r] = p.bias ? p.bias[min(orow + (r & 3) + 8 * (r >> 2), p.cout - 1)] : 0.f;
+#pragma unroll
+  for (int g = 0; g < RNP; ++g) {
+    const int py_ = y0 + wn * RNP + g, px_ = x0 + l31;
+    if (py_ >= p.oh || px_ >= p.ow) continue;
+    float* dpos = out_b + ((long long)py_ * p.ow + px_) * ost_p;
+    float v[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float t = __fadd_rn(acc[g][r], bias_r[r]);
+      v[r] = t > 0.f ? t : t * alpha;
+    }
+    if (p.out_nhwc && (p.cout & 3) == 0) {               // o and cout are multiples of 4: a quad is inside or outside
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int o = orow + 8 * j;
+        if (o < p.cout) {
+          f32x4 q4 = {v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
+          *reinterpret_cast<f32x4*>(dpos + o) = q4;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int o = orow + (r & 3) + 8 * (r >> 2);
+        if (o < p.cout) dpos[o * ost_o] = v[r];
+      }
+    }
+  }
+}
+
+int conv3x3s2_bf16x3(const float* in, const void* wt, const float* bias, float* out, int batch, int cin, int cout, int h,
+                     int w, float alpha, int out_nhwc, hipStream_t s) {
+  if (batch < 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || (out_nhwc != 0 && out_nhwc != 1)) return FMGAN_EINVAL;
+  if (batch == 0) return FMGAN_OK;
+  S2Params p{};
+  p.in = in; p.wt = (const unsigned short*)wt; p.bias = bias; p.out = out;
+  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w; p.alpha = alpha; p.out_nhwc = out_nhwc;
+  if (!s2_plan(p)) return FMGAN_EUNSUPPORTED;
+  if (!in || !wt || !out) return FMGAN_EINVAL;
+  if (out_nhwc && (cout & 3) == 0 && ((uintptr_t)out & 15)) return FMGAN_EINVAL;       // the 16-byte stores
+  static bool attr = false;     // > 48 KB of dynamic LDS needs the opt-in once (idempotent)
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)conv3x3s2_mfma_bf16x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2Tile::LDS);
+    attr = true;
+  }
+  const long long blocks = (long long)p.o_tiles * p.tiles_x * p.tiles_y * p.batch;
+  hipLaunchKernelGGL(conv3x3s2_mfma_bf16x3, dim3((unsigned)blocks), dim3(256), S2Tile::LDS, s, p);
+  return fmgan_check_launch();
+}
+
 // One launch for every tile of both contractions: the block grid, the LDS opt-in and the kernel, all from the tile.
 template <int PIECES, int MODE, int RM, int RNP>
 int launch_tile(BFParams& p, hipStream_t s) {
@@ -811,4 +1119,16 @@ extern "C" int fmgan_modconv2d_bf16x3(const float* in, const void* wt_split, con
                                       void* stream) {
   return modconv2d_bf(3, in, wt_split, style, demod, out, batch, cin, cout, h, w, mode, noise, noise_weight, bias,
                       noise_batch, fuse_act, alpha, act_scale, out_plane_stride, out_row_stride, (hipStream_t)stream);
+}
+
+// ---- pSp style heads: plain 3x3 / stride 2 / pad 1 conv + bias + LeakyReLU on the split-operand contraction
+extern "C" int fmgan_conv3x3s2_bf16x3_supported(int batch, int cin, int cout, int h, int w) {
+  S2Params p{};
+  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
+  return s2_plan(p) ? 1 : 0;
+}
+
+extern "C" int fmgan_conv3x3s2_bf16x3_f32(const float* in, const void* wt_split, const float* bias, float* out, int batch,
+                                          int cin, int cout, int h, int w, float alpha, int out_nhwc, void* stream) {
+  return conv3x3s2_bf16x3(in, wt_split, bias, out, batch, cin, cout, h, w, alpha, out_nhwc, (hipStream_t)stream);
 }

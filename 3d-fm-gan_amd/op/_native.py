@@ -110,6 +110,8 @@ def lib():
     _sig(L.fmgan_modconv_weight_to_bf16x3, [vp, vp, i, i, i, vp])
     _sig(L.fmgan_modconv2d_bf16x3_supported, [i] * 6)
     _sig(L.fmgan_modconv2d_bf16x3, [vp] * 5 + [i] * 6 + [vp] * 3 + [i, i, f, f, ll, i, vp])
+    _sig(L.fmgan_conv3x3s2_bf16x3_supported, [i] * 5)
+    _sig(L.fmgan_conv3x3s2_bf16x3_f32, [vp] * 4 + [i] * 5 + [f, i, vp])
     _sig(L.fmgan_modconv2d_rgb_fusable, [i] * 5)
     _sig(L.fmgan_modconv2d_select, [i] * 8 + [ctypes.POINTER(i)] * 5)
     _sig(L.fmgan_modconv2d_tiles, [ctypes.POINTER(i), i])
@@ -1159,6 +1161,37 @@ def modconv_weight_to_bf16x3(wt):
     with on_device(wt) as stream:
         check(lib().fmgan_modconv_weight_to_bf16x3(fp(wt), ptr(wts), cin, cout, taps, stream), 'modconv_weight_to_bf16x3')
     return wts
+
+
+def conv_weight_to_bf16x3(weight):
+    """A Conv2d weight [cout, cin, 3, 3] (any memory format) -> the split-operand image of conv3x3s2_bf16x3: the
+    [cin, 9, cout] order, then modconv_weight_to_bf16x3.  One bracket ('conv_weight_bf16x3') round the two steps."""
+    require_gpu(weight, 'weight')
+    cout, cin, kh, kw = weight.shape
+    with launching(weight, 'conv_weight_bf16x3', (cout, cin, kh * kw)):
+        wt = weight.detach().permute(1, 2, 3, 0).reshape(cin, kh * kw, cout).contiguous()
+        return modconv_weight_to_bf16x3(wt)
+
+
+def conv3x3s2_bf16x3_supported(batch, cin, cout, h, w):
+    return bool(lib().fmgan_conv3x3s2_bf16x3_supported(int(batch), int(cin), int(cout), int(h), int(w)))
+
+
+def conv3x3s2_bf16x3(x, wts, bias, cout, alpha=0.01, channels_last=False):
+    """LeakyReLU(conv3x3(x, stride 2, pad 1) + bias) with fp32 operands split into three bf16 pieces (fp32 accumulation).
+    x [B,cin,H,W] f32 NCHW-contiguous, wts = conv_weight_to_bf16x3(weight), bias [cout] or None.  Returns
+    [B,cout,(H-1)//2+1,(W-1)//2+1] — NCHW-contiguous, or in channels_last storage (written so by the kernel: what the
+    MIOpen tail of a style head reads) — or None where the library declines the shape."""
+    require_gpu(x, 'input')
+    if not x.is_contiguous():
+        raise RuntimeError(f'conv3x3s2_bf16x3: input must be NCHW-contiguous, got strides {x.stride()}')
+    b, cin, h, w = x.shape
+    out = torch.empty((b, cout, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    with launching(x, 'conv3x3s2_bf16x3', (b, cin, cout, h, w)) as stream:
+        st = lib().fmgan_conv3x3s2_bf16x3_f32(fp(x), ptr(wts), fp(bias), fp(out), b, cin, cout, h, w, float(alpha),
+                                              int(bool(channels_last)), stream)
+    return out if served(st, 'conv3x3s2_bf16x3') else None
 
 
 def current_modconv_precision():

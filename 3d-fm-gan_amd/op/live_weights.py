@@ -11,6 +11,8 @@ live storage in one launch (~240 MB of traffic for Generator(1024): tens of micr
 elementwise launches per forward the reference spends).  Outside such a forward (a bare StyledConv call, training with
 autograd) every module derives what it needs on the spot.
 """
+import weakref
+
 import numpy as np
 import torch
 
@@ -136,3 +138,35 @@ def live(module):
     if lv is not None and lv[0].active and not torch.is_grad_enabled():
         return lv[1], lv[2]
     return None
+
+
+_SPLIT = weakref.WeakKeyDictionary()      # Conv2d module -> (key, image, built event, stream); not copied with the module
+
+
+def split_conv_weight(conv):
+    """The three-piece bf16 image of `conv.weight` for _native.conv3x3s2_bf16x3, kept per module and rebuilt only when the
+    parameter's storage, device or autograd version changes: an optimizer step, `copy_` (load_state_dict) and any other
+    in-place update of the PARAMETER bump `_version`; `p.data = ...` changes the storage.  (A write through `p.data` in
+    place changes neither — see the module docstring; such an updater of an encoder calls drop_split_weight.  The
+    encoder's inference weights come from load_state_dict.)"""
+    w = conv.weight
+    key = (w.data_ptr(), w._version, w.device, tuple(w.shape), tuple(w.stride()))
+    kept = _SPLIT.get(conv)
+    stream = torch.cuda.current_stream(w.device)
+    if kept is None or kept[0] != key:
+        img = _native.conv_weight_to_bf16x3(w)
+        built = torch.cuda.Event()
+        built.record(stream)
+        kept = (key, img, built, stream)
+        _SPLIT[conv] = kept
+    elif kept[3] != stream:
+        stream.wait_event(kept[2])          # built on another stream (the heads run on side streams)
+    return kept[1]
+
+
+def drop_split_weight(conv=None):
+    """Forget the kept image of `conv` (None: of every module)."""
+    if conv is None:
+        _SPLIT.clear()
+    else:
+        _SPLIT.pop(conv, None)

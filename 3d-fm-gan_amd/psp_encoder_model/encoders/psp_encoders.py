@@ -19,7 +19,8 @@ from . import helpers
 from .helpers import PReLU, bottleneck_IR, bottleneck_IR_SE, get_blocks
 from stylegan2 import EqualLinear
 from op import fused_leaky_relu
-from op.live_weights import LiveWeights
+from op import _native
+from op.live_weights import LiveWeights, split_conv_weight
 from Util.streams import overlap_ok, run_deferred, side_streams
 
 # Inference: the style heads are independent of each other and each ends in a tail of tiny launches (conv at 16^2 ... 1^2
@@ -41,6 +42,18 @@ HEAD_STREAMS = int(os.environ.get('FMGAN_PSP_STREAMS', '2'))
 # done.  The per-head form therefore stays the default.
 GROUP_HEADS = os.environ.get('FMGAN_PSP_GROUPED', '0') == '1'
 
+# Inference: the FIRST convolution of a style head (3x3, stride 2, pad 1, 512 -> 512 on the level's shared feature map:
+# 425 of the heads' 627 GFLOP per step at B=8 are the eleven 64^2 -> 32^2 ones) runs on the split-operand contraction of
+# csrc/modconv_bf16.hip — each fp32 operand as three bf16 pieces, six v_mfma_f32_32x32x16_bf16 per product, fp32
+# accumulation, fixed summation order — with bias + LeakyReLU in its epilogue, instead of MIOpen's fp32 implicit GEMM
+# (+ fused_bias_act).  FMGAN_PSP_HEADS_X3=0 keeps MIOpen.  It serves the levels whose OUTPUT is at least
+# X3_MIN_OUT wide (profiles/psp_heads_x3.md: a 16-wide output fills half of the kernel's 32-column tile).
+HEADS_X3 = os.environ.get('FMGAN_PSP_HEADS_X3', '1') == '1'
+X3_MIN_OUT = 32
+# True: the kernel writes its output in channels_last storage, what the MIOpen tail reads (False: NCHW, which aten then
+# converts per head — 32 us each at B=8, profiles/psp_heads_x3.md)
+X3_TAIL_CHANNELS_LAST = True
+
 _TAPS = {18: (3, 5, 7), 50: (6, 20, 23)}   # units whose outputs feed the pyramid (psp_encoders.py:105-108)
 
 
@@ -58,11 +71,34 @@ class GradualStyleBlock(Module):
         self.convs = nn.Sequential(*layers)
         self.linear = EqualLinear(out_c, out_c, lr_mul=1)
 
-    def forward(self, x):
+    def x3_serves(self, x):
+        """Does the first convolution of this head run on conv3x3s2_bf16x3 for the feature map x?  (inference, fp32)"""
+        if not (HEADS_X3 and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()):
+            return False
+        conv = self.convs[0]
+        if conv.weight.dtype != torch.float32 or conv.bias is None or (x.shape[3] - 1) // 2 + 1 < X3_MIN_OUT:
+            return False
+        return _native.conv3x3s2_bf16x3_supported(x.shape[0], conv.in_channels, conv.out_channels, x.shape[2], x.shape[3])
+
+    def _first_x3(self, x_nchw):
+        """convs[0] + LeakyReLU on the split-operand kernel; the weight image is kept per parameter (live_weights)."""
+        conv, act = self.convs[0], self.convs[1]
+        y = _native.conv3x3s2_bf16x3(x_nchw, split_conv_weight(conv), conv.bias, conv.out_channels, act.negative_slope,
+                                     channels_last=X3_TAIL_CHANNELS_LAST)
+        if y is None:
+            raise RuntimeError('conv3x3s2_bf16x3 declined a shape its query accepted')
+        return y
+
+    def forward(self, x, x_nchw=None):
+        """x_nchw: the NCHW-contiguous copy of x, when the caller shares one among the heads of a pyramid level."""
         if x.is_cuda and x.dtype == torch.float32:
+            convs = list(zip(self.convs[0::2], self.convs[1::2]))
+            if self.x3_serves(x):
+                x = self._first_x3(x.contiguous() if x_nchw is None else x_nchw)
+                convs = convs[1:]
             # conv, then bias + LeakyReLU(0.01) in ONE pass of the HIP fused_bias_act kernel (the same arithmetic as
             # MIOpen's separate bias add followed by aten leaky_relu: (v + b) > 0 ? . : 0.01 * .  — bit-identical).
-            for conv, act in zip(self.convs[0::2], self.convs[1::2]):
+            for conv, act in convs:
                 y = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
                 if y.is_contiguous(memory_format=torch.channels_last) and not y.is_contiguous():
                     n, c, h, w = y.shape                       # NHWC storage: channel is the fastest dimension
@@ -231,14 +267,20 @@ class GradualStyleEncoder(Module):
         if HEAD_STREAMS > 1 and overlap_ok(x):
             streams = side_streams(x.device, HEAD_STREAMS, 'psp-heads')
 
-            def head(j, feat):
-                return run_deferred(streams[j % HEAD_STREAMS], self.styles[j], feat)
+            def head(j, feat, nchw):
+                return run_deferred(streams[j % HEAD_STREAMS], self.styles[j], feat, nchw)
         else:
-            def head(j, feat):
-                return (lambda: None), self.styles[j](feat)
-        latents = [head(j, c3) for j in range(min(self.coarse_ind, self.style_count))]
+            def head(j, feat, nchw):
+                return (lambda: None), self.styles[j](feat, nchw)
+
+        def level(js, feat):
+            # the level's feature map NHWC -> NCHW ONCE for all its heads that take the split-operand first conv
+            js = list(js)
+            nchw = feat.contiguous() if any(self.styles[j].x3_serves(feat) for j in js) else None
+            return [head(j, feat, nchw) for j in js]
+        latents = level(range(min(self.coarse_ind, self.style_count)), c3)
         p2 = self._upsample_add(c3, self.latlayer1(c2))
-        latents += [head(j, p2) for j in range(self.coarse_ind, min(self.middle_ind, self.style_count))]
+        latents += level(range(self.coarse_ind, min(self.middle_ind, self.style_count)), p2)
         p1 = self._upsample_add(p2, self.latlayer2(c1))
-        latents += [head(j, p1) for j in range(self.middle_ind, self.style_count)]
+        latents += level(range(self.middle_ind, self.style_count), p1)
         return latents

@@ -647,6 +647,22 @@ int fmgan_modconv2d_bf16x3(const float *in, const void *wt_split, const float *s
                            long long out_plane_stride, int out_row_stride, void *stream);
 
 /*
+ * The first convolution of a pSp style head (psp_encoders.py GradualStyleBlock) on the same split-operand contraction:
+ *     out[b,o,y,x] = lrelu(bias[o] + sum_{i,ky,kx} W[o,i,ky,kx] * in[b,i,2y+ky-1,2x+kx-1]),  lrelu(v) = v > 0 ? v : alpha*v
+ * a plain 3x3 convolution with stride 2 and zero padding 1, NCHW fp32 in and out ([batch,cout,(h-1)/2+1,(w-1)/2+1]), no
+ * style and no demodulation; bias may be NULL.  out_nhwc = 1 writes the same values as out[b][y][x][o] (channels_last
+ * storage, what MIOpen's NHWC kernels read; out 16-byte aligned when cout % 4 == 0), 0 as out[b][o][y][x].  wt_split = fmgan_modconv_weight_to_bf16x3 of W in [cin][9][cout] order.
+ * Fixed summation order (no split-K, no atomics): two calls give the same bits.  A finite operand never yields an
+ * infinite piece; a block that finds Inf or NaN among its operands recomputes its tile as fp32 products, so non-finite
+ * values propagate as they do in an fp32 convolution.  Any cin, cout, h, w >= 1 within 32-bit buffer ranges:
+ * fmgan_conv3x3s2_bf16x3_supported answers from the launch's plan, and the launch returns FMGAN_EUNSUPPORTED (and
+ * launches nothing) where it says 0.
+ */
+int fmgan_conv3x3s2_bf16x3_supported(int batch, int cin, int cout, int h, int w);
+int fmgan_conv3x3s2_bf16x3_f32(const float *in, const void *wt_split, const float *bias, float *out,
+                               int batch, int cin, int cout, int h, int w, float alpha, int out_nhwc, void *stream);
+
+/*
  * Plain (mode 0) modulated conv with the FOLLOWING ToRGB layer folded into its epilogue.  In the reference these are
  * two modules and three HBM passes over the activation (StyledConv conv2 -> ToRGB, stylegan2.py:646-651 calling
  * :360-376 and :393-404).  When one block holds every output channel of its pixels (cout <= the tile's channel
