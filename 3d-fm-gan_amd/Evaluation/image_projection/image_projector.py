@@ -14,8 +14,10 @@ What is different, on purpose:
     state_dict key) and its mapping network is called directly (the reference wraps it in nn.DataParallel);
   * the Generator's requires_grad flags and training mode are restored on return (the reference leaves it frozen and
     in eval mode); its parameters are never written;
-  * opt='LBFGS' raises NotImplementedError: the reference's third-party FullBatchLBFGS is not provided.  opt='Adam' is
-    the reference's; any torch.optim.Optimizer class or factory may be passed instead of a name;
+  * the reference's first optimiser, its third-party FullBatchLBFGS(lr=1), is LBFGS.py here and is asked for as
+    opt='FullBatchLBFGS'.  The reference's spelling opt='LBFGS' still raises NotImplementedError (its message names the
+    new spelling).  opt='Adam' is the reference's; any torch.optim.Optimizer class or factory may be passed instead of
+    a name, lambda p: LBFGS.FullBatchLBFGS(p, lr=1) among them;
   * `criterion` None builds project.ImageReconstructionLoss(loss='mse+lpips') without pretrained LPIPS weights (a load
     figure: see project.py); pass a criterion built with percept= for real scores.
 """
@@ -24,7 +26,7 @@ import math
 import numpy as np
 import torch
 
-from . import project
+from . import LBFGS, project
 
 NUM_AVG_SAMPLES = 1000
 
@@ -63,13 +65,17 @@ def Image_Projector(generator, device, per_layer_W, target_im, opt, num_iters=50
     the image after num_iters + 1 optimisation steps."""
     if opt == 'LBFGS':
         raise NotImplementedError("Image_Projector: opt='LBFGS' is the reference's third-party FullBatchLBFGS, which is "
-                                  "not provided; use opt='Adam' or pass a torch.optim.Optimizer class")
-    if opt == 'Adam':
+                                  "asked for as opt='FullBatchLBFGS' here; or use opt='Adam' or pass a "
+                                  "torch.optim.Optimizer class")
+    if opt == 'FullBatchLBFGS':
+        make_optimizer = lambda params: LBFGS.FullBatchLBFGS(params, lr=1)     # noqa: E731
+    elif opt == 'Adam':
         make_optimizer = lambda params: torch.optim.Adam(params, lr=0.01)      # noqa: E731
     elif callable(opt):
         make_optimizer = opt
     else:
-        raise ValueError(f"Image_Projector: opt {opt!r}: expected 'Adam' or a callable params -> torch.optim.Optimizer")
+        raise ValueError(f"Image_Projector: opt {opt!r}: expected 'FullBatchLBFGS', 'Adam' or a callable params -> "
+                         f"torch.optim.Optimizer")
     g = _plain(generator)
     params = list(generator.parameters())
     was = [p.requires_grad for p in params], generator.training

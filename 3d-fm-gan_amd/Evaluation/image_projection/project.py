@@ -5,7 +5,8 @@ Evaluation/image_projection/project/__init__.py:125-129, 147-221, 228-333).
                                         below the loss type's threshold mse_T, LPIPS of the clamped images at 256^2,
                                         summed over the batch
     _adjust_learning_rate    :228-234   cosine ramp-down over the last quarter, linear ramp-up over the first 5 %
-    optimize                 :245-333   iterations + 1 steps of a torch optimiser on the Generator's inputs
+    optimize                 :245-333   iterations + 1 steps of a torch optimiser, or of LBFGS.FullBatchLBFGS (:274-285),
+                                        on the Generator's inputs
 
 What is different, on purpose:
   * the image stage of the criterion (difference, square, mask, sum; clamp, reduction to 256^2, ScalingLayer, NHWC) is
@@ -30,8 +31,7 @@ Reference behaviour kept on purpose:
   * the mask is handed to the perceptual module as its `normalize` argument, which fails for a mask of more than one
     element: LPIPS together with a mask raises here too, with a message that says why;
   * optimize runs iterations + 1 steps, and the learning rate is 0 at the first and the last of them.
-Not provided: the third-party FullBatchLBFGS optimiser and the scipy branch of optimize, the alex / squeeze nets,
-VGGPerceptualLoss (its weights are a download).
+Not provided: the scipy branch of optimize, the alex / squeeze nets, VGGPerceptualLoss (its weights are a download).
 """
 import math
 import os
@@ -39,6 +39,7 @@ import os
 import torch
 
 from lpips import scaling_layer_of
+from . import LBFGS
 from op.projection_loss import TARGET, projection_stage, projection_stage_serves, projection_trunk_input
 
 # Image stage of the criterion on the HIP kernels where they serve; False keeps the aten composite.
@@ -140,9 +141,11 @@ def _print_loss(loss, iteration, iterations, print_iterations):
 def optimize(model, input_kwargs, targets, criterion, optimizer, iterations, print_iterations=10, device=None,
              history=None):
     """iterations + 1 steps of `optimizer` on the tensors of input_kwargs, which model(**input_kwargs) turns into the
-    image that criterion(image, targets) scores; returns the last loss as a numpy scalar.  torch.optim.LBFGS runs with a
+    image that criterion(image, targets) scores; returns the last loss as a numpy scalar.  LBFGS.FullBatchLBFGS runs its
+    line search with a closure that returns the loss without its gradients and max_ls 10; torch.optim.LBFGS runs with a
     closure; every other torch optimiser (Adam, SGD, ...) with _adjust_learning_rate from its initial rate.  history: a
-    list that receives (learning rate, detached loss) per step (not in the reference; the losses stay on the device).
+    list that receives (learning rate, or FullBatchLBFGS's step length, and the detached loss) per step (not in the
+    reference; the losses stay on the device).
     print_iterations 0 prints nothing; printing a loss synchronises with the host."""
     for key in input_kwargs:
         value = input_kwargs[key]
@@ -153,10 +156,22 @@ def optimize(model, input_kwargs, targets, criterion, optimizer, iterations, pri
                 if torch.is_tensor(v):
                     v.requires_grad = True
     if not isinstance(optimizer, torch.optim.Optimizer):
-        raise ValueError('Unsupported optimizer: a torch.optim.Optimizer is expected (the third-party FullBatchLBFGS and '
-                         'the scipy objective of the reference are not provided). Documentation of supported optimizers '
+        raise ValueError('Unsupported optimizer: a torch.optim.Optimizer or LBFGS.FullBatchLBFGS is expected (the scipy '
+                         'objective of the reference is not provided). Documentation of supported optimizers '
                          'can be found here:\n\nhttps://pytorch.org/docs/stable/optim.html\n')
-    if isinstance(optimizer, torch.optim.LBFGS):
+    if isinstance(optimizer, LBFGS.FullBatchLBFGS):
+        def closure():
+            optimizer.zero_grad()
+            return criterion(model(**input_kwargs), targets)
+        loss = closure()
+        loss.backward()
+        for i in range(iterations + 1):
+            options = {'closure': closure, 'current_loss': loss, 'max_ls': 10}
+            loss, _, t, _, _, _, _, _ = optimizer.step(options)
+            _print_loss(loss, i, iterations, print_iterations)
+            if history is not None:
+                history.append((t, loss.detach()))
+    elif isinstance(optimizer, torch.optim.LBFGS):
         for i in range(iterations + 1):
             def closure():
                 optimizer.zero_grad()

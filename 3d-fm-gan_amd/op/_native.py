@@ -138,6 +138,12 @@ def lib():
     _sig(L.fmgan_style_bank_entry_bytes, [])
     _sig(L.fmgan_style_bank_f32, [vp, i, vp, vp, i, i, i, vp, vp])
     _sig(L.fmgan_demod_bank_f32, [vp, i, vp, i, vp, vp])
+    _sig(L.fmgan_lbfgs_pair_blocks, [ll], ll)
+    _sig(L.fmgan_lbfgs_pair_f32, [vp, i] + [vp] * 7 + [ll, i, f, i, vp])
+    _sig(L.fmgan_lbfgs_coeffs_f64, [vp] * 5 + [ll, i, f, f, i, vp])
+    _sig(L.fmgan_lbfgs_direction_f32, [vp] * 9 + [ll, i, vp])
+    _sig(L.fmgan_lbfgs_update_f32, [vp, i, vp, f, ll, vp])
+    _sig(L.fmgan_lbfgs_gather_f32, [vp, i] + [vp] * 4 + [ll, vp])
     if L.fmgan_abi_version() != 1:
         raise RuntimeError('libfmgan_hip.so ABI version mismatch')
     _lib = L
@@ -1494,3 +1500,50 @@ def bank_gather(banks, index_a, index_b, offset, members, stride, groups, mean=0
                                      table, len(groups), fp(out), float(mean), float(std), int(pixels_per_lane), stream)
     check(st, 'bank_gather')
     return out
+
+
+# ----------------------------------------------------------------------------- L-BFGS (csrc/lbfgs.hip)
+# The five launches of a fused FullBatchLBFGS step over the buffers of an op.lbfgs.FusedState `s` (it has made the device,
+# dtype and layout checks); `table`: the ctypes segment table of lbfgs_segments.
+def lbfgs_segments(params):
+    """(table, nseg) for the entry points: 3 long long per parameter, {parameter address, gradient address or 0, numel}."""
+    vals = []
+    for p in params:
+        vals += [p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr(), p.numel()]
+    return (ctypes.c_longlong * len(vals))(*vals), len(vals) // 3
+
+
+def lbfgs_pair(s, table, nseg, t, has_pair):
+    with launching(s.g, 'lbfgs_pair', (s.n, s.m, bool(has_pair))) as stream:
+        st = lib().fmgan_lbfgs_pair_f32(ctypes.addressof(table), nseg, fp(s.g), fp(s.g_prev), fp(s.d), fp(s.S), fp(s.Y),
+                                        s.state.data_ptr(), s.partial.data_ptr(), s.n, s.m, float(t), int(has_pair),
+                                        stream)
+    check(st, 'lbfgs_pair')
+
+
+def lbfgs_coeffs(s, t, eps, has_pair):
+    with launching(s.g, 'lbfgs_coeffs', (s.n, s.m, bool(has_pair))) as stream:
+        st = lib().fmgan_lbfgs_coeffs_f64(s.partial.data_ptr(), s.G.data_ptr(), s.state.data_ptr(), s.record.data_ptr(),
+                                          s.coef.data_ptr(), s.n, s.m, float(t), float(eps), int(has_pair), stream)
+    check(st, 'lbfgs_coeffs')
+
+
+def lbfgs_direction(s):
+    with launching(s.g, 'lbfgs_direction', (s.n, s.m)) as stream:
+        st = lib().fmgan_lbfgs_direction_f32(s.coef.data_ptr(), s.state.data_ptr(), fp(s.S), fp(s.Y), fp(s.g),
+                                             fp(s.g_prev), fp(s.d), s.partial.data_ptr(), s.record.data_ptr(), s.n, s.m,
+                                             stream)
+    check(st, 'lbfgs_direction')
+
+
+def lbfgs_update(s, table, nseg, a):
+    with launching(s.g, 'lbfgs_update', (s.n,)) as stream:
+        st = lib().fmgan_lbfgs_update_f32(ctypes.addressof(table), nseg, fp(s.d), float(a), s.n, stream)
+    check(st, 'lbfgs_update')
+
+
+def lbfgs_gather(s, table, nseg):
+    with launching(s.g, 'lbfgs_gather', (s.n,)) as stream:
+        st = lib().fmgan_lbfgs_gather_f32(ctypes.addressof(table), nseg, fp(s.g_new), fp(s.d), s.partial.data_ptr(),
+                                          s.record.data_ptr(), s.n, stream)
+    check(st, 'lbfgs_gather')

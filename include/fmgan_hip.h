@@ -829,6 +829,44 @@ int fmgan_bank_gather(const void *bank0, const void *bank1, const void *bank2, c
                       long long offset, int members, int stride, const int *groups, int n_groups,
                       float *out, float mean, float stdv, int pixels_per_lane, void *stream);
 
+/*
+ * L-BFGS on flat float32 state, the direction computed in Gram space (csrc/lbfgs.hip; the fused path of
+ * Evaluation/image_projection/LBFGS.py's FullBatchLBFGS.step).  The caller owns, on one device:
+ *   g, g_prev, d, g_new   f32 [n]           gradient, previous gradient, direction, trial gradient
+ *   S, Y                  f32 [m + 1, n]    ring of the steps s and the gradient differences y; the slot after the
+ *                                           head is spare and receives the candidate pair
+ *   G                     f64 [D, D]        D = 2 (m + 1) + 1: products of s slots, y slots and g, kept between steps
+ *   state                 int32 [m + 2]     head slot, live pairs, then the live slots, oldest first
+ *   record                f64 [8]           accepted, H_diag, ys, sBs, g.d, g_new.d, g.g, yy
+ *   coef                  f64 [D]           the direction's coefficients in slot order
+ *   partial               f64 [max(fmgan_lbfgs_pair_blocks(n) * (6 m + 7), 2048)]
+ * `segs` is a HOST table of 3 long long per parameter tensor, {address of the f32 parameter, address of its f32 gradient
+ * or 0 (read as zeros), numel}, nseg in 1..64, the numels adding up to n; it travels to the kernels by value.
+ * Every sum is float64, added in a fixed order without atomics: bit-reproducible.
+ *   fmgan_lbfgs_pair_f32      g = gradients; with has_pair also the candidate s = t d, y = g - g_prev into the spare slot;
+ *                             partials of every product the Gram rows of s, y and g need, of ys, yy and s.g_prev
+ *   fmgan_lbfgs_coeffs_f64    one block: finalises the partials, accepts the pair iff ys > eps * sBs with
+ *                             sBs = -t (s.g_prev) (then: head advances, G gains the pair's rows, H_diag = ys / yy),
+ *                             runs the two-loop recursion on coefficient vectors and writes coef and record[0..3, 6, 7]
+ *   fmgan_lbfgs_direction_f32 d = sum coef * basis, g_prev = g, record[4] = g.d (measured from the vectors)
+ *   fmgan_lbfgs_update_f32    param += a d through the table (one fused multiply-add per element)
+ *   fmgan_lbfgs_gather_f32    g_new = gradients, record[5] = g_new.d
+ * FMGAN_EINVAL: null pointers, n <= 0, nseg outside 1..64, numels that do not add up to n; FMGAN_EUNSUPPORTED: m
+ * outside 1..32; FMGAN_EOVERFLOW: more tiles than a grid holds.
+ */
+long long fmgan_lbfgs_pair_blocks(long long n);
+int fmgan_lbfgs_pair_f32(const long long *segs, int nseg, float *g, const float *g_prev, const float *d, float *S,
+                         float *Y, const void *state, double *partial, long long n, int m, float t, int has_pair,
+                         void *stream);
+int fmgan_lbfgs_coeffs_f64(const double *partial, double *G, void *state, double *record, double *coef, long long n,
+                           int m, float t, float eps, int has_pair, void *stream);
+int fmgan_lbfgs_direction_f32(const double *coef, const void *state, const float *S, const float *Y, const float *g,
+                              float *g_prev, float *d, double *partial, double *record, long long n, int m,
+                              void *stream);
+int fmgan_lbfgs_update_f32(const long long *segs, int nseg, const float *d, float a, long long n, void *stream);
+int fmgan_lbfgs_gather_f32(const long long *segs, int nseg, float *g_new, const float *d, double *partial,
+                           double *record, long long n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
