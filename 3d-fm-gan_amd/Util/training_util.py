@@ -137,3 +137,24 @@ def accumulate(model1, model2, decay=0.999):
     with torch.no_grad():
         for k in par1.keys():
             par1[k].mul_(decay).add_(par2[k].detach(), alpha=1 - decay)
+
+
+def accumulate_fused(model1, model2, decay=0.999, plan=None):
+    """`accumulate` in one launch (op/ema.py EmaPlan: csrc/train_loop.hip).  `plan`: the EmaPlan of an earlier call on
+    the same two modules, or None to build one; returns the plan it used, for the next call.  Where
+    EmaPlan.declined(model1, model2) gives a reason (CPU modules, another dtype, shared storage) it runs `accumulate`
+    and returns None."""
+    from op.ema import EmaPlan
+    if plan is None or plan.model1 is not model1 or plan.model2 is not model2:
+        if EmaPlan.declined(model1, model2) is not None:
+            accumulate(model1, model2, decay)
+            return None
+        plan = EmaPlan(model1, model2)
+    try:
+        plan.update(decay)
+    except RuntimeError:
+        if EmaPlan.declined(model1, model2) is None:
+            raise
+        accumulate(model1, model2, decay)       # the modules changed under the plan into something the kernel declines
+        return None
+    return plan

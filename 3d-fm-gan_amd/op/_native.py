@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('FMGAN_LIB') or os.path.join(os.path.dirname(_HERE), 'csrc', 'libfmgan_hip.so')
 
 F32, F64, F16 = 0, 1, 2
-FMGAN_OK, FMGAN_EUNSUPPORTED = 0, -2      # include/fmgan_hip.h, status codes
+FMGAN_OK, FMGAN_EINVAL, FMGAN_EUNSUPPORTED = 0, -1, -2      # include/fmgan_hip.h, status codes
 LPIPS_SIZE = 256                          # the size LPIPS is evaluated at (TARGET of op.ppl_input, op.projection_loss)
 _DTYPES = {torch.float32: F32, torch.float64: F64, torch.float16: F16}
 
@@ -144,6 +144,9 @@ def lib():
     _sig(L.fmgan_lbfgs_direction_f32, [vp] * 9 + [ll, i, vp])
     _sig(L.fmgan_lbfgs_update_f32, [vp, i, vp, f, ll, vp])
     _sig(L.fmgan_lbfgs_gather_f32, [vp, i] + [vp] * 4 + [ll, vp])
+    _sig(L.fmgan_ema_blocks, [ll], ll)
+    _sig(L.fmgan_ema_f32, [vp, i, ll, f, f, vp])
+    _sig(L.fmgan_loss_row_f32, [vp, i, vp, vp])
     if L.fmgan_abi_version() != 1:
         raise RuntimeError('libfmgan_hip.so ABI version mismatch')
     _lib = L
@@ -1547,3 +1550,48 @@ def lbfgs_gather(s, table, nseg):
         st = lib().fmgan_lbfgs_gather_f32(ctypes.addressof(table), nseg, fp(s.g_new), fp(s.d), s.partial.data_ptr(),
                                           s.record.data_ptr(), s.n, stream)
     check(st, 'lbfgs_gather')
+
+
+# ----------------------------------------------------------------------------- training loop (csrc/train_loop.hip)
+EMA_CHUNK = 4096                          # elements per block of fmgan_ema_f32 (csrc/train_loop.hip EMA_CHUNK)
+LOSS_ROW_COLUMNS = 16                     # pointers of fmgan_loss_ptrs, columns of a ledger row
+
+
+def ema_blocks(numel):
+    return int(lib().fmgan_ema_blocks(int(numel)))
+
+
+def ema(table, n_entries, total_blocks, decay, numel=0):
+    """dst <- decay * dst + (1 - decay) * src over every entry of `table` (a uint8 GPU tensor holding n_entries
+    fmgan_ema_entry, built by op.ema.EmaPlan, which has made the device, dtype, layout and overlap checks) in one launch
+    on the current stream of the table's device.  decay travels as float(decay) and float(1 - decay), the difference
+    taken in double."""
+    require_gpu(table, 'table')
+    decay = float(decay)
+    with launching(table, 'ema', (int(n_entries), int(total_blocks), int(numel))) as stream:
+        st = lib().fmgan_ema_f32(table.data_ptr(), int(n_entries), int(total_blocks), ctypes.c_float(decay),
+                                 ctypes.c_float(1.0 - decay), stream)
+    check(st, 'ema')
+
+
+def loss_row(values, row):
+    """One row of the loss log in one launch: values, at most 16 entries, each None or a one-element float32 tensor on
+    row's device; row, a contiguous float32 GPU vector of 16 elements (a row of the ledger's ring).  row[i] = values[i]
+    (0.0 for None and for the columns past len(values))."""
+    n = len(values)
+    if n > LOSS_ROW_COLUMNS:
+        check(FMGAN_EINVAL, f'loss_row: {n} values for {LOSS_ROW_COLUMNS} columns')
+    require_f32_gpu('loss_row', ((row, 'row'),))
+    if row.numel() != LOSS_ROW_COLUMNS:
+        raise ValueError(f'loss_row: row of {row.numel()} elements, expected {LOSS_ROW_COLUMNS}')
+    ptrs = (ctypes.c_void_p * LOSS_ROW_COLUMNS)()
+    for k, v in enumerate(values):
+        if v is None:
+            continue
+        if v.numel() != 1 or v.device != row.device:
+            raise RuntimeError(f'loss_row: value {k} must hold one element on {row.device}, got {tuple(v.shape)} on '
+                               f'{v.device}')
+        ptrs[k] = fp(v)
+    with launching(row, 'loss_row', (n,)) as stream:
+        st = lib().fmgan_loss_row_f32(ctypes.addressof(ptrs), n, fp(row), stream)
+    check(st, 'loss_row')

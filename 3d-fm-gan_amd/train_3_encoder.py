@@ -32,7 +32,15 @@ What is different, on purpose:
     (op/landmark.py).  `extra_losses` takes any further (name, weight, fn(output, reference) -> scalar) terms.
   * the schedule is opt-in: Trainer.step(...) without flags is a reconstruction iteration, exactly as before;
     Trainer.train_iteration(...) draws the flags and the batch as train() does.
+
+The program around them is at the end of the file: Args_Parsing, Print_Experiment_Status,
+Module_To_Train_Setup, Training_Setup, Print_Train_Status, train() and main() (:43-187, :311-364, :599-665, :756-875).
+train() adds two launches per iteration and no host synchronisation: the loss values go through op.loss_log.LossLedger
+(one launch per iteration, read back every args.log_flush iterations) instead of nine .item() per iteration, and with
+args.ema_fuse the EMA is one launch (op.ema.EmaPlan) instead of two per parameter.
 """
+import argparse
+import os
 import types
 
 import numpy as np
@@ -41,9 +49,9 @@ from torch import nn, optim
 
 import dataset
 from Miscellaneous import distributed as D_
-from Util.network_util import Forward_Inference_3_Encoder, MODULATION_ENCODING
+from Util.network_util import CO_MODULATION_MODE, Forward_Inference_3_Encoder, MODULATION_ENCODING
 from Util.training_util import (Face_Identity_Loss, Face_Regional_Loss, Heat_Map_Loss, L1_Loss, LPIPS_Loss, accumulate,
-                                d_logistic_loss, d_r1_loss, g_nonsaturating_loss, requires_grad)
+                                accumulate_fused, d_logistic_loss, d_r1_loss, g_nonsaturating_loss, requires_grad)
 
 
 def default_args(**over):
@@ -452,6 +460,7 @@ class Trainer:
         self.iter_idx = 0
         self.ds_count = 0
         self.loss_dict = {'r1': torch.zeros((), device=device), 'g_reg': torch.zeros((), device=device)}
+        self.ema_plan = None        # op.ema.EmaPlan of (g_ema, G) once step() has run with args.ema_fuse; validates itself
 
     def ds_flags(self):
         """(ds_flag, extreme_ds_flag) of the coming iteration, self.iter_idx (train_3_encoder.py:780-786): every
@@ -487,7 +496,10 @@ class Trainer:
         if self.iter_idx % a.g_reg_every == 0 and a.use_g_reg:
             ld['g_reg'], _, self.mean_path_length = G_Reg_BackProp(G, E_Tsr, E_W, E_W_Plus, g_input, r_input, a,
                                                                    self.mean_path_length, self.g_enc_optim, ppl_choice)
-        accumulate(self.g_ema, self.bare['G'], self.accum)
+        if getattr(a, 'ema_fuse', False) and os.environ.get('FMGAN_NO_EMA_FUSE') != '1':
+            self.ema_plan = accumulate_fused(self.g_ema, self.bare['G'], self.accum, self.ema_plan)
+        else:
+            accumulate(self.g_ema, self.bare['G'], self.accum)
         self.iter_idx += 1
         return ld
 
@@ -678,3 +690,348 @@ class Trainer:
                               'Face Regional: ' + str(scores['face_reg_score']) + '\n\n')
             ckpt = self.save_checkpoint(ckpt_dir)
         return png, scores, ckpt
+
+
+# ====================================================================== the program: arguments, log, train(), main()
+def _parse_bool(text):
+    """true / false / 1 / 0 (any case).  The reference's type=bool makes every non-empty string True."""
+    t = str(text).strip().lower()
+    if t in ('true', '1', 'yes'):
+        return True
+    if t in ('false', '0', 'no'):
+        return False
+    raise argparse.ArgumentTypeError(f'expected true/false/1/0, got {text!r}')
+
+
+def _parse_int_list(text):
+    """Comma-separated integers ('4,5,6'; 'none' or '' for None).  The reference's type=list splits characters."""
+    t = str(text).strip()
+    if t.lower() in ('', 'none'):
+        return None
+    try:
+        return [int(v) for v in t.split(',') if v.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'expected comma-separated integers, got {text!r}') from None
+
+
+def Args_Parsing(argv=None):
+    """The reference's arguments (train_3_encoder.py:52-111), every name, with the defaults default_args() restates from
+    train_3_encoder_hyperparams.py.  Differences, on purpose:
+      * --synface_dir, --extreme_pose_dir, --ffhq_train_img_dir, --visual_real_img_dir, --quant_eval_img_dir and --ckpt
+        default to None (the reference's defaults are its authors' paths); a folder that is None leaves its loaders out;
+      * --device defaults to this rank's device (cuda:LOCAL_RANK, or cpu without a GPU), not 'cuda:4';
+      * --gpu_device_ids is accepted and ignored: args.n_gpu is the world size of Miscellaneous.distributed (one process
+        per GPU) and args.distributed = n_gpu > 1;
+      * booleans parse true/false/1/0, --w_plus_sliced_layer and --gpu_device_ids comma-separated integers,
+        --hmap_iter_thres a float (so that 'inf', the default, survives).
+    This build's own: --log_flush (rows of the loss ledger between two reads of the device, 50), --ema_fuse (the EMA in
+    one launch, true), --resident, --bank_cache_dir, --num_workers, --val_sample_tile, --grad_sync (the data path and the
+    Trainer's fields of the same names), --exp_dir ('Exp_' + Get_Readable_Cur_Time()), --start_iter (0; a checkpoint
+    loaded with --load_train_state sets it) and --use_loss_nets (build LPIPS / ArcFace with Module_Fix_Setup, true)."""
+    d = default_args()
+    local = int(os.environ.get('LOCAL_RANK', '0'))
+    device = f'cuda:{local % max(torch.cuda.device_count(), 1)}' if torch.cuda.is_available() else 'cpu'
+    parser = argparse.ArgumentParser(description='3D-FM GAN, 3-encoder training')
+    add = parser.add_argument
+    add('--synface_dir', type=str, default=None)
+    add('--extreme_pose_dir', type=str, default=None)
+    add('--ffhq_train_img_dir', type=str, default=None)
+    add('--size', type=int, default=d.size)
+    add('--channel_multiplier', type=int, default=2)
+    add('--latent', type=int, default=512)
+    add('--n_mlp', type=int, default=8)
+    add('--use_separate_D', type=_parse_bool, default=True)
+
+    add('--tsr_encode', type=str, default=d.tsr_encode)
+    add('--tsr_train', type=_parse_bool, default=d.tsr_train)
+    add('--w_encode', type=str, default=MODULATION_ENCODING[0])
+    add('--w_train', type=_parse_bool, default=d.w_train)
+    add('--w_plus_encode', type=str, default=MODULATION_ENCODING[1])
+    add('--w_plus_encoder_layer_num', type=int, default=18)
+    add('--w_plus_sliced_layer', type=_parse_int_list, default=d.w_plus_sliced_layer)
+    add('--w_plus_train', type=_parse_bool, default=d.w_plus_train)
+    add('--co_mod', type=str, default=CO_MODULATION_MODE[0])
+
+    add('--ckpt', type=str, default=None)
+    add('--use_tanh', type=_parse_bool, default=d.use_tanh)
+    add('--load_train_state', type=_parse_bool, default=True)
+
+    add('--device', type=str, default=device)
+    add('--gpu_device_ids', type=_parse_int_list, default=None)
+
+    add('--iter', type=int, default=420001)
+    add('--rec_batch', type=int, default=d.rec_batch)
+    add('--rec_dataset_type', type=str, default=d.rec_dataset_type)
+    add('--ds_batch', type=int, default=d.ds_batch)
+    add('--ds_dataset_type', type=str, default=d.ds_dataset_type)
+    add('--ds_freq', type=int, default=d.ds_freq)
+    add('--ex_ds_freq', type=int, default=d.ex_ds_freq)
+    add('--lr', type=float, default=d.lr)
+
+    add('--d_reg_every', type=int, default=d.d_reg_every)
+    add('--r1', type=float, default=d.r1)
+    add('--use_g_reg', type=_parse_bool, default=d.use_g_reg)
+    add('--g_reg_every', type=int, default=d.g_reg_every)
+    add('--path_reg_batch_shrink', type=int, default=d.path_reg_batch_shrink)
+    add('--generator_path_reg_weight', type=float, default=d.generator_path_reg_weight)
+
+    add('--l1_loss_lambda', type=float, default=d.l1_loss_lambda)
+    add('--lpips_loss_lambda', type=float, default=d.lpips_loss_lambda)
+    add('--ep_lpips_l1_weight_shrink', type=float, default=d.ep_lpips_l1_weight_shrink)
+    add('--face_id_loss_lambda', type=float, default=d.face_id_loss_lambda)
+    add('--face_id_loss_type', type=str, default=d.face_id_loss_type)
+    add('--hmap_loss_lambda', type=float, default=d.hmap_loss_lambda)
+    add('--hmap_iter_thres', type=float, default=d.hmap_iter_thres)
+    add('--rec_face_reg_loss_lambda', type=float, default=d.rec_face_reg_loss_lambda)
+    add('--ds_face_reg_loss_lambda', type=float, default=d.ds_face_reg_loss_lambda)
+    add('--ep_face_reg_loss_lambda', type=float, default=d.ep_face_reg_loss_lambda)
+
+    add('--n_real_eval_faces', type=int, default=d.n_real_eval_faces)
+    add('--n_syn_eval_faces', type=int, default=d.n_syn_eval_faces)
+    add('--visual_real_img_dir', type=str, default=None)
+    add('--val_sample_freq', type=int, default=d.val_sample_freq)
+    add('--model_save_freq', type=int, default=d.model_save_freq)
+    add('--quant_eval_img_dir', type=str, default=None)
+    add('--quant_eval_batch_size', type=int, default=d.quant_eval_batch_size)
+
+    add('--log_flush', type=int, default=50)
+    add('--ema_fuse', type=_parse_bool, default=True)
+    add('--resident', type=_parse_bool, default=True)
+    add('--bank_cache_dir', type=str, default=d.bank_cache_dir)
+    add('--num_workers', type=int, default=d.num_workers)
+    add('--val_sample_tile', type=int, default=d.val_sample_tile)
+    add('--grad_sync', type=str, default=d.grad_sync, choices=('ddp', 'flat'))
+    add('--exp_dir', type=str, default=None)
+    add('--start_iter', type=int, default=0)
+    add('--use_loss_nets', type=_parse_bool, default=True)
+
+    args = parser.parse_args(argv)
+    if args.exp_dir is None:
+        args.exp_dir = 'Exp_' + Get_Readable_Cur_Time()
+    args.n_gpu = D_.get_world_size()
+    args.distributed = args.n_gpu > 1
+    return args
+
+
+def Get_Readable_Cur_Time():
+    import datetime
+    return datetime.datetime.now().strftime("%Y-%m-%d_%H:%M:%S")
+
+
+# (label, field of args) of Print_Experiment_Status, section by section (train_3_encoder.py:124-184)
+_STATUS_SECTIONS = (
+    ('  Model and Training Data: ', (
+        ('Synthetic Data Folder', 'synface_dir'), ('Extreme Pose Data Folder', 'extreme_pose_dir'),
+        ('FFHQ Data Folder', 'ffhq_train_img_dir'), ('Generator Num Layers', 'n_latent'),
+        ('Latent Variable Dimension', 'latent'), ('Generated Image Size', 'size'),
+        ('Channel Multiplier', 'channel_multiplier'), ('Using Separate Discriminator', 'use_separate_D'),
+        ('Tensor Encoding', 'tsr_encode'), ('E_Tsr Trainable', 'tsr_train'), ('W Space Encoding', 'w_encode'),
+        ('E_W Trainable', 'w_train'), ('W+ Space Encoding', 'w_plus_encode'),
+        ('W+ Space Layer Slicing', 'w_plus_sliced_layer'), ('E_W+ Trainable', 'w_plus_train'),
+        ('Num W+ Encoder Layer', 'w_plus_encoder_layer_num'), ('Co-Modulation', 'co_mod'), ('Tanh Clipping', 'use_tanh'),
+        ('Initial Checkpoint', 'ckpt'), ('Load Training State', 'load_train_state'))),
+    ('  GPU Setup: ', (
+        ('Distributed Training', 'distributed'), ('Primiary GPU Device', 'device'), ('GPU Device IDs', 'gpu_device_ids'),
+        ('Number of GPUs', 'n_gpu'))),
+    ('  Training Params: ', (
+        ('Training Iterations', 'iter'), ('Reconstruction Dataset', 'rec_dataset_type'),
+        ('Reconstruction Batch Size', 'rec_batch'), ('Dual Supervision Dataset', 'ds_dataset_type'),
+        ('Dual Supervision Batch Size', 'ds_batch'), ('Dual Supervision Frequency', 'ds_freq'),
+        ('Extreme Disentangled Supervision Frequency', 'ex_ds_freq'), ('Learning Rate', 'lr'),
+        ('Use Generator Regularization', 'use_g_reg'), ('Generator Regularization Frequency', 'g_reg_every'),
+        ('Generator Regularization Weight', 'generator_path_reg_weight'),
+        ('Generator Regularization Batch Shrink', 'path_reg_batch_shrink'),
+        ('Discriminator Regularization Frequency', 'd_reg_every'), ('Discriminator Regularization Weight', 'r1'),
+        ('LPIPS Loss Weight', 'lpips_loss_lambda'), ('L1 Loss Weight', 'l1_loss_lambda'),
+        ('L1 LPIPS Weight Shrink for Extreme Pose', 'ep_lpips_l1_weight_shrink'),
+        ('Face ID Loss Weight', 'face_id_loss_lambda'), ('Face ID Loss Type', 'face_id_loss_type'),
+        ('Heat Map Loss Weight', 'hmap_loss_lambda'), ('Heat Map Loss Iteration Threshold', 'hmap_iter_thres'),
+        ('Reconstruction Face Regional Loss Weight', 'rec_face_reg_loss_lambda'),
+        ('Disentanglement Face Regional Loss Weight', 'ds_face_reg_loss_lambda'),
+        ('Extreme Pose Face Regional Loss Weight', 'ep_face_reg_loss_lambda'))),
+    ('  Validation Params: ', (
+        ('Model Saving Frequency', 'model_save_freq'), ('Quantitative Evaluation Directory', 'quant_eval_img_dir'),
+        ('Quantitative Evaluation Batch Size', 'quant_eval_batch_size'), ('Visual Evaluation Frequency', 'val_sample_freq'),
+        ('Number of Visual Real Samples', 'n_real_eval_faces'), ('Number of Visual Synthetic Samples', 'n_syn_eval_faces'),
+        ('Visual Real Samples Directory', 'visual_real_img_dir'))),
+)
+
+
+def Experiment_Status_Text(args):
+    """The text Print_Experiment_Status prints and writes: the reference's, character for character (:124-184)."""
+    text = '\n' + '--------------- Training Start ---------------' + '\n\n' + 'Params: ' + '\n\n'
+    for title, fields in _STATUS_SECTIONS:
+        text += title + '\n'
+        text += '\n'.join('    ' + label + ': ' + str(getattr(args, field)) for label, field in fields) + '\n\n'
+    return text
+
+
+def Print_Experiment_Status(args, exp_log_file):
+    """Prints the experiment's settings and writes them to the log (train_3_encoder.py:119-187); rank 0 only."""
+    if D_.get_rank() != 0:
+        return
+    text = Experiment_Status_Text(args)
+    print(text)
+    if exp_log_file is not None:
+        exp_log_file.write(text)
+
+
+def Module_To_Train_Setup(args):
+    """The networks to train (train_3_encoder.py:311-364): (G, E_Tsr, E_W, E_W_Plus, D, D_edit, g_ema, ckpt), bare
+    modules on args.device — Trainer wraps them for data parallelism, there is no nn.DataParallel.  D_edit exists under
+    the reference's condition (:325); with args.ckpt the reference's loading rules (:332-345); without one g_ema starts
+    as a copy of G (accumulate(g_ema, G, 0)).  The Generators of a checkpoint are built with args.n_mlp (the reference
+    leaves Build_Generator_From_Dict's default of 8 there, which is its own --n_mlp default).  Sets args.n_latent."""
+    import math
+    import resnet_encoder
+    from psp_encoder_model.encoders import psp_encoders
+    from stylegan2 import Discriminator, Generator
+    from Util.network_util import Build_Generator_From_Dict
+    device = args.device
+    E_Tsr = resnet_encoder.resnet18(tensor_encoding=True).to(device)
+    E_W = resnet_encoder.resnet18(tensor_encoding=False).to(device)
+    opts = types.SimpleNamespace(input_nc=3, n_styles=int(math.log(args.size, 2)) * 2 - 2)
+    E_W_Plus = psp_encoders.GradualStyleEncoder(args.w_plus_encoder_layer_num, 'ir_se', opts).to(device)
+    D = Discriminator(args.size, channel_multiplier=args.channel_multiplier).to(device)
+    D_edit = None
+    if args.rec_dataset_type == 'FFHQ' and args.ds_dataset_type == 'Synthetic' and args.use_separate_D:
+        D_edit = Discriminator(args.size, channel_multiplier=args.channel_multiplier).to(device)
+    ckpt = None
+    if args.ckpt is not None:
+        ckpt = torch.load(args.ckpt, map_location='cpu', weights_only=False)
+        G = Build_Generator_From_Dict(ckpt['g'], size=args.size, latent=args.latent, n_mlp=args.n_mlp).to(device)
+        g_ema = Build_Generator_From_Dict(ckpt['g_ema'], size=args.size, latent=args.latent, n_mlp=args.n_mlp).to(device)
+        D.load_state_dict(ckpt['d'])
+        if 'e_tsr' in ckpt and 'e_W' in ckpt and 'e_W_Plus' in ckpt:
+            E_Tsr.load_state_dict(ckpt['e_tsr'], strict=False)
+            E_W.load_state_dict(ckpt['e_W'], strict=False)
+            E_W_Plus.load_state_dict(ckpt['e_W_Plus'], strict=False)
+        if D_edit is not None:
+            D_edit.load_state_dict(ckpt['d_edit'] if ckpt.get('d_edit') is not None else ckpt['d'])
+    else:
+        G = Generator(args.size, args.latent, args.n_mlp, channel_multiplier=args.channel_multiplier).to(device)
+        g_ema = Generator(args.size, args.latent, args.n_mlp, channel_multiplier=args.channel_multiplier).to(device)
+        accumulate(g_ema, G, 0)
+    g_ema.eval()
+    args.n_latent = g_ema.n_latent
+    return G, E_Tsr, E_W, E_W_Plus, D, D_edit, g_ema, ckpt
+
+
+def Training_Setup(exp_dir, args):
+    """(sample_dir, ckpt_dir) below exp_dir (train_3_encoder.py:604-607), created on rank 0."""
+    sample_dir = os.path.join(exp_dir, 'sample') + '/'
+    ckpt_dir = os.path.join(exp_dir, 'ckpt') + '/'
+    if D_.get_rank() == 0:
+        os.makedirs(sample_dir, exist_ok=True)
+        os.makedirs(ckpt_dir, exist_ok=True)
+    return sample_dir, ckpt_dir
+
+
+def Train_Status_Line(iter_idx, seconds, ds_flag, extreme_ds_flag, values):
+    """The reference's log line of one iteration (train_3_encoder.py:655) from a dict of Python floats keyed by the
+    ledger's names; a name that is missing counts as 0.0."""
+    v = lambda name: str(round(float(values.get(name, 0.0)), 3))        # noqa: E731
+    return ('Iter #: ' + str(iter_idx) + ' Train Time: ' + str(round(seconds, 2)) + ' Dual Supervision: ' + str(ds_flag) +
+            ' Extreme Pose DS: ' + str(extreme_ds_flag) + ' D_Loss: ' + v('d') + ' G_Loss: ' + v('g') + ' G_Reg: ' +
+            v('g_reg') + ' L1_Loss: ' + v('l1') + ' LPIPS_Loss: ' + v('lpips') + ' Face_ID_Loss: ' + v('face_id') +
+            ' Heat_Map_Loss: ' + v('hmap') + ' Face_Regional_Loss: ' + v('face_reg') + '\n')
+
+
+def Print_Train_Status(rows, exp_log_file):
+    """One line per row of LossLedger.flush() into the log, on rank 0 (the other ranks' flush returns no rows)."""
+    if exp_log_file is None or D_.get_rank() != 0:
+        return
+    for iter_idx, seconds, ds_flag, extreme_ds_flag, values in rows:
+        exp_log_file.write(Train_Status_Line(iter_idx, seconds, ds_flag, extreme_ds_flag, values))
+
+
+def train(args, train_loaders, eval_loaders, trainer, visual_eval_samples, exp_dir, exp_log_file, ledger=None):
+    """The loop of train_3_encoder.py:756-828 over a Trainer: train_loaders = (rec, ds, ep, pure FFHQ) streams and
+    eval_loaders = (rec_eval, edit_eval), as Dataset_DataLoader_Setup returns them.  The trainer is touched only through
+    iter_idx, train_iteration and Sample_Eval_Save_Ckpt.
+
+    The loss values go through an op.loss_log.LossLedger of args.log_flush rows (returned; `ledger`: one to use
+    instead): an iteration adds one launch and two event records, and the log lines are written when the ring is full,
+    before an evaluation block (so that the file keeps the reference's order) and, in `finally`, at the end — an
+    exception leaves the line of every finished iteration in the file.  Between flushes the loop synchronises nothing
+    and copies nothing to the host.  The time in a line is the device time between the iteration's first and last
+    launch (events), where the reference prints the host clock over the same span."""
+    from op.loss_log import LossLedger
+    rec_train_loader, ds_train_loader, ep_train_loader = train_loaders[:3]
+    rec_eval_loader, edit_eval_loader = eval_loaders
+    sample_dir, ckpt_dir = Training_Setup(exp_dir, args)
+    if ledger is None:
+        device = getattr(trainer, 'device', None)
+        device = device if device is not None else getattr(args, 'device', 'cpu')
+        ledger = LossLedger(device, max(1, int(getattr(args, 'log_flush', 50))))
+
+    def flush():
+        Print_Train_Status(ledger.flush(), exp_log_file)
+
+    try:
+        while trainer.iter_idx < args.iter:
+            iter_idx = trainer.iter_idx
+            ledger.begin()
+            loss_dict, ds_flag, extreme_ds_flag = trainer.train_iteration(rec_train_loader, ds_train_loader, ep_train_loader)
+            ledger.write(iter_idx, loss_dict, ds_flag, extreme_ds_flag)
+            # Sample_Eval_Save_Ckpt's own condition for the evaluation text and the checkpoint (:708)
+            evaluates = iter_idx % args.model_save_freq == 0 and iter_idx > 0
+            if ledger.full() or evaluates:
+                flush()
+            trainer.Sample_Eval_Save_Ckpt(sample_dir, ckpt_dir, visual_eval_samples, rec_eval_loader, edit_eval_loader,
+                                          log=exp_log_file)
+    finally:
+        flush()
+    return ledger
+
+
+def main(argv=None):
+    """train_3_encoder.py:831-875 on one process per GPU: the arguments, the data, the networks, the frozen loss networks,
+    the Trainer (resumed from --ckpt when --load_train_state), the experiment folder and its log, the loop."""
+    import time
+    rank, world, device = D_.init_distributed()
+    args = Args_Parsing(argv)
+    device = torch.device(args.device)
+    (transform, synface_dataset, extreme_pose_dataset, rec_train_loader, ds_train_loader, ep_train_loader,
+     pure_ffhq_loader, rec_eval_loader, edit_eval_loader) = Dataset_DataLoader_Setup(args, device, resident=args.resident)
+    G, E_Tsr, E_W, E_W_Plus, D, D_edit, g_ema, ckpt = Module_To_Train_Setup(args)
+    lpips_model = face_rec_model = None
+    if args.use_loss_nets:
+        lpips_model, face_rec_model = Module_Fix_Setup(args, device)
+    nets = dict(G=G, E_Tsr=E_Tsr, E_W=E_W, E_W_Plus=E_W_Plus, D=D)
+    if D_edit is not None:
+        nets['D_edit'] = D_edit
+    trainer = Trainer(nets, args, device, g_ema=g_ema, lpips_model=lpips_model, face_rec_model=face_rec_model)
+    trainer.iter_idx = args.start_iter
+    if args.ckpt is not None and args.load_train_state:
+        trainer.load_checkpoint(args.ckpt)
+        args.start_iter = trainer.iter_idx
+
+    exp_dir = args.exp_dir
+    exp_log_file = None
+    if rank == 0:
+        os.makedirs(exp_dir, exist_ok=True)
+        exp_log_file = open(os.path.join(exp_dir, Get_Readable_Cur_Time() + '_training_log.out'), 'w')
+    D_.synchronize()
+    try:
+        Print_Experiment_Status(args, exp_log_file)
+        visual_eval_samples = None
+        if args.visual_real_img_dir is not None and synface_dataset is not None and extreme_pose_dataset is not None:
+            visual_eval_samples = Visual_Evaluation_Setup(args, synface_dataset, extreme_pose_dataset, transform, device)
+        train_start_time = time.time()
+        train_loaders = rec_train_loader, ds_train_loader, ep_train_loader, pure_ffhq_loader
+        eval_loaders = rec_eval_loader, edit_eval_loader
+        train(args, train_loaders, eval_loaders, trainer, visual_eval_samples, exp_dir, exp_log_file)
+        if device.type == 'cuda':
+            torch.cuda.synchronize(device)
+        train_end_time = time.time()
+        if exp_log_file is not None:
+            exp_log_file.write('\n' + 'Total training time: ' + str(round(train_end_time - train_start_time, 3)))
+    finally:
+        if exp_log_file is not None:
+            exp_log_file.close()
+    return exp_dir
+
+
+if __name__ == '__main__':
+    main()

@@ -27,6 +27,8 @@
  *   fmgan_images_to_tensor <- transforms.ToTensor()+Normalize   train_3_encoder.py:233-239
  *   fmgan_resize_*         <- transforms.Resize(size) (PIL BILINEAR) train_3_encoder.py:235
  *   fmgan_tensor_to_images <- tensor2im                 Evaluation/visual_eval.py:24-38
+ *   fmgan_ema_f32          <- accumulate                train_3_encoder.py:195-200
+ *   fmgan_loss_row_f32     <- the nine .item() of Print_Train_Status   train_3_encoder.py:641-651
  */
 #ifndef FMGAN_HIP_H
 #define FMGAN_HIP_H
@@ -866,6 +868,37 @@ int fmgan_lbfgs_direction_f32(const double *coef, const void *state, const float
 int fmgan_lbfgs_update_f32(const long long *segs, int nseg, const float *d, float a, long long n, void *stream);
 int fmgan_lbfgs_gather_f32(const long long *segs, int nseg, float *g_new, const float *d, double *partial,
                            double *record, long long n, void *stream);
+
+/*
+ * The two launches train() adds per iteration (csrc/train_loop.hip).
+ *
+ * fmgan_ema_f32: dst <- decay * dst + alpha * src over a whole parameter set in ONE launch (replaces the two aten
+ * launches per parameter of `accumulate`, train_3_encoder.py:195-200).  table_dev: DEVICE array of n_entries entries
+ * sorted by block_begin; entry k owns the logical blocks [block_begin_k, block_begin_k + fmgan_ema_blocks(numel_k)),
+ * total_blocks = their sum; an entry of 0 elements owns none.  A block handles 4096 consecutive elements of one tensor
+ * with 16-byte accesses from the first 16-byte boundary of dst when src is aligned there too, scalar accesses before
+ * it, after the last whole vector, and everywhere when the two alignments differ.  Every offset is 64-bit.  Per element
+ * fmaf(alpha, src, dst * decay): two roundings, written explicitly; elementwise, hence bit-reproducible.  dst and src
+ * ranges of different entries must not overlap.  n_entries == 0 or total_blocks == 0: FMGAN_OK without a launch.
+ * FMGAN_EINVAL: negative counts, NULL table; FMGAN_EOVERFLOW: more blocks than a grid holds (2^31 - 1).
+ *
+ * fmgan_loss_row_f32: one row of the loss log.  `ptrs` is a HOST struct of 16 device addresses (each of one float, or
+ * NULL); it is read during the call and travels to the kernel by value.  One wave: lane i < n writes *p[i] (0.0f for
+ * NULL) to row_dev[i], lanes n..15 write 0.0f.  FMGAN_EINVAL: n outside 0..16, NULL ptrs or row_dev.
+ */
+typedef struct fmgan_ema_entry {
+  void *dst;
+  const void *src;
+  long long numel;
+  long long block_begin;
+} fmgan_ema_entry;
+typedef struct fmgan_loss_ptrs {
+  const float *p[16];
+} fmgan_loss_ptrs;
+long long fmgan_ema_blocks(long long numel);
+int fmgan_ema_f32(const fmgan_ema_entry *table_dev, int n_entries, long long total_blocks, float decay, float alpha,
+                  void *stream);
+int fmgan_loss_row_f32(const fmgan_loss_ptrs *ptrs, int n, float *row_dev, void *stream);
 
 #ifdef __cplusplus
 }
