@@ -57,6 +57,18 @@ template <typename T> __device__ __forceinline__ T from_acc(typename AccT<T>::ty
 }
 template <> __device__ __forceinline__ __half from_acc<__half>(float v) { return __float2half(v); }
 
+// The activation of fused_bias_act, shared by fused_bias_act.hip and act16.hip so that the 16-bit kernels apply the
+// very expression of the fp32 ones.  code = act*10 + grad  (op/fused_bias_act_kernel.cu:36-45)
+template <typename A> __device__ __forceinline__ A act_apply(A x, A ref, int code, A alpha) {
+  switch (code) {
+    case 12: return A(0);
+    case 30: return (x > A(0)) ? x : x * alpha;
+    case 31: return (ref > A(0)) ? x : x * alpha;
+    case 32: return A(0);
+    default: return x;  // 10, 11 and anything else: linear
+  }
+}
+
 // 4-byte-aligned vector types: global_load/store_dwordx{2,4} need only dword alignment
 // on gfx950, and rows of 2H+1 floats are never 16-byte aligned.
 typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));

@@ -10,17 +10,6 @@
 
 namespace {
 
-template <typename A> __device__ __forceinline__ A act_apply(A x, A ref, int code, A alpha) {
-  // code = act*10 + grad  (op/fused_bias_act_kernel.cu:36-45)
-  switch (code) {
-    case 12: return A(0);
-    case 30: return (x > A(0)) ? x : x * alpha;
-    case 31: return (ref > A(0)) ? x : x * alpha;
-    case 32: return A(0);
-    default: return x;  // 10, 11 and anything else: linear
-  }
-}
-
 // generic: any dtype, any step_b
 template <typename T>
 __global__ __launch_bounds__(256) void fba_generic(T* __restrict__ out, const T* __restrict__ x,

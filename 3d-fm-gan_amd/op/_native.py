@@ -6,6 +6,7 @@ of the tensor's device (as the reference launches on at::cuda::getCurrentCUDAStr
 op/upfirdn2d_kernel.cu:213-215), asynchronously, so calls can be captured in a HIP graph.
 """
 import ctypes
+import functools
 import os
 
 import torch
@@ -14,9 +15,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('FMGAN_LIB') or os.path.join(os.path.dirname(_HERE), 'csrc', 'libfmgan_hip.so')
 
 F32, F64, F16 = 0, 1, 2
+BF16 = 3                                  # the 16-bit activation kernels only (csrc/act16.hip)
 FMGAN_OK, FMGAN_EINVAL, FMGAN_EUNSUPPORTED = 0, -1, -2      # include/fmgan_hip.h, status codes
 LPIPS_SIZE = 256                          # the size LPIPS is evaluated at (TARGET of op.ppl_input, op.projection_loss)
 _DTYPES = {torch.float32: F32, torch.float64: F64, torch.float16: F16}
+_DTYPES16 = {torch.float16: F16, torch.bfloat16: BF16}
 
 _lib = None
 
@@ -26,6 +29,59 @@ _lib = None
 # autocast is not active.
 amp_fwd = torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
 amp_bwd = torch.amp.custom_bwd(device_type='cuda')
+
+# Activations of op/upfirdn2d.py and op/fused_act.py in HBM: 'fp32' (default: under autocast amp_fwd widens their 16-bit
+# inputs, the fp32 kernels run and hand fp32 on) or '16' (16-bit tensors stay 16-bit on the kernels of csrc/act16.hip:
+# half the bytes and no cast kernels around each op; f16 takes those kernels too).  bf16 tensors outside autocast run on
+# the 16-bit kernels in either mode; f16 tensors in 'fp32' mode keep the generic kernels.  Context manager only.
+_act_io = 'fp32'
+
+
+class activation_io:
+    """`with activation_io('16'):` — inside, and under torch.autocast, FusedLeakyReLU / fused_leaky_relu / Blur / upfirdn2d
+    keep a 16-bit input 16-bit (fp32 inputs stay on the fp32 kernels)."""
+
+    def __init__(self, mode):
+        if mode not in ('fp32', '16'):
+            raise ValueError("mode must be 'fp32' or '16'")
+        self.mode = mode
+
+    def __enter__(self):
+        global _act_io
+        self.prev, _act_io = _act_io, self.mode
+        return self
+
+    def __exit__(self, *exc):
+        global _act_io
+        _act_io = self.prev
+        return False
+
+
+def current_activation_io():
+    return _act_io
+
+
+def io16(t):
+    """Does this tensor run on the 16-bit kernels (act16.hip)?  bf16 always; f16 under activation_io('16')."""
+    return t.dtype == torch.bfloat16 or (t.dtype == torch.float16 and _act_io == '16')
+
+
+def amp_fwd_io(fwd):
+    """amp_fwd for the Functions of op/upfirdn2d.py and op/fused_act.py: under autocast and activation_io('16') the
+    forward runs with autocast off and its inputs AS THEY ARE (nothing is widened; an fp32 input stays on the fp32
+    kernels), and amp_bwd runs the backward the same way; otherwise exactly amp_fwd."""
+    cast = amp_fwd(fwd)
+
+    @functools.wraps(fwd)
+    def decorate(ctx, *args, **kwargs):
+        if _act_io == '16' and torch.is_autocast_enabled('cuda'):
+            ctx._dtype = torch.get_autocast_dtype('cuda')
+            ctx._fwd_used_autocast = False
+            with torch.autocast(device_type='cuda', enabled=False):
+                return fwd(ctx, *args, **kwargs)
+        return cast(ctx, *args, **kwargs)
+
+    return decorate
 
 
 def _sig(fn, argtypes, restype=ctypes.c_int):
@@ -147,6 +203,12 @@ def lib():
     _sig(L.fmgan_ema_blocks, [ll], ll)
     _sig(L.fmgan_ema_f32, [vp, i, ll, f, f, vp])
     _sig(L.fmgan_loss_row_f32, [vp, i, vp, vp])
+    _sig(L.fmgan_act16_fba_select, [i, ll, i, i, i, i])
+    _sig(L.fmgan_act16_fba, [i, vp, vp, vp, vp, ll, i, i, i, i, f, f, vp])
+    _sig(L.fmgan_act16_fba_bwd_blocks, [ll, i])
+    _sig(L.fmgan_act16_fba_bwd, [i] + [vp] * 4 + [ll, i, f, f, vp])
+    _sig(L.fmgan_ufd16_select, [i] * 15)
+    _sig(L.fmgan_ufd16, [i, vp, vp, vp] + [i] * 14 + [vp])
     if L.fmgan_abi_version() != 1:
         raise RuntimeError('libfmgan_hip.so ABI version mismatch')
     _lib = L
@@ -298,6 +360,8 @@ def upfirdn2d(input, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0,
     input [major,in_h,in_w,minor], kernel [kh,kw] -> new tensor [major,out_h,out_w,minor]."""
     require_gpu(input, 'input')
     require_gpu(kernel, 'kernel')
+    if force_path == -1 and io16(input):
+        return upfirdn2d16(input, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1)
     x = input.contiguous()
     k = kernel.to(dtype=x.dtype).contiguous()
     major, in_h, in_w, minor = x.shape
@@ -370,6 +434,8 @@ def fused_bias_act(input, bias, refer, act, grad, alpha, scale):
     require_gpu(input, 'input')
     if bias is not None and bias.numel():
         require_gpu(bias, 'bias')
+    if io16(input):
+        return fused_bias_act16(input, bias, refer, act, grad, alpha, scale)
     x = input.contiguous()
     b = bias.to(dtype=x.dtype).contiguous() if bias is not None and bias.numel() else None
     r = refer.to(dtype=x.dtype).contiguous() if refer is not None and refer.numel() else None
@@ -407,6 +473,99 @@ def fused_bias_act_backward(grad_output, out, alpha, scale):
         st = lib().fmgan_fused_bias_act_bwd_f32(fp(g), fp(r), fp(gi), fp(partial), b * c, hw, float(alpha),
                                                 float(scale), stream)
     return (gi, partial.sum((0, 2))) if served(st, 'fused_bias_act_backward') else None
+
+
+# ----------------------------------------------------------------------------- 16-bit activations (csrc/act16.hip)
+def dtype16_code(t):
+    try:
+        return _DTYPES16[t.dtype]
+    except KeyError:
+        raise RuntimeError(f'unsupported dtype {t.dtype}: the 16-bit kernels take float16/bfloat16 only') from None
+
+
+def _same_device(what, x, named):
+    for t, name in named:
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f'{what}: {name} is on {t.device}, input on {x.device}')
+
+
+def upfirdn2d16(input, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1):
+    """upfirdn2d on a bf16 / f16 tensor [major,in_h,in_w,minor] without widening it: the taps are read as fp32 (a 16-bit
+    `kernel` of a converted module is widened here, which is exact), the sums are fp32 and the result is rounded once."""
+    require_gpu(input, 'input')
+    require_gpu(kernel, 'kernel')
+    _same_device('upfirdn2d', input, ((kernel, 'kernel'),))
+    x = input.contiguous()
+    k = kernel.to(dtype=torch.float32).contiguous()
+    major, in_h, in_w, minor = x.shape
+    kh, kw = k.shape
+    out_h, out_w = upfirdn2d_out_size(in_h, in_w, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1)
+    if out_h <= 0 or out_w <= 0:
+        raise RuntimeError(f'upfirdn2d: empty output {out_h}x{out_w}')
+    out = torch.empty((major, out_h, out_w, minor), dtype=x.dtype, device=x.device)
+    with launching(x, 'upfirdn2d', (major, in_h, in_w, out_h, out_w, up_x, down_x, x.element_size())) as stream:
+        st = lib().fmgan_ufd16(dtype16_code(x), ptr(x), fp(k), ptr(out), major, in_h, in_w, minor, kh, kw, up_x, up_y,
+                               down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, stream)
+    check(st, 'upfirdn2d16')
+    return out
+
+
+def fused_bias_act16(input, bias, refer, act, grad, alpha, scale):
+    """fused_bias_act on a bf16 / f16 tensor without widening it; the bias is handed over as fp32 (a parameter under
+    autocast is fp32 already; a 16-bit bias of a converted module is widened here, which is exact)."""
+    require_gpu(input, 'input')
+    x = input.contiguous()
+    b = bias.to(dtype=torch.float32).contiguous() if bias is not None and bias.numel() else None
+    r = refer.to(dtype=x.dtype).contiguous() if refer is not None and refer.numel() else None
+    if b is not None:
+        require_gpu(b, 'bias')
+    _same_device('fused_bias_act', x, ((b, 'bias'), (r, 'refer')))
+    if r is not None and r.numel() != x.numel():
+        raise RuntimeError('fused_bias_act: refer must have as many elements as input')
+    step_b = 1
+    for d in x.shape[2:]:
+        step_b *= d
+    out = torch.empty_like(x)
+    with launching(x, 'fused_bias_act', (x.numel(), x.element_size())) as stream:
+        st = lib().fmgan_act16_fba(dtype16_code(x), ptr(x), fp(b), ptr(r), ptr(out), x.numel(),
+                                   0 if b is None else b.numel(), step_b, int(act), int(grad), float(alpha),
+                                   float(scale), stream)
+    check(st, 'fused_bias_act16')
+    return out
+
+
+# act16_fba_bwd gives every (batch, channel) plane a row of 256-thread blocks.  Below one wave of elements per plane —
+# the [B, C] tensors of EqualLinear(fused_lrelu) are planes of ONE element — that is a block per handful of elements:
+# such tensors take the elementwise kernel over the whole tensor and one fp32 torch sum of the stored 16-bit gradient.
+_BWD16_MIN_HW = 64
+
+
+def fused_bias_act16_backward(grad_output, out, alpha, scale):
+    """fused_bias_act_backward on bf16 / f16 tensors of at least 2 dims: (grad_input in the tensors' dtype, grad_bias
+    [C] in fp32 — the sum of the stored grad_input), or None for a tensor of fewer dims or mixed dtypes (the caller then
+    runs fused_bias_act(..., 3, 1) and a torch sum)."""
+    require_gpu(grad_output, 'input')
+    if (grad_output.ndim < 2 or grad_output.numel() == 0 or out.dtype != grad_output.dtype
+            or out.numel() != grad_output.numel()):
+        return None
+    _same_device('fused_bias_act_backward', grad_output, ((out, 'out'),))
+    g = grad_output.contiguous()
+    r = out.contiguous()
+    b, c = g.shape[:2]
+    hw = g[0, 0].numel()
+    if hw < _BWD16_MIN_HW:
+        gi = fused_bias_act16(g, None, r, 3, 1, alpha, scale)
+        return gi, gi.sum([0] + list(range(2, g.ndim)), dtype=torch.float32)
+    gx = lib().fmgan_act16_fba_bwd_blocks(b * c, hw)
+    if gx == 0:
+        return None
+    gi = torch.empty_like(g)
+    partial = torch.empty((b, c, gx), dtype=torch.float32, device=g.device)
+    with launching(g, 'fused_bias_act', (g.numel(), g.element_size())) as stream:
+        st = lib().fmgan_act16_fba_bwd(dtype16_code(g), ptr(g), ptr(r), ptr(gi), fp(partial), b * c, hw, float(alpha),
+                                       float(scale), stream)
+    check(st, 'fused_bias_act16_backward')
+    return gi, partial.sum((0, 2))
 
 
 def noise_bias_act(x, noise, noise_weight, bias, alpha, scale):

@@ -8,13 +8,16 @@ The backward saves the OUTPUT, not the input (op/fused_act.py:76): sign(out) == 
 scale > 0 and the slope is positive, so grad_input = act'(grad_output; ref=out).
 Differences, on purpose: no import-time JIT, no CPU branch (a CPU tensor raises RuntimeError), and
 `negative_slope` is honoured as the CUDA kernel does (the reference's CPU branch ignores it).
+16-bit tensors: bf16 (and f16 under _native.activation_io('16')) run on the kernels of csrc/act16.hip in their own dtype,
+gradients of every order included; the bias gradient is summed in fp32 and returned in the bias's dtype.  Under autocast
+the inputs are widened to fp32 first unless activation_io('16') is on (see _native.amp_fwd_io).
 """
 import torch
 from torch import nn
 from torch.autograd import Function
 
 from . import _native
-from ._native import amp_fwd as _amp_fwd, amp_bwd as _amp_bwd
+from ._native import amp_fwd_io as _amp_fwd, amp_bwd as _amp_bwd
 
 
 class _Ext:
@@ -39,7 +42,10 @@ class FusedLeakyReLUFunctionBackward(Function):
         if bias:
             # one pass: the kernel that writes grad_input also leaves per-block partial sums for the bias gradient
             # (the reference: a full-size reduction kernel after the elementwise one, op/fused_act.py:42-50)
-            both = _native.fused_bias_act_backward(grad_output, out, negative_slope, scale)
+            if _native.io16(grad_output):
+                both = _native.fused_bias_act16_backward(grad_output, out, negative_slope, scale)
+            else:
+                both = _native.fused_bias_act_backward(grad_output, out, negative_slope, scale)
             if both is not None:
                 return both
         grad_input = fused.fused_bias_act(grad_output, empty, out, 3, 1, negative_slope, scale)
@@ -60,6 +66,7 @@ class FusedLeakyReLUFunction(Function):
     @_amp_fwd
     def forward(ctx, input, bias, negative_slope, scale):
         ctx.has_bias = bias is not None
+        ctx.bias_dtype = bias.dtype if ctx.has_bias else None
         out = fused.fused_bias_act(input, bias if ctx.has_bias else input.new_empty(0), input.new_empty(0), 3, 0,
                                    negative_slope, scale)
         ctx.save_for_backward(out)
@@ -73,7 +80,7 @@ class FusedLeakyReLUFunction(Function):
         negative_slope, scale = ctx.cfg
         grad_input, grad_bias = FusedLeakyReLUFunctionBackward.apply(grad_output, out, ctx.has_bias, negative_slope,
                                                                      scale)
-        return grad_input, (grad_bias if ctx.has_bias else None), None, None
+        return grad_input, (grad_bias.to(ctx.bias_dtype) if ctx.has_bias else None), None, None
 
 
 class FusedLeakyReLU(nn.Module):

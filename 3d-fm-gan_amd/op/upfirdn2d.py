@@ -8,6 +8,9 @@ Differences, on purpose:
   * no import-time JIT (op/upfirdn2d.py:19-25): the library is built ahead of time for gfx950;
   * no CPU branch (op/upfirdn2d.py:155-158): a CPU tensor raises RuntimeError, as the reference's
     extension does for non-CUDA tensors (op/upfirdn2d.cpp:8).
+16-bit tensors: bf16 (and f16 under _native.activation_io('16')) run on the kernels of csrc/act16.hip in their own
+dtype with fp32 taps and fp32 sums, gradients of every order included; under autocast the input is widened to fp32 first
+unless activation_io('16') is on (see _native.amp_fwd_io).
 Gradient algebra (op/upfirdn2d.py:108-125, 28-94): the adjoint of upfirdn2d(k, up, down, pad) is
 upfirdn2d(flip(k), up=down, down=up, g_pad) and the adjoint of that is the original op again.
 """
@@ -15,7 +18,7 @@ import torch
 from torch.autograd import Function
 
 from . import _native
-from ._native import amp_fwd as _amp_fwd, amp_bwd as _amp_bwd
+from ._native import amp_fwd_io as _amp_fwd, amp_bwd as _amp_bwd
 
 
 class _Ext:

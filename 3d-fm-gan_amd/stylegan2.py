@@ -796,8 +796,10 @@ class Discriminator(nn.Module):
         out = self.convs(input)
         batch, channel, height, width = out.shape
         group = min(batch, self.stddev_group)
-        sd = out.view(group, -1, self.stddev_feat, channel // self.stddev_feat, height, width)
+        # (the statistic is taken in fp32 also when the activations are 16-bit — a converted network, or autocast with
+        # _native.activation_io('16'): a variance over 4 samples in bf16 keeps 2-3 digits; a no-op on fp32 activations)
+        sd = out.float().view(group, -1, self.stddev_feat, channel // self.stddev_feat, height, width)
         sd = torch.sqrt(sd.var(0, unbiased=False) + 1e-8)
         sd = sd.mean([2, 3, 4], keepdims=True).squeeze(2).repeat(group, 1, height, width)
-        out = self.final_conv(torch.cat([out, sd], 1))
+        out = self.final_conv(torch.cat([out, sd.to(out.dtype)], 1))
         return self.final_linear(out.view(batch, -1))

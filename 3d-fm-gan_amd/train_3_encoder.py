@@ -40,6 +40,7 @@ train() adds two launches per iteration and no host synchronisation: the loss va
 args.ema_fuse the EMA is one launch (op.ema.EmaPlan) instead of two per parameter.
 """
 import argparse
+import contextlib
 import os
 import types
 
@@ -49,9 +50,15 @@ from torch import nn, optim
 
 import dataset
 from Miscellaneous import distributed as D_
+from op import _native
 from Util.network_util import CO_MODULATION_MODE, Forward_Inference_3_Encoder, MODULATION_ENCODING
 from Util.training_util import (Face_Identity_Loss, Face_Regional_Loss, Heat_Map_Loss, L1_Loss, LPIPS_Loss, accumulate,
                                 accumulate_fused, d_logistic_loss, d_r1_loss, g_nonsaturating_loss, requires_grad)
+
+
+# Default of --bf16_io / args.bf16_io: the 16-bit activation kernels under --precision bf16.  On, because the bf16
+# training step at 1024^2 is faster with them by far more than its run-to-run spread (profiles/act16.md).
+BF16_IO_DEFAULT = True
 
 
 def default_args(**over):
@@ -430,6 +437,32 @@ def G_Reg_BackProp(G, E_Tsr, E_W, E_W_Plus, g_input, r_input, args, mean_path_le
     return path_loss, path_lengths, mean_path_length
 
 
+def training_precision(args):
+    """(precision, bf16_io) of a Trainer with these settings: args.precision ('fp32' when the field is absent, as in
+    default_args()) and whether the 16-bit activation kernels are on — args.bf16_io under 'bf16', unless
+    FMGAN_NO_BF16_IO=1 (read at every step, like the other FMGAN_NO_* switches)."""
+    precision = getattr(args, 'precision', 'fp32')
+    if precision not in ('fp32', 'bf16'):
+        raise ValueError(f"args.precision must be 'fp32' or 'bf16', got {precision!r}")
+    io = (precision == 'bf16' and bool(getattr(args, 'bf16_io', BF16_IO_DEFAULT))
+          and os.environ.get('FMGAN_NO_BF16_IO') != '1')
+    return precision, io
+
+
+def precision_context(args):
+    """What Trainer.step runs inside.  'fp32': nothing.  'bf16': torch.autocast(bfloat16) + the bf16 MFMA contraction of
+    the modulated convolutions (+ 16-bit activations in HBM with bf16_io) around the forward, backward and optimiser
+    steps of the iteration; parameters, the gradients Adam applies, its moments and the EMA stay fp32.  A labelled
+    reduced-precision extension, never the parity path; sample(), evaluate() and checkpoints do not enter it."""
+    precision, io = training_precision(args)
+    stack = contextlib.ExitStack()
+    if precision == 'bf16':
+        stack.enter_context(torch.autocast('cuda', dtype=torch.bfloat16))
+        stack.enter_context(_native.modconv_precision('bf16'))
+        stack.enter_context(_native.activation_io('16' if io else 'fp32'))
+    return stack
+
+
 class Trainer:
     """State of `train()` (train_3_encoder.py:756-828) for one rank: wrapped networks, g_ema, optimisers, counters.
 
@@ -485,23 +518,24 @@ class Trainer:
         reconstruction iteration.  ds_flag: a dual-supervision batch — D_edit (when given) and its optimiser take D's
         place in the D loss, R1 and the G step's adversarial term (:788-796), and the G step adds the face-regional
         term; extreme_ds_flag: an extreme-pose batch (L1 shrunk, face-id reference = input, face-regional weight 100)."""
-        a, n, ld = self.args, self.nets, self.loss_dict
-        G, E_Tsr, E_W, E_W_Plus = n['G'], n['E_Tsr'], n['E_W'], n['E_W_Plus']
-        Dn, d_optim = self.discriminator(ds_flag)
-        D_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, Dn, g_input, r_input, g_ref, a, ld, d_optim)
-        if self.iter_idx % a.d_reg_every == 0:
-            ld['r1'] = D_Reg_BackProp(g_ref, Dn, a, d_optim)
-        G_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, Dn, g_input, r_input, g_ref, a, ld, self.g_enc_optim,
-                        self.lpips_model, self.face_rec_model, self.fa_model, self.iter_idx, extreme_ds_flag, ds_flag)
-        if self.iter_idx % a.g_reg_every == 0 and a.use_g_reg:
-            ld['g_reg'], _, self.mean_path_length = G_Reg_BackProp(G, E_Tsr, E_W, E_W_Plus, g_input, r_input, a,
-                                                                   self.mean_path_length, self.g_enc_optim, ppl_choice)
-        if getattr(a, 'ema_fuse', False) and os.environ.get('FMGAN_NO_EMA_FUSE') != '1':
-            self.ema_plan = accumulate_fused(self.g_ema, self.bare['G'], self.accum, self.ema_plan)
-        else:
-            accumulate(self.g_ema, self.bare['G'], self.accum)
-        self.iter_idx += 1
-        return ld
+        with precision_context(self.args):
+            a, n, ld = self.args, self.nets, self.loss_dict
+            G, E_Tsr, E_W, E_W_Plus = n['G'], n['E_Tsr'], n['E_W'], n['E_W_Plus']
+            Dn, d_optim = self.discriminator(ds_flag)
+            D_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, Dn, g_input, r_input, g_ref, a, ld, d_optim)
+            if self.iter_idx % a.d_reg_every == 0:
+                ld['r1'] = D_Reg_BackProp(g_ref, Dn, a, d_optim)
+            G_Loss_BackProp(G, E_Tsr, E_W, E_W_Plus, Dn, g_input, r_input, g_ref, a, ld, self.g_enc_optim,
+                            self.lpips_model, self.face_rec_model, self.fa_model, self.iter_idx, extreme_ds_flag, ds_flag)
+            if self.iter_idx % a.g_reg_every == 0 and a.use_g_reg:
+                ld['g_reg'], _, self.mean_path_length = G_Reg_BackProp(G, E_Tsr, E_W, E_W_Plus, g_input, r_input, a,
+                                                                       self.mean_path_length, self.g_enc_optim, ppl_choice)
+            if getattr(a, 'ema_fuse', False) and os.environ.get('FMGAN_NO_EMA_FUSE') != '1':
+                self.ema_plan = accumulate_fused(self.g_ema, self.bare['G'], self.accum, self.ema_plan)
+            else:
+                accumulate(self.g_ema, self.bare['G'], self.accum)
+            self.iter_idx += 1
+            return ld
 
     def train_iteration(self, rec_loader, ds_loader, ep_loader=None, ppl_choice=None):
         """One iteration of train()'s schedule (train_3_encoder.py:780-812): the flags, the batch from the loader they
@@ -727,7 +761,9 @@ def Args_Parsing(argv=None):
     This build's own: --log_flush (rows of the loss ledger between two reads of the device, 50), --ema_fuse (the EMA in
     one launch, true), --resident, --bank_cache_dir, --num_workers, --val_sample_tile, --grad_sync (the data path and the
     Trainer's fields of the same names), --exp_dir ('Exp_' + Get_Readable_Cur_Time()), --start_iter (0; a checkpoint
-    loaded with --load_train_state sets it) and --use_loss_nets (build LPIPS / ArcFace with Module_Fix_Setup, true)."""
+    loaded with --load_train_state sets it), --use_loss_nets (build LPIPS / ArcFace with Module_Fix_Setup, true),
+    --precision (fp32 | bf16: Trainer.step under autocast(bfloat16) with the bf16 modulated convolutions; a labelled
+    extension, fp32 is the parity path) and --bf16_io (with bf16: 16-bit activations in HBM, precision_context)."""
     d = default_args()
     local = int(os.environ.get('LOCAL_RANK', '0'))
     device = f'cuda:{local % max(torch.cuda.device_count(), 1)}' if torch.cuda.is_available() else 'cpu'
@@ -804,6 +840,8 @@ def Args_Parsing(argv=None):
     add('--exp_dir', type=str, default=None)
     add('--start_iter', type=int, default=0)
     add('--use_loss_nets', type=_parse_bool, default=True)
+    add('--precision', type=str, default='fp32', choices=('fp32', 'bf16'))
+    add('--bf16_io', type=_parse_bool, default=BF16_IO_DEFAULT)
 
     args = parser.parse_args(argv)
     if args.exp_dir is None:
@@ -866,11 +904,25 @@ def Experiment_Status_Text(args):
     return text
 
 
+def Precision_Status_Text(args):
+    """This build's own line after the reference's text: the precision Trainer.step runs in.  Settings without the field
+    (default_args(), the reference's own) are fp32 and print the reference's text alone."""
+    if not hasattr(args, 'precision'):
+        return ''
+    precision = args.precision
+    text = '  Precision: ' + str(precision)
+    if precision == 'bf16':
+        on = training_precision(args)[1]
+        text += ' (16-bit activation kernels: ' + ('on' if on else 'off') + ')'
+    return text + '\n\n'
+
+
 def Print_Experiment_Status(args, exp_log_file):
-    """Prints the experiment's settings and writes them to the log (train_3_encoder.py:119-187); rank 0 only."""
+    """Prints the experiment's settings and writes them to the log (train_3_encoder.py:119-187), then the precision line;
+    rank 0 only."""
     if D_.get_rank() != 0:
         return
-    text = Experiment_Status_Text(args)
+    text = Experiment_Status_Text(args) + Precision_Status_Text(args)
     print(text)
     if exp_log_file is not None:
         exp_log_file.write(text)

@@ -51,6 +51,7 @@ extern "C" {
 #define FMGAN_F32 0
 #define FMGAN_F64 1
 #define FMGAN_F16 2
+#define FMGAN_BF16 3  /* fmgan_act16_* and fmgan_ufd16 only: the entry points above take FMGAN_F32/F64/F16 */
 
 int         fmgan_abi_version(void);
 const char *fmgan_status_string(int status);
@@ -899,6 +900,45 @@ long long fmgan_ema_blocks(long long numel);
 int fmgan_ema_f32(const fmgan_ema_entry *table_dev, int n_entries, long long total_blocks, float decay, float alpha,
                   void *stream);
 int fmgan_loss_row_f32(const fmgan_loss_ptrs *ptrs, int n, float *row_dev, void *stream);
+
+/*
+ * 16-bit activations in HBM (csrc/act16.hip): bf16 (FMGAN_BF16) and f16 (FMGAN_F16) tensors read and written as they
+ * are; every value is widened to fp32, the arithmetic is that of the fp32 entry point in the same order, and the result
+ * is narrowed once (round to nearest even) at the store.  Any other dtype: FMGAN_EUNSUPPORTED.  Data pointers need
+ * 2-byte alignment only: 16-byte accesses are used from the first 16-byte boundary of the output where the inputs are
+ * aligned there too, 2-byte accesses elsewhere.
+ *
+ * fmgan_act16_fba: fmgan_fused_bias_act on 16-bit x / refer / out, for the codes 10, 11, 12, 30, 31, 32 (another
+ * act*10+grad: FMGAN_EUNSUPPORTED).  bias is ALWAYS an fp32 array of size_b elements (NULL or size_b == 0: none).
+ * Layouts: step_b > 1 — planes of step_b elements, one bias scalar per plane (size_x % step_b != 0: FMGAN_EINVAL);
+ * step_b == 1 — the bias runs along the innermost dimension.  fmgan_act16_fba_select answers without a GPU: 1 planes
+ * kernel, 2 bias-innermost kernel, 3 planes kernel over the whole tensor (no bias), else the status the launch returns
+ * (the launch also returns FMGAN_EINVAL for a NULL or odd data pointer).
+ *
+ * fmgan_act16_fba_bwd: fmgan_fused_bias_act_bwd_f32 on 16-bit grad_out / ref_out / grad_in, any hw >= 1:
+ *   grad_in[p,i] = narrow((ref_out[p,i] > 0 ? grad_out[p,i] : alpha * grad_out[p,i]) * scale)
+ *   partial[p, blk] = fp32 sum of the block's share of the STORED grad_in[p, :] (widened back), fixed association
+ * partial [planes, fmgan_act16_fba_bwd_blocks(planes, hw)] f32; the blocks query returns 0 for planes <= 0, hw <= 0 or
+ * planes or hw > 0x7f000000 (the launch: FMGAN_EINVAL / FMGAN_EOVERFLOW; planes == 0 is FMGAN_OK without a launch).
+ *
+ * fmgan_ufd16: fmgan_upfirdn2d on 16-bit input / out with fp32 taps `kernel` [kernel_h, kernel_w] (un-flipped).
+ * fmgan_ufd16_select answers without a GPU: 1 = the FIR kernel (up = down = 1, minor = 1, at most 4x4 taps, any pads:
+ * 8 outputs per lane, taps accumulated with fmaf in tap order), 0 = one output per thread (everything else), else the
+ * launch's status: FMGAN_EINVAL for non-positive sizes or an empty output, FMGAN_EOVERFLOW when a plane or major does
+ * not fit 31 bits.
+ */
+int fmgan_act16_fba_select(int dtype, long long size_x, int size_b, int step_b, int act, int grad);
+int fmgan_act16_fba(int dtype, const void *x, const float *bias, const void *refer, void *out,
+                    long long size_x, int size_b, int step_b, int act, int grad, float alpha, float scale,
+                    void *stream);
+int fmgan_act16_fba_bwd_blocks(long long planes, int hw);
+int fmgan_act16_fba_bwd(int dtype, const void *grad_out, const void *ref_out, void *grad_in, float *partial,
+                        long long planes, int hw, float alpha, float scale, void *stream);
+int fmgan_ufd16_select(int dtype, int major, int in_h, int in_w, int minor, int kernel_h, int kernel_w,
+                       int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1);
+int fmgan_ufd16(int dtype, const void *input, const float *kernel, void *out, int major, int in_h, int in_w,
+                int minor, int kernel_h, int kernel_w, int up_x, int up_y, int down_x, int down_y,
+                int pad_x0, int pad_x1, int pad_y0, int pad_y1, void *stream);
 
 #ifdef __cplusplus
 }
