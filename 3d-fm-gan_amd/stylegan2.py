@@ -301,7 +301,7 @@ WINOGRAD = os.environ.get('FMGAN_NO_WINOGRAD', '0') != '1'   # Winograd F(2x2,3x
 
 
 def winograd_pays(batch, cin, cout, h, w):
-    """Plain StyledConv layers served by the Winograd form (op/_native.py: modconv2d_winograd) instead of the direct MFMA kernel.
+    """Plain StyledConv layers served by the Winograd form (op/_native/conv.py: modconv2d_winograd) instead of the direct MFMA kernel.
     Measured at B = 8 (profiles/r03_winograd.md): 16^2..64^2 x 512 channels 1.6-1.9x, 128^2 x 256 channels 1.23x, 256^2 x 128
     channels 0.83x (its transforms move 4x the activation through HBM): wide layers of at most 128^2 only, with enough tiles
     for the 16 GEMMs to fill the chip."""

@@ -2,6 +2,7 @@
 declares, pure-host entry points behave, the product has NO CPU path, and the product modules keep the
 reference's parameter/buffer names and shapes (manifests captured from the reference)."""
 import ctypes
+import inspect
 import os
 import re
 
@@ -177,10 +178,9 @@ def test_raw_pointer_entry_points_refuse_other_dtypes():
     for t in (torch.zeros(4, dtype=torch.bfloat16), torch.zeros(4, dtype=torch.float64), torch.zeros(4)):
         with pytest.raises(RuntimeError):
             _native.fp(t)
-    src = open(os.path.join(ROOT, '3d-fm-gan_amd', 'op', '_native.py')).read()
     for fn in ('modconv2d', 'modconv_demod', 'torgb', 'torgb_backward', 'noise_bias_act', 'blur_noise_bias_act',
                'modconv2d_rgb', 'modconv_wgrad', 'prelu_backward', 'fused_bias_act_backward'):
-        body = re.search(r'^def ' + fn + r'\(.*?(?=^def |\Z)', src, re.S | re.M).group(0)
+        body = inspect.getsource(getattr(_native, fn))
         assert ' ptr(' not in body.replace('ptr(wtb)', '').replace('ptr(wts)', '') and 'fp(' in body, fn
 
 

@@ -133,11 +133,11 @@ def test_wrappers_have_no_cpu_path():
 
 def test_activation_io_switch():
     from op import _native
-    assert _native.current_activation_io() == 'fp32' and _native._act_io == 'fp32'
+    assert _native.current_activation_io() == 'fp32' and _native.activation._act_io == 'fp32'
     h, b, f = (torch.zeros(1, dtype=d) for d in (torch.float16, torch.bfloat16, torch.float32))
     assert _native.io16(b) and not _native.io16(h) and not _native.io16(f)
     with _native.activation_io('16'):
-        assert _native.current_activation_io() == '16' and _native._act_io == '16'
+        assert _native.current_activation_io() == '16' and _native.activation._act_io == '16'
         assert _native.io16(b) and _native.io16(h) and not _native.io16(f)
         with _native.activation_io('fp32'):
             assert _native.current_activation_io() == 'fp32'

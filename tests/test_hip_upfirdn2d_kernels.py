@@ -256,7 +256,7 @@ def test_up2_second_grid_trip():
 
 # ------------------------------------------------------------------------------------------- fused epilogue, unequal pads
 def _fused_blur(p0, device, b, c, in_h, in_w, ps, rs, k, pads, nz, nw, bias, alpha, scale, force_path=-1):
-    """fmgan_blur_noise_bias_act_path_f32 with four pads (op/_native.py::blur_noise_bias_act has one pair, as its caller);
+    """fmgan_blur_noise_bias_act_path_f32 with four pads (op/_native/activation.py::blur_noise_bias_act has one pair, as its caller);
     a refusal raises."""
     from op import _native
     kh, kw = k.shape

@@ -1,4 +1,4 @@
-"""op/_native.py's launch bracket (`launching`) and status function (`served`): what an observer sees of a wrapper — one
+"""op/_native/core.py's launch bracket (`launching`) and status function (`served`): what an observer sees of a wrapper — one
 begin / end pair per bracket, with the wrapper's (name, info), also round a multi-launch wrapper and round a launch the
 library declines — and how a status becomes True / False / RuntimeError."""
 import numpy as np
@@ -21,10 +21,10 @@ def test_served_interprets_the_status():
     assert text and text != L.fmgan_status_string(0).decode()
     for fn in (_native.served, _native.check):
         with pytest.raises(RuntimeError) as e, launches.observed() as rec:
-            assert _native._observer is rec
+            assert _native.core._observer is rec
             fn(einval, 'some_launch')
         assert str(e.value) == f'some_launch: {text} (status {einval})'
-        assert isinstance(_native._observer, _native._NullObserver)         # back after a body that raised
+        assert isinstance(_native.core._observer, _native.core._NullObserver)         # back after a body that raised
 
 
 class _Recorder:
@@ -59,7 +59,7 @@ def test_single_launch_gives_one_bracket():
     pre = x + bias[None, :, None, None]
     # three fp32 roundings (add, slope, gain) of 2^-24 each, whatever the kernel's association: 1e-6 covers them
     torch.testing.assert_close(y, torch.where(pre > 0, pre, pre * 0.2) * 2 ** 0.5, rtol=1e-6, atol=1e-6)
-    assert isinstance(_native._observer, _native._NullObserver)
+    assert isinstance(_native.core._observer, _native.core._NullObserver)
 
 
 @pytest.mark.gpu
@@ -97,4 +97,4 @@ def test_declined_launch_returns_none_with_the_bracket_closed():
     out, events = _recorded(lambda: _native.bn_prelu(x, bn, slope))
     assert out is None                                                          # C % 4 != 0: the library declines
     assert events == [('begin', 'bn_prelu', (1, 6, 4, 4)), ('end',)]
-    assert isinstance(_native._observer, _native._NullObserver)
+    assert isinstance(_native.core._observer, _native.core._NullObserver)

@@ -21,7 +21,7 @@ OK, EINVAL, EUNSUPPORTED, EOVERFLOW = 0, -1, -2, -4
 
 # ------------------------------------------------------------------------------------------------ library and binding
 def test_library_exports_the_pair_input_entry_points():
-    """Both symbols are exported, declared in the header, and bound in op/_native.py's table with the header's argument
+    """Both symbols are exported, declared in the header, and bound in op/_native/core.py's table with the header's argument
     counts (eight ints; five pointers, eight ints and the stream)."""
     hdr = open(os.path.join(ROOT, 'include', 'fmgan_hip.h')).read()
     hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)

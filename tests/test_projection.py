@@ -27,7 +27,7 @@ def percept():
 
 # ------------------------------------------------------------------------------------------------ library and binding
 def test_library_exports_the_projection_entry_points():
-    """The four symbols are exported, declared in the header, and bound in op/_native.py's table with the header's
+    """The four symbols are exported, declared in the header, and bound in op/_native/core.py's table with the header's
     argument kinds in the header's order."""
     hdr = open(os.path.join(ROOT, 'include', 'fmgan_hip.h')).read()
     hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)

@@ -1,5 +1,5 @@
 """The pSp style heads' first convolution on the split-operand kernel (csrc/modconv_bf16.hip: conv3x3s2_mfma_bf16x3;
-op/_native.py: conv3x3s2_bf16x3, conv_weight_to_bf16x3; op/live_weights.py: split_conv_weight; psp_encoders.py:
+op/_native/conv.py: conv3x3s2_bf16x3, conv_weight_to_bf16x3; op/live_weights.py: split_conv_weight; psp_encoders.py:
 GradualStyleBlock with HEADS_X3).
 
 The exact value is float64 F.conv2d(stride 2, pad 1) + bias + LeakyReLU(0.01) on the CPU, the reference is the same

@@ -33,7 +33,7 @@ def rowmarch_tall_major(cus):
 
 
 # ------------------------------------------------------------------------------------------------ kernel 5: LDS-DMA ring
-# Inputs in the aligned-row layout (op/_native.py::aligned_rows_buffer(pad0=px0)); out_w % 4 == 0, >= 256, out_h >= 8.
+# Inputs in the aligned-row layout (op/_native/conv.py::aligned_rows_buffer(pad0=px0)); out_w % 4 == 0, >= 256, out_h >= 8.
 RING = [
     (5, 2, 12, 259, 4, 4, 1, 0, 0, 3, -1),    # 11 rows: an 8-row tile plus a 3-row remainder (the vmcnt(0) steps)
     (5, 2, 9, 254, 3, 4, 1, 3, 2, 0, 3),      # pad_x0 = 3: three masked positions on the left; 10 rows
