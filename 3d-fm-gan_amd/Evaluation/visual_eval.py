@@ -3,7 +3,9 @@ the sample grid (:86-142, and as one picture composed on the device: Batch_Eval_
 (:147-205: one photo, the frames of a render GIF) on the photo-encoded-once path of Util/network_util.py, the video
 reconstruction driver (:265-302: a photo GIF and a render GIF, frame by frame, in chunks) and the two test drivers that
 write result GIFs (:207-263, :304-340).  Every image leaves the device as uint8: one copy per source tensor, one per
-sheet, one per chunk of triptychs (op/canvas.py).  The 2-encoder scheme (three modules) is not provided."""
+sheet, one per chunk of triptychs (op/canvas.py).  These drivers take the four modules of the 3-encoder scheme; the
+2-encoder scheme (three modules) has the re-animation pair Reanimate_Frames_2_Encoder /
+Get_Single_Photo_Multi_Render_Result_2_Encoder of its own."""
 import os
 import random
 
@@ -12,7 +14,8 @@ import torch
 
 from op import _native
 from op.canvas import sheet_layout, tiles_to_canvas
-from Util.network_util import Encode_Photo, Forward_Inference_3_Encoder, Forward_Inference_Reanimate
+from Util.network_util import (Encode_Photo, Encode_Photo_2_Encoder, Forward_Inference_3_Encoder,
+                               Forward_Inference_Reanimate, Forward_Inference_Reanimate_2_Encoder)
 
 VAL_SET_LEN = 3
 NUM_IMG_PER_ID = 7
@@ -75,6 +78,41 @@ def Get_Single_Photo_Multi_Render_Result(photo_img_png_path, render_img_gif_path
     with Image.open(photo_img_png_path) as img:
         p_input = transform(img).to(device).unsqueeze(0)
     return Reanimate_Frames(p_input, Load_GIF_As_Img_List(render_img_gif_path, transform), model_modules, **kwargs)
+
+
+def Reanimate_Frames_2_Encoder(p_input, r_frames, model_modules, chunk=8, return_float=False, **kwargs):
+    """Reanimate_Frames for the 2-encoder scheme: model_modules = (E_Tsr, E_W, g_ema) (tensor encoder, modulation
+    encoder, generator); kwargs: mod_encode, co_modulation, sliced_layer, use_tanh, noise, randomize_noise.  The photo
+    is encoded once (Encode_Photo_2_Encoder), the frames run `chunk` at a time, one uint8 copy per chunk."""
+    if len(model_modules) != 3:
+        raise ValueError('model_modules = (E_Tsr, E_W, g_ema): the three modules of the 2-encoder scheme')
+    if chunk < 1:
+        raise ValueError('chunk must be positive')
+    E_Tsr, E_W, g_ema = model_modules
+    if not torch.is_tensor(r_frames):
+        r_frames = torch.stack([f.reshape(f.shape[-3:]) for f in r_frames], 0)
+    r_frames = r_frames.to(p_input.device)
+    mod_encode = kwargs.pop('mod_encode', 'Render Image')
+    co_modulation = kwargs.pop('co_modulation', None)
+    code = Encode_Photo_2_Encoder(p_input, E_Tsr, E_W, mod_encode, co_modulation)
+    images, floats = [], []
+    for i in range(0, r_frames.shape[0], chunk):
+        out = Forward_Inference_Reanimate_2_Encoder(code, r_frames[i:i + chunk].contiguous(), E_Tsr, E_W, g_ema,
+                                                    mod_encode=mod_encode, co_modulation=co_modulation, **kwargs)
+        images += list(tensor2im_batch(out).cpu().numpy())
+        if return_float:
+            floats.append(out.clone())      # a workspace-backed output may be overwritten by the next chunk
+    return (images, torch.cat(floats, 0)) if return_float else images
+
+
+def Get_Single_Photo_Multi_Render_Result_2_Encoder(photo_img_png_path, render_img_gif_path, model_modules, transform,
+                                                   device, **kwargs):
+    """Get_Single_Photo_Multi_Render_Result for the 2-encoder scheme; kwargs as Reanimate_Frames_2_Encoder."""
+    from PIL import Image
+    with Image.open(photo_img_png_path) as img:
+        p_input = transform(img).to(device).unsqueeze(0)
+    return Reanimate_Frames_2_Encoder(p_input, Load_GIF_As_Img_List(render_img_gif_path, transform), model_modules,
+                                      **kwargs)
 
 
 # ----------------------------------------------------------------------------------------------- sample pickers

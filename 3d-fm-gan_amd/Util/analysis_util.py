@@ -1,7 +1,7 @@
 """Reading a training log back (Util/analysis_util.py of the reference): the loss values of the iteration lines
 train_3_encoder.Train_Status_Line writes, the scores of the two evaluation blocks Trainer.Sample_Eval_Save_Ckpt writes,
-and the inference models of a checkpoint.  The parsing functions return what the reference's return on the same text.
-Not provided: the 2-encoder builder and the loss-curve figure (no matplotlib, no easydict here)."""
+and the inference models of a checkpoint (both schemes).  The parsing functions return what the reference's return on
+the same text.  Not provided: the loss-curve figure (no matplotlib, no easydict here)."""
 import math
 import types
 
@@ -91,3 +91,58 @@ def Model_Building_Func_3_Encoder(ckpt_model, device, gpu_device_ids=None):
     E_W.load_state_dict(ckpt_model['e_W'])
     E_W_Plus.load_state_dict(ckpt_model['e_W_Plus'])
     return g_ema.eval(), E_Tsr.eval(), E_W.eval(), E_W_Plus.eval()
+
+
+def _psp_depth(e_w_dict):
+    """Depth of the pSp body a state dict was saved from, read off its number of units (`body.N.`): 8 units are the
+    18-layer body (the reference's 325-key dict at 14 styles), 24 the 50-layer one (565 keys) — whatever the number of
+    style heads.  Anything else: ValueError naming the key count (the reference leaves its variable unbound there)."""
+    units = {k.split('.')[1] for k in e_w_dict.keys() if k.startswith('body.')}
+    depth = {8: 18, 24: 50}.get(len(units))
+    if depth is None:
+        raise ValueError(f'Model_Building_Func_2_Encoder: e_W has {len(e_w_dict.keys())} keys and {len(units)} body units; '
+                         f'8 units (the 18-layer pSp body, 325 keys) or 24 (the 50-layer one, 565 keys) are recognised')
+    return depth
+
+
+def Model_Building_Func_2_Encoder(ckpt_model, device, gpu_device_ids=None):
+    """(g_ema, E_Tsr, E_W, mod_encode, co_mod) of a checkpoint dict of the 2-encoder scheme (:135-201), the modules bare
+    and in eval mode on `device` as Model_Building_Func_3_Encoder builds its own.  Defaults where the checkpoint has no
+    mode keys: mod_space 'W', mod_encode 'Render Image', co_mod None; co_mod True means 'Multiplication'.  Size 256; the
+    Generator's style_dim is 1024 for 'Concatenation' and 'Tensor Transform', else 512.  The tensor encoder is
+    resnet18(tensor_encoding=True) in the plain mode, with tensor_transform=True for 'Tensor Transform', and the vector
+    form (tensor_encoding=False) for the other two co-modulation modes; the modulation encoder is the vector ResNet for
+    mod_space 'W' in the plain mode and the pSp encoder otherwise, with the 14 styles of size 256 and its depth read
+    off ckpt_model['e_W'].  gpu_device_ids is ignored: there is no nn.DataParallel."""
+    import resnet_encoder
+    from psp_encoder_model.encoders import psp_encoders
+    from .network_util import CO_MODULATION_MODE, MODULATION_ENCODING, Build_Generator_From_Dict
+    mod_space = ckpt_model['mod_space'] if 'mod_space' in ckpt_model.keys() else 'W'
+    mod_encode = ckpt_model['mod_encode'] if 'mod_encode' in ckpt_model.keys() else 'Render Image'
+    co_mod = ckpt_model['co_mod'] if 'co_mod' in ckpt_model.keys() else None
+    if co_mod is True:
+        co_mod = 'Multiplication'
+    elif co_mod is False:
+        co_mod = None
+    if mod_space not in ('W', 'W+') or mod_encode not in MODULATION_ENCODING or (
+            co_mod is not None and co_mod not in CO_MODULATION_MODE):
+        raise ValueError(f'Model_Building_Func_2_Encoder: mod_space {mod_space!r}, mod_encode {mod_encode!r}, '
+                         f'co_mod {co_mod!r} is not a mode of the 2-encoder scheme')
+    size = 256
+    latent_dim = 1024 if co_mod in ('Concatenation', 'Tensor Transform') else 512
+    g_ema = Build_Generator_From_Dict(ckpt_model['g_ema'], size=size, latent=latent_dim).to(device)
+    if co_mod is None:
+        E_Tsr = resnet_encoder.resnet18(tensor_encoding=True)
+    elif co_mod == 'Tensor Transform':
+        E_Tsr = resnet_encoder.resnet18(tensor_encoding=True, tensor_transform=True)
+    else:
+        E_Tsr = resnet_encoder.resnet18(tensor_encoding=False)
+    if co_mod is None and mod_space == 'W':
+        E_W = resnet_encoder.resnet18(tensor_encoding=False)
+    else:
+        opts = types.SimpleNamespace(input_nc=3, n_styles=int(math.log(size, 2)) * 2 - 2)
+        E_W = psp_encoders.GradualStyleEncoder(_psp_depth(ckpt_model['e_W']), 'ir_se', opts)
+    E_Tsr, E_W = E_Tsr.to(device), E_W.to(device)
+    E_Tsr.load_state_dict(ckpt_model['e_tsr'])
+    E_W.load_state_dict(ckpt_model['e_W'])
+    return g_ema.eval(), E_Tsr.eval(), E_W.eval(), mod_encode, co_mod

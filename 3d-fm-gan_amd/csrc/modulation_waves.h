@@ -18,6 +18,21 @@ __device__ __forceinline__ float equal_linear_wave(const float* __restrict__ wn,
   return wave_sum_xor(acc);
 }
 
+// sum_k wn[k] * x[k] over the concatenation x = [va (k_a floats) | vb (k_b floats)], never materialised: the SAME
+// lane-strided fma chain over the concatenated index (lane l takes k = l, l + 64, ..., crossing from va into vb wherever
+// k_a falls) and the same butterfly, so the bits equal equal_linear_wave<false> on the concatenated row.  Scalar loads
+// only: k_a is arbitrary, so vb's elements have no alignment relative to the lane stride.  The bias is the caller's.
+__device__ __forceinline__ float equal_linear_concat_wave(const float* __restrict__ wn, const float* __restrict__ va,
+                                                          const float* __restrict__ vb, int k_a, int k_b, int lane) {
+  float acc = 0.f;
+  const int k_in = k_a + k_b;
+  for (int k = lane; k < k_in; k += 64) {
+    const float x = k < k_a ? va[k] : vb[k - k_a];
+    acc = fmaf(wn[k], x, acc);
+  }
+  return wave_sum_xor(acc);
+}
+
 // Demodulation of one output channel.  PRE: wo is the channel's row of per-(o,i) squared-tap sums [cin]; otherwise its
 // raw taps [cin][ktaps].  Up to DEMOD_MAXJ * 64 input channels are held in registers across the samples of a wave.
 constexpr int DEMOD_MAXJ = 8;

@@ -16,6 +16,9 @@
 // sample block (26 x 1 MB at 1024^2, L2-resident across the samples), the demod launch each [cout, cin] table.
 // Grid: x = feature blocks of 4 waves (capped; a wave strides over the features beyond), y = entry, z = sample (capped at
 // 64, strided beyond).
+// The concatenating co-modulation modes of the 2-encoder scheme (the reference: Util/network_util.py:264-282) modulate
+// with x[t] = [v[t] | wplus[p, col]] over a [cin, Dv + Dw] matrix: style_bank_concat_f32 is the same walk with the
+// concatenated chain (equal_linear_concat_wave); every column is concatenated, `sliced` is not read.
 #include "modulation_waves.h"
 
 namespace {
@@ -42,6 +45,27 @@ __global__ __launch_bounds__(256) void style_bank_f32(const fmgan_style_bank_ent
       } else {
         acc = equal_linear_wave<false>(wn, xb, nullptr, style_dim, lane);
       }
+      if (lane == 0) out[(long long)t * e.cin + n] = bs ? acc + bs[n] : acc;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void style_bank_concat_f32(const fmgan_style_bank_entry* __restrict__ table,
+                                                             const float* __restrict__ v, const float* __restrict__ wplus,
+                                                             int wplus_batch, int batch, int dv, int dw,
+                                                             float* __restrict__ styles_out) {
+  const fmgan_style_bank_entry e = table[blockIdx.y];
+  if (e.col < 0 || e.col >= e.n_styles) return;   // block-uniform: never read outside wplus (the host refuses such a table)
+  const int lane = threadIdx.x & 63;
+  const float* __restrict__ ws = (const float*)e.ws;
+  const float* __restrict__ bs = (const float*)e.bs;
+  float* __restrict__ out = styles_out + (long long)batch * e.style_off;
+  for (int n = blockIdx.x * 4 + (threadIdx.x >> 6); n < e.cin; n += gridDim.x * 4) {   // wave-uniform
+    const float* wn = ws + (long long)n * (dv + dw);
+    for (int t = blockIdx.z; t < batch; t += gridDim.z) {
+      const long long p = wplus_batch == 1 ? 0 : t;
+      const float acc = equal_linear_concat_wave(wn, v + (long long)t * dv, wplus + (p * e.n_styles + e.col) * dw, dv, dw,
+                                                 lane);
       if (lane == 0) out[(long long)t * e.cin + n] = bs ? acc + bs[n] : acc;
     }
   }
@@ -79,6 +103,18 @@ extern "C" int fmgan_style_bank_f32(const fmgan_style_bank_entry* table_dev, int
   if (wplus_batch != 1 && wplus_batch != batch) return FMGAN_EINVAL;
   hipLaunchKernelGGL(style_bank_f32, dim3(SB_MAX_XBLOCKS, n_entries, batch < 64 ? batch : 64), dim3(256), 0,
                      (hipStream_t)stream, table_dev, w, wplus, wplus_batch, batch, style_dim, styles_out);
+  return fmgan_check_launch();
+}
+
+extern "C" int fmgan_style_bank_concat_f32(const fmgan_style_bank_entry* table_dev, int n_entries, const float* v,
+                                           const float* wplus, int wplus_batch, int batch, int dv, int dw,
+                                           float* styles_out, void* stream) {
+  if (n_entries <= 0 || n_entries > 65535 || batch < 0 || dv <= 0 || dw <= 0) return FMGAN_EINVAL;
+  if (batch == 0) return FMGAN_OK;
+  if (!table_dev || !v || !wplus || !styles_out) return FMGAN_EINVAL;
+  if (wplus_batch != 1 && wplus_batch != batch) return FMGAN_EINVAL;
+  hipLaunchKernelGGL(style_bank_concat_f32, dim3(SB_MAX_XBLOCKS, n_entries, batch < 64 ? batch : 64), dim3(256), 0,
+                     (hipStream_t)stream, table_dev, v, wplus, wplus_batch, batch, dv, dw, styles_out);
   return fmgan_check_launch();
 }
 

@@ -376,6 +376,18 @@ def style_bank(table, n_entries, w, wplus, styles_out):
                                          w.shape[0], w.shape[1], fp(styles_out), stream), 'style_bank')
 
 
+def style_bank_concat(table, n_entries, v, wplus, styles_out):
+    """Every table entry's style of the concatenating co-modulation in one launch: x = [v | wplus[:, col]] over each
+    entry's [cin, Dv + Dw] matrix; v [T,Dv], wplus [P,n_styles,Dw] with P in {1, T}, styles_out as for style_bank()."""
+    if v.dim() != 2 or wplus.dim() != 3 or not (v.is_contiguous() and wplus.is_contiguous()):
+        raise RuntimeError(f'style_bank_concat: V {tuple(v.shape)} / W+ {tuple(wplus.shape)} must be contiguous [T,Dv] / '
+                           f'[P,n,Dw]')
+    with on_device(v) as stream:
+        check(lib().fmgan_style_bank_concat_f32(fp(table.view(torch.float32)), n_entries, fp(v), fp(wplus), wplus.shape[0],
+                                                v.shape[0], v.shape[1], wplus.shape[2], fp(styles_out), stream),
+              'style_bank_concat')
+
+
 def demod_bank(table, n_entries, styles, batch, demod_out):
     """Every demodulated table entry's coefficients in one launch, from the flat styles of style_bank()."""
     with on_device(styles) as stream:

@@ -128,6 +128,7 @@ def lib():
     # csrc/style_bank.hip
     _sig(L.fmgan_style_bank_entry_bytes, [])
     _sig(L.fmgan_style_bank_f32, [vp, i, vp, vp, i, i, i, vp, vp])
+    _sig(L.fmgan_style_bank_concat_f32, [vp, i, vp, vp, i, i, i, i, vp, vp])
     _sig(L.fmgan_demod_bank_f32, [vp, i, vp, i, vp, vp])
     # csrc/live_weights.hip
     _sig(L.fmgan_weight_refresh_blocks, [i, i, i, i, ll], ll)

@@ -8,6 +8,10 @@ at the layer's refreshed `weight*scale` / `bias*lr_mul` / `sum_tap W^2` buffers 
 in two flat output buffers.  The table holds raw pointers of the LiveWeights buffers, so it is rebuilt whenever
 LiveWeights rebuilds (recognised by the identity of its device table, which every rebuild replaces), a deep copy starts
 without one, and it is valid only inside the Generator's inference forward, after the weight refresh.
+
+The concatenating co-modulation modes of the 2-encoder scheme ('Concatenation', 'Tensor Transform') modulate with
+x = [V | W+[:, col]] over a [cin, Dv + Dw] matrix: `run_concat` is the same table walked by fmgan_style_bank_concat_f32
+(the concatenation is never materialised), then the same demodulation launch.
 """
 from typing import NamedTuple, Optional
 
@@ -33,6 +37,13 @@ def sliced_columns(sliced_layer, n_latent, n_styles):
 def comod_column(w, wplus_i, i, sliced):
     """Latent column i of the multiplicative co-modulation: W * W+[:, i] where sliced, W elsewhere."""
     return w * wplus_i if i in sliced else w
+
+
+def concat_column(v, wplus_i):
+    """Latent column of the concatenating co-modulation: [V | W+[:, i]] ([T, Dv + Dw]; W+ of one photo serves T frames)."""
+    if wplus_i.shape[0] != v.shape[0]:
+        wplus_i = wplus_i.expand(v.shape[0], -1)
+    return torch.cat([v, wplus_i], 1)
 
 _ENTRY = np.dtype([('ws', '<u8'), ('bs', '<u8'), ('wsq', '<u8'), ('style_off', '<i8'), ('demod_off', '<i8'),
                    ('col', '<i4'), ('sliced', '<i4'), ('n_styles', '<i4'), ('cin', '<i4'), ('cout', '<i4'),
@@ -68,6 +79,7 @@ class Table:
             s_off += cin
             d_off += cout if demod else 0
         self.n, self.n_styles = len(rows), int(n_styles)
+        self.cols = [int(l['col']) for l in layers]
         self.style_floats, self.demod_floats = s_off, d_off
         self.style_dim = int(layers[0]['ws'].shape[1])
         self.device = layers[0]['ws'].device
@@ -87,6 +99,19 @@ class Table:
         if self.demod_floats:
             _native.demod_bank(self.dev, self.n, styles, w.shape[0], demod)
 
+    def run_concat(self, v, wplus, styles, demod):
+        """The two launches of the concatenating co-modulation, x = [v | wplus[:, col]], on the current stream.  Every
+        entry's column is read (the `sliced` flags are not), so every one must be a column of W+."""
+        if (v.dim() != 2 or wplus.dim() != 3 or wplus.shape[1] != self.n_styles
+                or v.shape[1] + wplus.shape[2] != self.style_dim or wplus.shape[0] not in (1, v.shape[0])
+                or styles.numel() < v.shape[0] * self.style_floats or demod.numel() < v.shape[0] * self.demod_floats):
+            raise RuntimeError('style_bank: buffers, Dv + Dw = style_dim, W+ columns or batch do not match the table')
+        if not all(0 <= c < self.n_styles for c in self.cols):
+            raise RuntimeError(f"style_bank: a concatenated column lies outside W+'s {self.n_styles} columns")
+        _native.style_bank_concat(self.dev, self.n, v, wplus, styles)
+        if self.demod_floats:
+            _native.demod_bank(self.dev, self.n, styles, v.shape[0], demod)
+
     def views(self, batch, styles, demod):
         """Per-layer Modulation([batch,cin] style, [batch,cout] demod or None): views into the flat buffers."""
         out = []
@@ -98,7 +123,8 @@ class Table:
 
 
 class StyleBank:
-    """The bank of one Generator: tables per (sliced columns, n_styles), output buffers per batch size."""
+    """The bank of one Generator: tables per (sliced columns, n_styles) — the concatenating form's under a key of its
+    own — and output buffers per batch size."""
 
     def __init__(self, generator):
         self.root = generator
@@ -129,13 +155,14 @@ class StyleBank:
         if lw._table is not self._source:   # LiveWeights rebuilt its buffers: every pointer of every table is stale.  Its
             # pointer key would miss a rebuild A -> B -> A between two of our forwards; a rebuild always makes a new table.
             self._source, self._tables, self._buffers = lw._table, {}, {}
-        tk = (sliced, n_styles)
+        tk = (sliced, n_styles)      # sliced: a frozenset of columns, or 'concat' (every column, the flags unused)
         if tk not in self._tables:
             rows = []
             for conv, col in self.layers():
                 ws, bs = live(conv.modulation)
                 lv = live(conv) if conv.kernel_size == 3 else None
-                rows.append(dict(ws=ws, bs=bs, wsq=lv[1] if lv else None, col=col, sliced=col in sliced,
+                rows.append(dict(ws=ws, bs=bs, wsq=lv[1] if lv else None, col=col,
+                                 sliced=sliced != 'concat' and col in sliced,
                                  cout=conv.out_channel, scale=conv.scale, eps=conv.eps, demodulate=conv.demodulate))
                 if conv.demodulate and lv is None:
                     raise RuntimeError('style_bank: a demodulated layer without refreshed weight squares')
@@ -152,3 +179,13 @@ class StyleBank:
         styles, demod = self._buffers[batch]
         table.run(w, wplus, styles, demod)
         return {conv: v for (conv, _), v in zip(self.layers(), table.views(batch, styles, demod))}
+
+    def run_concat(self, v, wplus):
+        """The same mapping for the concatenating co-modulation: V [T,Dv], W+ [P,n_styles,Dw], Dv + Dw = style_dim."""
+        table = self._table('concat', int(wplus.shape[1]))
+        batch = int(v.shape[0])
+        if batch not in self._buffers:
+            self._buffers[batch] = table.buffers(batch)
+        styles, demod = self._buffers[batch]
+        table.run_concat(v, wplus, styles, demod)
+        return {conv: m for (conv, _), m in zip(self.layers(), table.views(batch, styles, demod))}

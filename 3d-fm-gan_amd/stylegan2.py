@@ -21,7 +21,7 @@ from op import FusedLeakyReLU, fused_leaky_relu, upfirdn2d
 from op import _native, conv_grad, modconv, placement
 from op._native import amp_fwd as _amp_fwd, amp_bwd as _amp_bwd
 from op.live_weights import LiveWeights, live
-from op.style_bank import Modulation, StyleBank, comod_column, sliced_columns
+from op.style_bank import Modulation, StyleBank, comod_column, concat_column, sliced_columns
 from Util.streams import side_streams, run_on, overlap_ok
 
 _SQRT2 = math.sqrt(2.0)
@@ -590,36 +590,47 @@ class Generator(nn.Module):
     def _forward(self, noise_z, return_latents=False, inject_index=None, truncation=1, truncation_latent=None,
                  latent_styles=None, input_is_latent=False, noise=None, randomize_noise=True,
                  use_external_input_tensor=False, external_input_tensor=None, PPL_regularize=False,
-                 return_rgb_list=False, return_style_scalars=False, latent_columns=None, comod=None):
+                 return_rgb_list=False, return_style_scalars=False, latent_columns=None, comod=None, comod_concat=None):
         """latent_columns (not in the reference): callable i -> W+[:, i] replacing latent_styles; inference only, with
         an external input tensor (see _column_styles).
         comod (not in the reference): (W [T,D], W+ [P,n_styles,D] with P in {1,T}, sliced columns or None for all),
         replacing latent_styles with latent[:, i] = W * W+[:, i] where sliced, W elsewhere — all known before the network
         starts, so the styles and demodulation coefficients of every layer come from the style bank's two launches
         (op/style_bank.py; STYLE_BANK = False / FMGAN_NO_STYLE_BANK=1: per layer, from the same columns).  Inference
-        only, float32 GPU tensors, with an external input tensor of T samples.  The bank reads the LiveWeights buffers, so
+        only, float32 GPU tensors, with an external input tensor of T samples or (the 2-encoder scheme's 'Multiplication'
+        mode has none) the Generator's own ConstantInput for T samples.  The bank reads the LiveWeights buffers, so
         with STYLE_BANK on a Generator whose weights could not be refreshed (parameters that are not contiguous float32
-        GPU tensors) raises RuntimeError rather than changing to the per-layer form unasked; STYLE_BANK = False serves it."""
-        def run(noise, external_input_tensor, *comod):
+        GPU tensors) raises RuntimeError rather than changing to the per-layer form unasked; STYLE_BANK = False serves it.
+        comod_concat (not in the reference): (V [T,Dv], W+ [P,n_styles,Dw] with P in {1,T}), Dv + Dw = style_dim,
+        replacing latent_styles with latent[:, i] = [V | W+[:, i]] for every column (the 2-encoder scheme's 'Concatenation'
+        and 'Tensor Transform' modes, Util/network_util.py:264-282) — from the bank's concatenating launch, the
+        concatenation never materialised, or (STYLE_BANK = False) per layer from each concatenated column.  Same
+        restrictions as comod, and not together with it."""
+        if comod is not None and comod_concat is not None:
+            raise ValueError('comod and comod_concat are two forms of co-modulation: give one')
+
+        def run(noise, external_input_tensor, *codes):
             source = self._style_source(noise_z, return_latents, inject_index, truncation, truncation_latent, latent_styles,
                                         input_is_latent, noise, randomize_noise, use_external_input_tensor,
                                         external_input_tensor, PPL_regularize, return_style_scalars, latent_columns,
-                                        comod or None)
+                                        codes if comod is not None else None, codes if comod_concat is not None else None)
             return self._synthesis(*source, PPL_regularize, return_rgb_list, return_style_scalars)
-        if comod is None:
+        if comod is None and comod_concat is None:
             return run(noise, external_input_tensor)
-        return _fp32(run, noise, external_input_tensor, *comod)    # the bank takes raw fp32 pointers, like the fused layers
+        # the bank takes raw fp32 pointers, like the fused layers
+        return _fp32(run, noise, external_input_tensor, *(comod if comod is not None else comod_concat))
 
     def _comod_styles(self, comod, external_input_tensor):
         """Style source of comod=(W, W+, sliced): the bank's result, or (STYLE_BANK = False) the columns one at a time."""
         w_r, w_plus, sliced = comod
-        for t in (w_r, w_plus, external_input_tensor):
+        tensors = [t for t in (w_r, w_plus, external_input_tensor) if t is not None]   # no tensor: ConstantInput
+        for t in tensors:
             _native.require_gpu(t, 'comod input')
         if (w_r.dim() != 2 or w_plus.dim() != 3 or w_plus.shape[0] not in (1, w_r.shape[0])
                 or w_plus.shape[2] != w_r.shape[1] or w_plus.shape[1] < self.n_latent
-                or external_input_tensor.shape[0] != w_r.shape[0]):
+                or (external_input_tensor is not None and external_input_tensor.shape[0] != w_r.shape[0])):
             raise ValueError('comod: W [T,D], W+ [1 or T, n_styles >= n_latent, D] and an external tensor of T samples')
-        for t in (w_r, w_plus, external_input_tensor):
+        for t in tensors:
             _native.fp(t)           # float32 GPU tensors only: the kernels take raw pointers
         w_r, w_plus = w_r.contiguous(), w_plus.contiguous()
         cols = sliced_columns(sliced, self.n_latent, w_plus.shape[1])
@@ -638,15 +649,56 @@ class Generator(nn.Module):
             return cache[i]
         return _column_styles(column)
 
+    def _concat_styles(self, comod_concat, external_input_tensor):
+        """Style source of comod_concat=(V, W+): the bank's result, or (STYLE_BANK = False) each concatenated column, built
+        once, one at a time."""
+        if len(comod_concat) != 2:
+            raise ValueError('comod_concat: (V [T,Dv], W+ [1 or T, n_styles >= n_latent, Dw])')
+        v, w_plus = comod_concat
+        tensors = [t for t in (v, w_plus, external_input_tensor) if t is not None]     # no tensor: ConstantInput
+        for t in tensors:
+            _native.require_gpu(t, 'comod_concat input')
+        if (v.dim() != 2 or w_plus.dim() != 3 or w_plus.shape[0] not in (1, v.shape[0])
+                or v.shape[1] + w_plus.shape[2] != self.style_dim or w_plus.shape[1] < self.n_latent
+                or (external_input_tensor is not None and external_input_tensor.shape[0] != v.shape[0])):
+            raise ValueError('comod_concat: V [T,Dv], W+ [1 or T, n_styles >= n_latent, Dw] with Dv + Dw = style_dim and, '
+                             'if any, an external tensor of T samples')
+        for t in tensors:
+            _native.fp(t)           # float32 GPU tensors only: the kernels take raw pointers
+        v, w_plus = v.contiguous(), w_plus.contiguous()
+        if STYLE_BANK:
+            if self._live_weights is None or not self._live_weights.active:
+                raise RuntimeError('comod_concat: the style bank needs the Generator\'s refreshed weights (call the '
+                                   'module, with float32 parameters on the GPU)')
+            if getattr(self, '_style_bank', None) is None:
+                self._style_bank = StyleBank(self)
+            return _bank_styles(self._style_bank.run_concat(v, w_plus))
+        cache = {}
+
+        def column(i):
+            if i not in cache:
+                cache[i] = concat_column(v, w_plus[:, i])
+            return cache[i]
+        return _column_styles(column)
+
     def _style_source(self, noise_z, return_latents, inject_index, truncation, truncation_latent, latent_styles,
                       input_is_latent, noise, randomize_noise, use_external_input_tensor, external_input_tensor,
-                      PPL_regularize, return_style_scalars, latent_columns, comod):
+                      PPL_regularize, return_style_scalars, latent_columns, comod, comod_concat=None):
         """(style source, noise of every layer, first activation) for the arguments of _forward."""
         plain = use_external_input_tensor and not (PPL_regularize or return_latents or return_style_scalars)
-        if comod is not None:
-            if not plain or torch.is_grad_enabled() or latent_columns is not None or external_input_tensor is None:
-                raise ValueError('comod serves the plain inference forward (no_grad, external input tensor) only')
-            styles = self._comod_styles(comod, external_input_tensor)
+        frames = None           # co-modulation without an external tensor: samples of the Generator's own ConstantInput
+        if comod is not None or comod_concat is not None:
+            # the plain inference forward on the GPU: with the caller's input tensor, or with this Generator's constant
+            # input (which then has to be where the kernels are: a Generator on the CPU has no such forward)
+            served = not (PPL_regularize or return_latents or return_style_scalars) and (
+                external_input_tensor is not None if use_external_input_tensor else self.input.input.is_cuda)
+            if not served or torch.is_grad_enabled() or latent_columns is not None:
+                raise ValueError(('comod' if comod is not None else 'comod_concat') +
+                                 ' serves the plain inference forward (no_grad, external input tensor) only')
+            tensor = external_input_tensor if use_external_input_tensor else None
+            styles = self._comod_styles(comod, tensor) if comod is not None else self._concat_styles(comod_concat, tensor)
+            if tensor is None:
+                frames = (comod or comod_concat)[0]
         elif latent_columns is not None:
             if not plain:
                 raise ValueError('latent_columns serves the plain inference forward only')
@@ -661,7 +713,7 @@ class Generator(nn.Module):
         if use_external_input_tensor:
             assert external_input_tensor is not None
             return styles, noise, external_input_tensor
-        return styles, noise, self.input(styles.latent)
+        return styles, noise, self.input(styles.latent if frames is None else frames)
 
     def _synthesis(self, styles, noise, out, PPL_regularize, return_rgb_list, return_style_scalars):
         """The synthesis network on the first activation `out`: layer L, reading latent column i, gets styles(L, i)."""

@@ -557,6 +557,11 @@ int fmgan_weight_refresh_f32(const fmgan_refresh_entry *table_dev, int n_entries
  *   style_dim], wplus_batch = 1 (one photo shared by the batch: p = 0) or batch (p = t).
  * fmgan_demod_bank_f32:  demod_out[batch*demod_off + t*cout + o] = 1/sqrt(scale^2 * sum_i wsq[o,i] * s[t,i]^2 + eps) for
  *   every entry with demodulate != 0 and wsq != NULL, s = that entry's block of `styles`.
+ * fmgan_style_bank_concat_f32 (the concatenating co-modulation of the 2-encoder scheme): every entry's ws is
+ *   [cin, dv + dw] and x[t,k] = v[t,k] for k < dv, wplus[p,col,k-dv] for k >= dv; v [batch, dv], wplus [wplus_batch,
+ *   n_styles, dw]; `sliced` is not read (every column is concatenated), dv and dw are any positive ints.  ONE fma chain
+ *   over the concatenated index: the bits of fmgan_equal_linear_f32 on the materialised concatenation.  An entry whose
+ *   col is outside [0, n_styles) is skipped.  Its demodulation coefficients come from fmgan_demod_bank_f32.
  * Same fma chains, butterfly and rounding as the per-layer entry points (one shared definition): bit-identical.
  * No atomics, one writer per element.  EINVAL for NULL pointers, n_entries outside [1, 65535], non-positive dims or
  * wplus_batch not in {1, batch}; batch == 0 is a no-op (both checked before any HIP call).
@@ -572,6 +577,9 @@ typedef struct fmgan_style_bank_entry {
 int fmgan_style_bank_entry_bytes(void);   /* sizeof(fmgan_style_bank_entry), for bindings that build the table by hand */
 int fmgan_style_bank_f32(const fmgan_style_bank_entry *table_dev, int n_entries, const float *w, const float *wplus,
                          int wplus_batch, int batch, int style_dim, float *styles_out, void *stream);
+int fmgan_style_bank_concat_f32(const fmgan_style_bank_entry *table_dev, int n_entries, const float *v,
+                                const float *wplus, int wplus_batch, int batch, int dv, int dw, float *styles_out,
+                                void *stream);
 int fmgan_demod_bank_f32(const fmgan_style_bank_entry *table_dev, int n_entries, const float *styles, int batch,
                          float *demod_out, void *stream);
 
