@@ -29,8 +29,11 @@
 //     the MFMA launch far less.
 // Shapes it serves: cin % 16 == 0, cout % 32 == 0, position grid at least 32 wide; everything else returns
 // FMGAN_EUNSUPPORTED and the caller keeps the fp32 kernel (the 4^2..16^2 layers: < 3 % of the FLOPs at B=8).
-// One instantiation of the split-operand contraction IS on the default inference path: conv3x3s2_mfma_bf16x3 below, the
-// first convolution of the pSp encoder's fine style heads.
+// One kernel family of the split-operand contraction IS on the default inference path: conv3x3_mfma_bf16x3 below, a plain
+// 3x3 / pad 1 convolution at stride 1 or 2.  It serves the first convolution of the pSp encoder's fine style heads and
+// the encoder body's 3x3 convolutions whose output is at least 32 wide (at a 256^2 photo: both convolutions of units
+// 0-5 and conv1 of unit 6, thirteen of sixteen; helpers.py body_x3_serves is the rule, FMGAN_PSP_BODY_X3=0 the switch;
+// DESIGN 3.3c / 3.4d, profiles/psp_body_x3.md).
 #include <type_traits>
 #include "common.h"
 
@@ -719,46 +722,78 @@ __global__ __launch_bounds__(256, 2) void modconv_mfma_bf16x3(const BFParams p) 
 //     mid + lo, still exact).  Inf or NaN cannot be split — (Inf, 0, 0) times a finite (bh, 0, 0) would give Inf*0 —
 //     so a block that meets one among ITS operands (patch or weight rows; found while staging, no extra pass) recomputes
 //     its tile with plain fp32 FMAs in a fixed order: the non-finite outputs are those of the fp32 products.
-struct S2Params {
-  const float* in; const unsigned short* wt; const float* bias; float* out;
+//
+// The family (template arguments of conv3x3_mfma_bf16x3; the contraction and its summation order are the same in all):
+//   * S = 2 (above) or 1: the stride-1 patch is the plain one, rows y0-1 .. y0+4 and columns x0-1 .. x0+32 in order
+//     (6 x 34 = 19 KB in three pieces, a third of the stride-2 one), one LDS slot per thread; same 64 x (4 x 32) tile,
+//     built for three blocks per CU (the registers then set the limit, not the LDS);
+//   * NHWC_IN: the input is channels_last storage in[b][y][x][i].  A slot's 16 channels are 64 contiguous bytes: four
+//     16-byte loads (by four neighbouring lanes) instead of sixteen 4-byte ones a plane apart.  Needs cin % 4 == 0 (a
+//     quad is inside cin or outside: outside it is parked out of range like the padding) and a 16-byte aligned input;
+//   * EPI: none (plain store) / bias + LeakyReLU(alpha) / per-channel PReLU v > 0 ? v : slope[o] * v without bias
+//     (aten's prelu arithmetic on the accumulator value: the fused result is conv followed by aten PReLU).  The fp32
+//     recomputation of a block with Inf / NaN operands applies the same epilogue.
+// The encoder body's 3x3 convolutions (helpers._fused_unit: conv1 with the PReLU epilogue, conv2 with none, both
+// channels_last in and out) and the style heads' first convolution (stride 2, LeakyReLU) run on it.
+enum { C3_NONE = 0, C3_LRELU = 1, C3_PRELU = 2 };
+
+struct C3Params {
+  const float* in; const unsigned short* wt; const float* aux; float* out;     // aux: bias (C3_LRELU) or slope (C3_PRELU)
   int batch, cin, cout, h, w, oh, ow;
   int tiles_x, tiles_y, o_tiles, mp;
   float alpha;
-  int out_nhwc;                                          // 0: out[b][o][y][x]; 1: out[b][y][x][o] (channels_last storage)
+  int stride, epi;
+  int in_nhwc, out_nhwc;                                 // 0: [b][c][y][x]; 1: [b][y][x][c] (channels_last storage)
 };
 
-struct S2Tile {
+template <int S>
+struct C3Tile {
   static constexpr int BM = 64, TH = 4, TW = 32;
-  static constexpr int PH = 2 * (TH - 1) + 3, PWP = 2 * (TW - 1) + 3, EVEN = (PWP + 1) / 2;
+  static constexpr int PH = S * (TH - 1) + 3, PWP = S * (TW - 1) + 3, EVEN = (PWP + 1) / 2;
   static constexpr int PLANE = PH * PWP;
   static constexpr size_t LDS = (size_t)(3 * 2 * PLANE) * 16;
+  static constexpr int BLOCKS_PER_CU = S == 1 ? 3 : 2;
 };
 
-// the launch's plan; false when the shape is not served (32-bit buffer ranges, grid size)
-bool s2_plan(S2Params& p) {
+// the launch's plan; false when the shape is not served (stride, channels_last width, 32-bit buffer ranges, grid size)
+bool c3_plan(C3Params& p) {
   if (p.batch <= 0 || p.cin <= 0 || p.cout <= 0 || p.h <= 0 || p.w <= 0) return false;
-  p.oh = (p.h - 1) / 2 + 1; p.ow = (p.w - 1) / 2 + 1;
+  if (p.stride != 1 && p.stride != 2) return false;
+  if (p.in_nhwc && (p.cin & 3)) return false;                                               // 16-byte channel quads
+  using Tile = C3Tile<1>;                                                                   // (the output tile of both strides)
+  p.oh = (p.h - 1) / p.stride + 1; p.ow = (p.w - 1) / p.stride + 1;
   p.mp = (p.cout + 31) / 32 * 32;
-  p.tiles_x = (p.ow + S2Tile::TW - 1) / S2Tile::TW;
-  p.tiles_y = (p.oh + S2Tile::TH - 1) / S2Tile::TH;
-  p.o_tiles = (p.cout + S2Tile::BM - 1) / S2Tile::BM;
-  if ((long long)p.cin * p.h * p.w * 4 >= 0xFFFFFFF0LL) return false;                      // one sample's input
+  p.tiles_x = (p.ow + Tile::TW - 1) / Tile::TW;
+  p.tiles_y = (p.oh + Tile::TH - 1) / Tile::TH;
+  p.o_tiles = (p.cout + Tile::BM - 1) / Tile::BM;
+  // one sample's input, either layout: the largest byte offset a lane forms is below cin * h * w * 4
+  if ((long long)p.cin * p.h * p.w * 4 >= 0xFFFFFFF0LL) return false;
   if ((long long)((p.cin + 15) / 16) * 54 * p.mp * 16 >= 0xFFFFFFF0LL) return false;       // the weight image
   if ((long long)p.o_tiles * p.tiles_x * p.tiles_y * p.batch > 0x7fffffffLL) return false;
   if ((long long)p.batch * p.cout * p.oh * p.ow > (1LL << 40)) return false;
   return true;
 }
 
-__global__ __launch_bounds__(256, 2) void conv3x3s2_mfma_bf16x3(const S2Params p) {
-  using Tile = S2Tile;
+template <int S, bool NHWC_IN, int EPI>
+__global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf16x3(const C3Params p) {
+  using Tile = C3Tile<S>;
   constexpr int BM = Tile::BM, TH = Tile::TH, TW = Tile::TW, PWP = Tile::PWP, EVEN = Tile::EVEN, PLANE = Tile::PLANE;
   constexpr int RNP = 2;
-  constexpr int NU = (PLANE + 255) / 256;
+  // staging units per thread and floats per unit.  A thread owns whole slots: 16 channels a plane apart (NCHW input) or
+  // as four 16-byte loads (channels_last input, stride 1: 204 slots, the staging is a small part of the block's work).
+  // QUAD (channels_last input, stride 2: 585 slots for the same products): four lanes share a slot, each on one 16-byte
+  // channel quad of its 64 contiguous bytes, so that one load instruction of a wave covers 16 whole slots — a lane on a
+  // whole slot of its own, 64 lanes 4 KB apart, measured 20 % slower than the NCHW staging at the heads' shape.  (At
+  // stride 1 the QUAD form spills at three blocks per CU.)
+  constexpr bool QUAD = NHWC_IN && S == 2;
+  constexpr int NU = QUAD ? (4 * PLANE + 255) / 256 : (PLANE + 255) / 256, NV = QUAD ? 4 : 16;
+  static_assert(NU <= 16, "one staging unit per issue_x call");
   extern __shared__ u32x4 smem_q[];
   u32x4* Xs = smem_q;                                   // [3 pieces][2 k-halves][PLANE]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, khalf = lane >> 5, wm = wave & 1, wn = wave >> 1;
+  const int kq = tid & 3;                                // QUAD: this lane's channel quad of its slots
   unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
   const int o_tile = lb % p.o_tiles; lb /= p.o_tiles;
   const int tx_i = lb % p.tiles_x; lb /= p.tiles_x;
@@ -786,57 +821,92 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_mfma_bf16x3(const S2Params p
   unsigned xvo[NU];
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
-    const int q = tid + 256 * u;                         // the LDS slot: row r, then even patch columns, then odd
+    const int q = QUAD ? (tid + 256 * u) >> 2 : tid + 256 * u;      // the LDS slot: row r, then (S = 2) even patch columns, then odd
     const int r = q / PWP, t = q - r * PWP;
-    const int c = t < EVEN ? 2 * t : 2 * (t - EVEN) + 1;
-    const int y = 2 * y0 + r - 1, x = 2 * x0 + c - 1;
-    xvo[u] = (q < PLANE && y >= 0 && y < p.h && x >= 0 && x < p.w) ? (unsigned)(y * p.w + x) * 4u : PARK;
+    const int c = S == 1 ? t : (t < EVEN ? 2 * t : 2 * (t - EVEN) + 1);
+    const int y = S * y0 + r - 1, x = S * x0 + c - 1;
+    const bool inside = q < PLANE && y >= 0 && y < p.h && x >= 0 && x < p.w;
+    const unsigned pos_bytes = NHWC_IN ? 4u * (unsigned)p.cin : 4u;
+    xvo[u] = inside ? (unsigned)(y * p.w + x) * pos_bytes + (QUAD ? 16u * (unsigned)kq : 0u) : PARK;
   }
   const int arow = o0 + wm * 32 + l31;                   // this lane's weight row (a 32-row group lies wholly inside mp or not)
   const unsigned avo = arow < p.mp ? (unsigned)(khalf * p.mp + arow) * 16u : PARK;
 
-  float xv[NU][16];
-  auto issue_x = [&](int i0, int kc) {                   // channel i0 + kc of the patch (past cin: channel 0, dropped in commit_x)
-    const unsigned soff = i0 + kc < p.cin ? (unsigned)((i0 + kc) * hw * 4) : 0u;
+  float xv[NU][NV];
+  auto issue_x = [&](int i0, int kc) {
+    if constexpr (QUAD) {                                // staging unit kc: channels i0 + 4*kq .. + 3 of its slot (past cin: parked, zeros)
+      if (kc < NU) {
+        const unsigned vo = i0 + 4 * kq < p.cin ? xvo[kc] : PARK;
+        const u32x4 v = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, vo, (unsigned)(i0 * 4), 0));
 #pragma unroll
-    for (int u = 0; u < NU; ++u)
-      xv[u][kc] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_x, xvo[u], soff, 0));
+        for (int e = 0; e < 4; ++e) xv[kc][e] = __uint_as_float(v[e]);
+      }
+    } else if constexpr (NHWC_IN) {                      // channels i0 + kc .. + 3 of the patch, once per quad (past cin: parked)
+      if ((kc & 3) == 0) {
+        const bool inside = i0 + kc < p.cin;
+        const unsigned soff = inside ? (unsigned)((i0 + kc) * 4) : 0u;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+          const u32x4 v = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, inside ? xvo[u] : PARK, soff, 0));
+#pragma unroll
+          for (int e = 0; e < 4; ++e) xv[u][kc + e] = __uint_as_float(v[e]);
+        }
+      }
+    } else {                                             // channel i0 + kc of the patch (past cin: channel 0, dropped in commit_x)
+      const unsigned soff = i0 + kc < p.cin ? (unsigned)((i0 + kc) * hw * 4) : 0u;
+#pragma unroll
+      for (int u = 0; u < NU; ++u)
+        xv[u][kc] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_x, xvo[u], soff, 0));
+    }
   };
   float xflag = 0.f;                                     // NaN once an activation of this block's patch is Inf or NaN
+  // two activations as their three bf16 pieces (hi clamped to the largest finite bf16: the residual stays exact)
+  auto split2 = [&](float v0, float v1, unsigned& h01, unsigned& m01, unsigned& l01) {
+    xflag = __builtin_fmaf(v0, 0.f, xflag);
+    xflag = __builtin_fmaf(v1, 0.f, xflag);
+    h01 = pack_bf16(__builtin_amdgcn_fmed3f(v0, -BF16_MAX, BF16_MAX), __builtin_amdgcn_fmed3f(v1, -BF16_MAX, BF16_MAX));
+    const float r0 = v0 - __uint_as_float(h01 << 16), r1 = v1 - __uint_as_float(h01 & 0xffff0000u);
+    m01 = pack_bf16(r0, r1);
+    const float s0 = r0 - __uint_as_float(m01 << 16), s1 = r1 - __uint_as_float(m01 & 0xffff0000u);
+    l01 = pack_bf16(s0, s1);
+  };
   auto commit_x = [&](int i0) {
-    if (i0 + 16 > p.cin) {                               // the partial last chunk: zeros past cin
+    if constexpr (QUAD) {                                // a quad is half of a k-half's 16-byte slot: 8-byte LDS writes
 #pragma unroll
-      for (int kc = 0; kc < 16; ++kc)
-        if (i0 + kc >= p.cin) {
-#pragma unroll
-          for (int u = 0; u < NU; ++u) xv[u][kc] = 0.f;
+      for (int u = 0; u < NU; ++u) {
+        const int q = (tid + 256 * u) >> 2;
+        if (q < PLANE) {
+          unsigned h[2], m[2], l[2];
+          split2(xv[u][0], xv[u][1], h[0], m[0], l[0]);
+          split2(xv[u][2], xv[u][3], h[1], m[1], l[1]);
+          u32x2* dst = reinterpret_cast<u32x2*>(Xs + (kq >> 1) * PLANE + q) + (kq & 1);
+          u32x2 ph = {h[0], h[1]}, pm = {m[0], m[1]}, pl = {l[0], l[1]};
+          dst[0] = ph; dst[4 * PLANE] = pm; dst[8 * PLANE] = pl;       // a piece is 2 * PLANE slots
         }
-    }
+      }
+    } else {
+      if (i0 + 16 > p.cin) {                             // the partial last chunk: zeros past cin
 #pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      const int q = tid + 256 * u;
-      if (q < PLANE) {
+        for (int kc = 0; kc < 16; ++kc)
+          if (i0 + kc >= p.cin) {
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-          u32x4 ph, pm, pl;
-          unsigned* qh = reinterpret_cast<unsigned*>(&ph);
-          unsigned* qm = reinterpret_cast<unsigned*>(&pm);
-          unsigned* ql = reinterpret_cast<unsigned*>(&pl);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float v0 = xv[u][8 * hh + 2 * e], v1 = xv[u][8 * hh + 2 * e + 1];
-            xflag = __builtin_fmaf(v0, 0.f, xflag);
-            xflag = __builtin_fmaf(v1, 0.f, xflag);
-            const unsigned h01 = pack_bf16(__builtin_amdgcn_fmed3f(v0, -BF16_MAX, BF16_MAX),
-                                           __builtin_amdgcn_fmed3f(v1, -BF16_MAX, BF16_MAX));
-            const float r0 = v0 - __uint_as_float(h01 << 16), r1 = v1 - __uint_as_float(h01 & 0xffff0000u);
-            const unsigned m01 = pack_bf16(r0, r1);
-            const float s0 = r0 - __uint_as_float(m01 << 16), s1 = r1 - __uint_as_float(m01 & 0xffff0000u);
-            qh[e] = h01; qm[e] = m01; ql[e] = pack_bf16(s0, s1);
+            for (int u = 0; u < NU; ++u) xv[u][kc] = 0.f;
           }
-          Xs[(0 * 2 + hh) * PLANE + q] = ph;
-          Xs[(1 * 2 + hh) * PLANE + q] = pm;
-          Xs[(2 * 2 + hh) * PLANE + q] = pl;
+      }
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        const int q = tid + 256 * u;
+        if (q < PLANE) {
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh) {
+            unsigned h[4], m[4], l[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) split2(xv[u][8 * hh + 2 * e], xv[u][8 * hh + 2 * e + 1], h[e], m[e], l[e]);
+            u32x4 ph = {h[0], h[1], h[2], h[3]}, pm = {m[0], m[1], m[2], m[3]}, pl = {l[0], l[1], l[2], l[3]};
+            Xs[(0 * 2 + hh) * PLANE + q] = ph;
+            Xs[(1 * 2 + hh) * PLANE + q] = pm;
+            Xs[(2 * 2 + hh) * PLANE + q] = pl;
+          }
         }
       }
     }
@@ -844,7 +914,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_mfma_bf16x3(const S2Params p
 
   int pbase[RNP];
 #pragma unroll
-  for (int g = 0; g < RNP; ++g) pbase[g] = khalf * PLANE + 2 * (wn * RNP + g) * PWP + l31;
+  for (int g = 0; g < RNP; ++g) pbase[g] = khalf * PLANE + S * (wn * RNP + g) * PWP + l31;
 
   struct Ops { u32x4 a[3]; bf16x8 b[3][RNP]; };
   auto fetch_a = [&](Ops& o, unsigned soff_chunk, int t) {
@@ -854,7 +924,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_mfma_bf16x3(const S2Params p
   };
   auto fetch_b = [&](Ops& o, int t) {
     const int ky = t / 3, kx = t - 3 * ky;
-    const int off = ky * PWP + (kx & 1) * EVEN + (kx >> 1);     // patch column 2*l31 + kx
+    const int off = S == 1 ? ky * PWP + kx : ky * PWP + (kx & 1) * EVEN + (kx >> 1);     // patch column S*l31 + kx
 #pragma unroll
     for (int pc = 0; pc < 3; ++pc)
 #pragma unroll
@@ -909,6 +979,18 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_mfma_bf16x3(const S2Params p
 
   float* out_b = p.out + (long long)b * p.cout * p.oh * p.ow;
   const float alpha = p.alpha;
+  // the epilogue on one accumulator value; a = bias[o] (C3_LRELU: fused_leaky_relu's order with scale 1) or slope[o]
+  // (C3_PRELU: aten's prelu, weight * x on the negative side)
+  auto epilogue = [&](float v, float a) -> float {
+    if constexpr (EPI == C3_LRELU) {
+      const float t = __fadd_rn(v, a);
+      return t > 0.f ? t : t * alpha;
+    } else if constexpr (EPI == C3_PRELU) {
+      return v > 0.f ? v : a * v;
+    } else {
+      return v;
+    }
+  };
   const long long ost_o = p.out_nhwc ? 1 : (long long)p.oh * p.ow, ost_p = p.out_nhwc ? p.cout : 1;   // channel / position strides
   if (__syncthreads_or((xflag != xflag) | (wflag != 0u))) {
     // Inf / NaN among this block's operands: the tile again as fp32 products.  Thread = one position x 32 channels.
@@ -922,8 +1004,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_mfma_bf16x3(const S2Params p
         const long long slot0 = (long long)(i >> 4) * 54 * p.mp;
         const int hh = (i >> 3) & 1, j = i & 7;
         for (int t = 0; t < 9; ++t) {
-          const int y = 2 * oy + t / 3 - 1, x = 2 * ox + t % 3 - 1;
-          const float xin = (y >= 0 && y < p.h && x >= 0 && x < p.w) ? in_b[(long long)i * hw + y * p.w + x] : 0.f;
+          const int y = S * oy + t / 3 - 1, x = S * ox + t % 3 - 1;
+          const long long at = NHWC_IN ? (long long)(y * p.w + x) * p.cin + i : (long long)i * hw + y * p.w + x;
+          const float xin = (y >= 0 && y < p.h && x >= 0 && x < p.w) ? in_b[at] : 0.f;
           float wv = 0.f;
 #pragma unroll
           for (int pc = 0; pc < 3; ++pc)     // hi + mid + lo is the fp32 weight again, exactly
@@ -931,19 +1014,18 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_mfma_bf16x3(const S2Params p
           s = __builtin_fmaf(wv, xin, s);
         }
       }
-      const float v = __fadd_rn(s, p.bias ? p.bias[o] : 0.f);
-      out_b[o * ost_o + ((long long)oy * p.ow + ox) * ost_p] = v > 0.f ? v : v * alpha;
+      out_b[o * ost_o + ((long long)oy * p.ow + ox) * ost_p] = epilogue(s, (EPI != C3_NONE && p.aux) ? p.aux[o] : 0.f);
     }
     return;
   }
 
-  // ---- epilogue: bias, LeakyReLU (fused_leaky_relu's order with scale 1); NCHW: 32 lanes on 32 consecutive x; NHWC: a
-  // lane's four consecutive channels (r & 3) as one 16-byte store, the two k-halves and four row groups of a position
-  // filling 128 consecutive bytes
+  // ---- store through the epilogue; NCHW: 32 lanes on 32 consecutive x; NHWC: a lane's four consecutive channels
+  // (r & 3) as one 16-byte store, the two k-halves and four row groups of a position filling 128 consecutive bytes
   const int orow = o0 + wm * 32 + 4 * khalf;            // row r of the 32-row group adds (r&3) + 8*(r>>2)
-  float bias_r[16];
+  float aux_r[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) bias_r[r] = p.bias ? p.bias[min(orow + (r & 3) + 8 * (r >> 2), p.cout - 1)] : 0.f;
+  for (int r = 0; r < 16; ++r)
+    aux_r[r] = (EPI != C3_NONE && p.aux) ? p.aux[min(orow + (r & 3) + 8 * (r >> 2), p.cout - 1)] : 0.f;
 #pragma unroll
   for (int g = 0; g < RNP; ++g) {
     const int py_ = y0 + wn * RNP + g, px_ = x0 + l31;
@@ -951,10 +1033,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_mfma_bf16x3(const S2Params p
     float* dpos = out_b + ((long long)py_ * p.ow + px_) * ost_p;
     float v[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float t = __fadd_rn(acc[g][r], bias_r[r]);
-      v[r] = t > 0.f ? t : t * alpha;
-    }
+    for (int r = 0; r < 16; ++r) v[r] = epilogue(acc[g][r], aux_r[r]);
     if (p.out_nhwc && (p.cout & 3) == 0) {               // o and cout are multiples of 4: a quad is inside or outside
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -974,24 +1053,43 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_mfma_bf16x3(const S2Params p
   }
 }
 
-int conv3x3s2_bf16x3(const float* in, const void* wt, const float* bias, float* out, int batch, int cin, int cout, int h,
-                     int w, float alpha, int out_nhwc, hipStream_t s) {
-  if (batch < 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || (out_nhwc != 0 && out_nhwc != 1)) return FMGAN_EINVAL;
-  if (batch == 0) return FMGAN_OK;
-  S2Params p{};
-  p.in = in; p.wt = (const unsigned short*)wt; p.bias = bias; p.out = out;
-  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w; p.alpha = alpha; p.out_nhwc = out_nhwc;
-  if (!s2_plan(p)) return FMGAN_EUNSUPPORTED;
-  if (!in || !wt || !out) return FMGAN_EINVAL;
-  if (out_nhwc && (cout & 3) == 0 && ((uintptr_t)out & 15)) return FMGAN_EINVAL;       // the 16-byte stores
-  static bool attr = false;     // > 48 KB of dynamic LDS needs the opt-in once (idempotent)
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv3x3s2_mfma_bf16x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2Tile::LDS);
+template <int S, bool NHWC_IN, int EPI>
+int c3_launch(const C3Params& p, hipStream_t s) {
+  using Tile = C3Tile<S>;
+  void (*kernel)(const C3Params) = conv3x3_mfma_bf16x3<S, NHWC_IN, EPI>;
+  static bool attr = false;     // > 48 KB of dynamic LDS needs the opt-in once per instantiation (idempotent)
+  if (Tile::LDS > 48 * 1024 && !attr) {
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Tile::LDS);
     attr = true;
   }
   const long long blocks = (long long)p.o_tiles * p.tiles_x * p.tiles_y * p.batch;
-  hipLaunchKernelGGL(conv3x3s2_mfma_bf16x3, dim3((unsigned)blocks), dim3(256), S2Tile::LDS, s, p);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), Tile::LDS, s, p);
   return fmgan_check_launch();
+}
+
+template <int S, bool NHWC_IN>
+int c3_launch_epi(const C3Params& p, hipStream_t s) {
+  if (p.epi == C3_LRELU) return c3_launch<S, NHWC_IN, C3_LRELU>(p, s);
+  if (p.epi == C3_PRELU) return c3_launch<S, NHWC_IN, C3_PRELU>(p, s);
+  return c3_launch<S, NHWC_IN, C3_NONE>(p, s);
+}
+
+// The host side of fmgan_conv3x3_bf16x3_f32 and of fmgan_conv3x3s2_bf16x3_f32 (stride 2, NCHW in, bias + LeakyReLU).
+int conv3x3_bf16x3(const float* in, const void* wt, const float* aux, float* out, int batch, int cin, int cout, int h, int w,
+                   int stride, int in_nhwc, int out_nhwc, int epi, float alpha, hipStream_t s) {
+  if (batch < 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || (stride != 1 && stride != 2)) return FMGAN_EINVAL;
+  if ((in_nhwc != 0 && in_nhwc != 1) || (out_nhwc != 0 && out_nhwc != 1) || epi < C3_NONE || epi > C3_PRELU) return FMGAN_EINVAL;
+  if (batch == 0) return FMGAN_OK;
+  C3Params p{};
+  p.in = in; p.wt = (const unsigned short*)wt; p.aux = aux; p.out = out;
+  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w; p.alpha = alpha;
+  p.stride = stride; p.epi = epi; p.in_nhwc = in_nhwc; p.out_nhwc = out_nhwc;
+  if (!c3_plan(p)) return FMGAN_EUNSUPPORTED;
+  if (!in || !wt || !out || (epi == C3_PRELU && !aux)) return FMGAN_EINVAL;
+  if (in_nhwc && ((uintptr_t)in & 15)) return FMGAN_EINVAL;                            // the 16-byte loads
+  if (out_nhwc && (cout & 3) == 0 && ((uintptr_t)out & 15)) return FMGAN_EINVAL;       // the 16-byte stores
+  if (stride == 1) return in_nhwc ? c3_launch_epi<1, true>(p, s) : c3_launch_epi<1, false>(p, s);
+  return in_nhwc ? c3_launch_epi<2, true>(p, s) : c3_launch_epi<2, false>(p, s);
 }
 
 // One launch for every tile of both contractions: the block grid, the LDS opt-in and the kernel, all from the tile.
@@ -1123,12 +1221,24 @@ extern "C" int fmgan_modconv2d_bf16x3(const float* in, const void* wt_split, con
 
 // ---- pSp style heads: plain 3x3 / stride 2 / pad 1 conv + bias + LeakyReLU on the split-operand contraction
 extern "C" int fmgan_conv3x3s2_bf16x3_supported(int batch, int cin, int cout, int h, int w) {
-  S2Params p{};
-  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
-  return s2_plan(p) ? 1 : 0;
+  return fmgan_conv3x3_bf16x3_supported(batch, cin, cout, h, w, 2, 0);
 }
 
 extern "C" int fmgan_conv3x3s2_bf16x3_f32(const float* in, const void* wt_split, const float* bias, float* out, int batch,
                                           int cin, int cout, int h, int w, float alpha, int out_nhwc, void* stream) {
-  return conv3x3s2_bf16x3(in, wt_split, bias, out, batch, cin, cout, h, w, alpha, out_nhwc, (hipStream_t)stream);
+  return conv3x3_bf16x3(in, wt_split, bias, out, batch, cin, cout, h, w, 2, 0, out_nhwc, C3_LRELU, alpha, (hipStream_t)stream);
+}
+
+// ---- the family: stride 1 or 2, NCHW or channels_last on either side, one of three epilogues (pSp encoder body)
+extern "C" int fmgan_conv3x3_bf16x3_supported(int batch, int cin, int cout, int h, int w, int stride, int in_nhwc) {
+  C3Params p{};
+  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w; p.stride = stride; p.in_nhwc = in_nhwc;
+  return c3_plan(p) ? 1 : 0;
+}
+
+extern "C" int fmgan_conv3x3_bf16x3_f32(const float* in, const void* wt_split, const float* aux, float* out, int batch,
+                                        int cin, int cout, int h, int w, int stride, int in_nhwc, int out_nhwc,
+                                        int epilogue, float alpha, void* stream) {
+  return conv3x3_bf16x3(in, wt_split, aux, out, batch, cin, cout, h, w, stride, in_nhwc, out_nhwc, epilogue, alpha,
+                        (hipStream_t)stream);
 }

@@ -4,7 +4,7 @@ import ctypes
 
 import torch
 
-from .core import ambient, check, fp, launching, lib, _noise_args, on_device, ptr, require_gpu, served
+from .core import ambient, check, fp, launching, lib, nhwc_dense, _noise_args, on_device, ptr, require_gpu, served
 
 
 # ----------------------------------------------------------------------------- csrc/modconv_prep.hip
@@ -206,19 +206,65 @@ def conv3x3s2_bf16x3_supported(batch, cin, cout, h, w):
 
 def conv3x3s2_bf16x3(x, wts, bias, cout, alpha=0.01, channels_last=False):
     """LeakyReLU(conv3x3(x, stride 2, pad 1) + bias) with fp32 operands split into three bf16 pieces (fp32 accumulation).
-    x [B,cin,H,W] f32 NCHW-contiguous, wts = conv_weight_to_bf16x3(weight), bias [cout] or None.  Returns
+    x [B,cin,H,W] f32 NCHW-contiguous or dense channels_last storage (read as it is, same bits), wts =
+    conv_weight_to_bf16x3(weight), bias [cout] or None.  Returns
     [B,cout,(H-1)//2+1,(W-1)//2+1] — NCHW-contiguous, or in channels_last storage (written so by the kernel: what the
     MIOpen tail of a style head reads) — or None where the library declines the shape."""
     require_gpu(x, 'input')
-    if not x.is_contiguous():
-        raise RuntimeError(f'conv3x3s2_bf16x3: input must be NCHW-contiguous, got strides {x.stride()}')
+    in_nhwc = _c3_input_layout('conv3x3s2_bf16x3', x)
     b, cin, h, w = x.shape
     out = torch.empty((b, cout, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device,
                       memory_format=torch.channels_last if channels_last else torch.contiguous_format)
     with launching(x, 'conv3x3s2_bf16x3', (b, cin, cout, h, w)) as stream:
-        st = lib().fmgan_conv3x3s2_bf16x3_f32(fp(x), ptr(wts), fp(bias), fp(out), b, cin, cout, h, w, float(alpha),
-                                              int(bool(channels_last)), stream)
+        if in_nhwc:     # the same kernel reading channels_last storage (same bits), through the family's entry point
+            st = lib().fmgan_conv3x3_bf16x3_f32(fp(x), ptr(wts), fp(bias), fp(out), b, cin, cout, h, w, 2, 1,
+                                                int(bool(channels_last)), C3_EPILOGUES['lrelu'], float(alpha), stream)
+        else:
+            st = lib().fmgan_conv3x3s2_bf16x3_f32(fp(x), ptr(wts), fp(bias), fp(out), b, cin, cout, h, w, float(alpha),
+                                                  int(bool(channels_last)), stream)
     return out if served(st, 'conv3x3s2_bf16x3') else None
+
+
+C3_EPILOGUES = {None: 0, 'lrelu': 1, 'prelu': 2}        # include/fmgan_hip.h, fmgan_conv3x3_bf16x3_f32
+
+
+def _c3_input_layout(what, x):
+    """0 for an NCHW-contiguous input, 1 for dense channels_last storage (a tensor that is both, C = 1 or H = W = 1,
+    counts as NCHW: the two layouts then coincide); anything else is refused."""
+    if x.is_contiguous():
+        return 0
+    if nhwc_dense(x):
+        return 1
+    raise RuntimeError(f'{what}: input must be NCHW-contiguous or dense channels_last, got strides {x.stride()}')
+
+
+def conv3x3_bf16x3_supported(batch, cin, cout, h, w, stride=1, channels_last_in=False):
+    return bool(lib().fmgan_conv3x3_bf16x3_supported(int(batch), int(cin), int(cout), int(h), int(w), int(stride),
+                                                     int(bool(channels_last_in))))
+
+
+def conv3x3_bf16x3(x, wts, cout, stride=1, epilogue=None, aux=None, alpha=0.01, channels_last=False):
+    """conv3x3(x, stride 1 or 2, pad 1) through one epilogue, fp32 operands split into three bf16 pieces (fp32
+    accumulation): epilogue None: the plain convolution; 'lrelu': LeakyReLU(conv + aux) with aux = bias [cout] or None;
+    'prelu': conv > 0 ? conv : aux * conv with aux = the PReLU slope [cout].  x [B,cin,H,W] f32, NCHW-contiguous or dense
+    channels_last storage (read as it is); wts = conv_weight_to_bf16x3(weight).  Returns [B,cout,(H-1)//stride+1,
+    (W-1)//stride+1], NCHW-contiguous or (channels_last=True) written in channels_last storage, or None where the library
+    declines the shape.  Launch bracket 'conv3x3_bf16x3' with info (b, cin, cout, h, w, stride, epilogue code)."""
+    require_gpu(x, 'input')
+    in_nhwc = _c3_input_layout('conv3x3_bf16x3', x)
+    epi = C3_EPILOGUES[epilogue]
+    if epilogue == 'prelu' and (aux is None or aux.numel() != cout):
+        raise RuntimeError('conv3x3_bf16x3: the prelu epilogue needs one slope per output channel')
+    if aux is not None:
+        aux = aux.contiguous()
+    stride = int(stride)
+    b, cin, h, w = x.shape
+    out = torch.empty((b, cout, (h - 1) // max(stride, 1) + 1, (w - 1) // max(stride, 1) + 1), dtype=torch.float32,
+                      device=x.device, memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    with launching(x, 'conv3x3_bf16x3', (b, cin, cout, h, w, stride, epi)) as stream:
+        st = lib().fmgan_conv3x3_bf16x3_f32(fp(x), ptr(wts), fp(aux), fp(out), b, cin, cout, h, w, stride, in_nhwc,
+                                            int(bool(channels_last)), epi, float(alpha), stream)
+    return out if served(st, 'conv3x3_bf16x3') else None
 
 
 # ----------------------------------------------------------------------------- csrc/modconv_wgrad.hip

@@ -1,4 +1,12 @@
-"""IR / IR-SE building blocks of the pSp W+ encoder (reference: psp_encoder_model/encoders/helpers.py)."""
+"""IR / IR-SE building blocks of the pSp W+ encoder (reference: psp_encoder_model/encoders/helpers.py).
+
+Inference on the GPU (fused_body / fused_units): BN / SE / shortcut / add of the units run on the glue kernels of
+csrc/encoder_glue.hip, and the units' 3x3 convolutions whose output is at least BODY_X3_MIN_OUT = 32 wide run on the
+split-operand kernel family of csrc/modconv_bf16.hip (three bf16 pieces per fp32 operand, fp32 accumulation) instead of
+MIOpen's fp32 implicit GEMM: conv1 with the unit's PReLU in its epilogue, conv2 (stride 1 or 2) with a plain store,
+channels_last in and out.  At a 256^2 photo these are both convolutions of units 0-5 and conv1 of unit 6; the 16^2 ones
+keep MIOpen + aten PReLU.  The rule is body_x3_serves, the switch BODY_X3 / FMGAN_PSP_BODY_X3=0
+(profiles/psp_body_x3.md)."""
 import os
 from collections import namedtuple
 
@@ -141,6 +149,15 @@ class bottleneck_IR_SE(Module):
 # evaluated in-kernel from the module's live vectors on every launch; modules, state_dict names and the training path
 # are untouched.  FMGAN_NO_ENCODER_FUSE=1 (or ENCODER_FUSE = False) keeps the module path.
 ENCODER_FUSE = os.environ.get('FMGAN_NO_ENCODER_FUSE', '0') != '1'
+# On that path the units' 3x3 convolutions themselves run on the split-operand contraction of csrc/modconv_bf16.hip
+# (conv3x3_mfma_bf16x3: three bf16 pieces per fp32 operand, fp32 accumulation, fixed summation order) reading and writing
+# channels_last storage: conv1 with the PReLU in its epilogue (the aten PReLU pass goes), conv2 (stride 1 or 2) with a
+# plain store.  Which layers: body_x3_serves — every 3x3 convolution whose OUTPUT is at least BODY_X3_MIN_OUT wide (the
+# kernel's position tile is 32 columns; profiles/psp_body_x3.md has the per-shape measurement against MIOpen): at a
+# 256^2 photo units 0-5 and conv1 of unit 6, thirteen of the sixteen; the 16^2 ones stay on MIOpen's fp32 implicit GEMM
+# followed by aten PReLU, exactly as before.  FMGAN_PSP_BODY_X3=0 (or BODY_X3 = False) gives MIOpen back everywhere.
+BODY_X3 = os.environ.get('FMGAN_PSP_BODY_X3', '1') == '1'
+BODY_X3_MIN_OUT = 32
 
 
 class _NotServed(Exception):
@@ -186,12 +203,50 @@ def _input_fusable(x):
             and x.dtype == torch.float32 and x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous())
 
 
+def body_x3_serves(conv, x):
+    """Does this 3x3 convolution of a unit run on _native.conv3x3_bf16x3 for the channels_last activation x?  The per-shape
+    rule of the body, in one place: the switch, a plain 3x3 / pad 1 / stride 1 or 2 convolution without bias, an output
+    at least BODY_X3_MIN_OUT wide, and the library's own query."""
+    from op import _native
+    if not (BODY_X3 and isinstance(conv, Conv2d) and conv.kernel_size == (3, 3) and conv.padding == (1, 1)
+            and conv.stride in ((1, 1), (2, 2)) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
+            and conv.weight.dtype == torch.float32 and _native.nhwc_dense(x) and x.shape[1] == conv.in_channels):
+        return False
+    stride = conv.stride[0]
+    if (x.shape[3] - 1) // stride + 1 < BODY_X3_MIN_OUT:
+        return False
+    return _native.conv3x3_bf16x3_supported(x.shape[0], conv.in_channels, conv.out_channels, x.shape[2], x.shape[3],
+                                            stride, True)
+
+
+def _unit_convs(res, xn):
+    """conv1 -> PReLU -> conv2 of a unit on xn = BN_in(x): each convolution on the split-operand kernel where
+    body_x3_serves says so (conv1 with the PReLU in its epilogue), on MIOpen (+ aten PReLU) otherwise."""
+    from op import _native
+    from op.live_weights import split_conv_weight
+    conv1, act, conv2 = res[1], res[2], res[3]
+    if body_x3_serves(conv1, xn):
+        r = _native.conv3x3_bf16x3(xn, split_conv_weight(conv1), conv1.out_channels, conv1.stride[0], 'prelu', act.weight,
+                                   channels_last=True)
+        if r is None:
+            raise RuntimeError('conv3x3_bf16x3 declined a shape its query accepted')
+    else:
+        r = act(conv1(xn))
+    if body_x3_serves(conv2, r):
+        r2 = _native.conv3x3_bf16x3(r, split_conv_weight(conv2), conv2.out_channels, conv2.stride[0], None,
+                                    channels_last=True)
+        if r2 is None:
+            raise RuntimeError('conv3x3_bf16x3 declined a shape its query accepted')
+        return r2
+    return conv2(r)
+
+
 def _fused_unit(unit, x, xn, bn_next, sub=None):
     """One unit on the glue kernels.  x: the unit's input, xn = BN_in(x), sub: x already subsampled by the unit's
     MaxPool2d(1, stride) shortcut (x may then be None).  Returns (out, bn_next(out) or None)."""
     from op import _native
     res, sc = unit.res_layer, unit.shortcut_layer
-    r = res[3](res[2](res[1](xn)))
+    r = _unit_convs(res, xn)
     gate = None
     if len(res) == 6:
         se = res[5]

@@ -6,6 +6,11 @@ names as the reference.  On the GPU the encoder runs in channels_last (NHWC) mem
 kernels are NHWC-native, so this removes ~260 layout-transpose launches per forward and makes the FPN's bilinear
 resize 13x faster (measured on MI355X: 14.9 -> 10.7 ms at B=8, 51.3 -> 32.0 ms at B=32; identical values).  The two Backbone* encoders of the reference file are not on the 3-encoder path and are
 not provided.
+
+Not every convolution of the default inference path is MIOpen's: the body's 3x3 convolutions with an output at least 32
+wide (helpers.body_x3_serves; switch helpers.BODY_X3 / FMGAN_PSP_BODY_X3=0) and the fine heads' first convolution
+(HEADS_X3 / FMGAN_PSP_HEADS_X3=0, reading the level's channels_last feature map as it is) run on the split-operand bf16
+contraction with fp32 accumulation of csrc/modconv_bf16.hip (profiles/psp_body_x3.md, profiles/psp_heads_x3.md).
 """
 import math
 import os
@@ -53,6 +58,10 @@ X3_MIN_OUT = 32
 # True: the kernel writes its output in channels_last storage, what the MIOpen tail reads (False: NCHW, which aten then
 # converts per head — 32 us each at B=8, profiles/psp_heads_x3.md)
 X3_TAIL_CHANNELS_LAST = True
+# True: the kernel READS the level's channels_last feature map as it is (its channels_last-input instantiation: four
+# 16-byte loads per 16-channel slot, same bits); False: an NCHW copy of the map is made once per level for its heads
+# (66 us for p1 at B=8).  profiles/psp_body_x3.md has the stand-alone comparison that decided it.
+X3_HEAD_CHANNELS_LAST_IN = True
 
 _TAPS = {18: (3, 5, 7), 50: (6, 20, 23)}   # units whose outputs feed the pyramid (psp_encoders.py:105-108)
 
@@ -80,10 +89,16 @@ class GradualStyleBlock(Module):
             return False
         return _native.conv3x3s2_bf16x3_supported(x.shape[0], conv.in_channels, conv.out_channels, x.shape[2], x.shape[3])
 
-    def _first_x3(self, x_nchw):
-        """convs[0] + LeakyReLU on the split-operand kernel; the weight image is kept per parameter (live_weights)."""
+    @staticmethod
+    def x3_reads(x):
+        """Can the kernel read the feature map x as it is (dense channels_last storage, whole channel quads)?"""
+        return X3_HEAD_CHANNELS_LAST_IN and _native.nhwc_dense(x) and x.shape[1] % 4 == 0
+
+    def _first_x3(self, x):
+        """convs[0] + LeakyReLU on the split-operand kernel (x: NCHW-contiguous or dense channels_last); the weight image
+        is kept per parameter (live_weights)."""
         conv, act = self.convs[0], self.convs[1]
-        y = _native.conv3x3s2_bf16x3(x_nchw, split_conv_weight(conv), conv.bias, conv.out_channels, act.negative_slope,
+        y = _native.conv3x3s2_bf16x3(x, split_conv_weight(conv), conv.bias, conv.out_channels, act.negative_slope,
                                      channels_last=X3_TAIL_CHANNELS_LAST)
         if y is None:
             raise RuntimeError('conv3x3s2_bf16x3 declined a shape its query accepted')
@@ -94,7 +109,9 @@ class GradualStyleBlock(Module):
         if x.is_cuda and x.dtype == torch.float32:
             convs = list(zip(self.convs[0::2], self.convs[1::2]))
             if self.x3_serves(x):
-                x = self._first_x3(x.contiguous() if x_nchw is None else x_nchw)
+                if x_nchw is None:
+                    x_nchw = x if self.x3_reads(x) else x.contiguous()
+                x = self._first_x3(x_nchw)
                 convs = convs[1:]
             # conv, then bias + LeakyReLU(0.01) in ONE pass of the HIP fused_bias_act kernel (the same arithmetic as
             # MIOpen's separate bias add followed by aten leaky_relu: (v + b) > 0 ? . : 0.01 * .  — bit-identical).
@@ -274,9 +291,11 @@ class GradualStyleEncoder(Module):
                 return (lambda: None), self.styles[j](feat, nchw)
 
         def level(js, feat):
-            # the level's feature map NHWC -> NCHW ONCE for all its heads that take the split-operand first conv
+            # the split-operand first conv reads the level's channels_last feature map as it is; where it cannot, the map
+            # goes NHWC -> NCHW ONCE for all the level's heads that take it
             js = list(js)
-            nchw = feat.contiguous() if any(self.styles[j].x3_serves(feat) for j in js) else None
+            copy = not GradualStyleBlock.x3_reads(feat) and any(self.styles[j].x3_serves(feat) for j in js)
+            nchw = feat.contiguous() if copy else None
             return [head(j, feat, nchw) for j in js]
         latents = level(range(min(self.coarse_ind, self.style_count)), c3)
         p2 = self._upsample_add(c3, self.latlayer1(c2))

@@ -674,6 +674,24 @@ int fmgan_conv3x3s2_bf16x3_f32(const float *in, const void *wt_split, const floa
                                int batch, int cin, int cout, int h, int w, float alpha, int out_nhwc, void *stream);
 
 /*
+ * The same kernel as a family (the pSp encoder body's 3x3 convolutions, helpers.py _fused_unit): a plain 3x3 convolution
+ * with zero padding 1 and
+ *   stride   1 or 2 (out [batch,cout,(h-1)/stride+1,(w-1)/stride+1]); anything else is FMGAN_EINVAL;
+ *   in_nhwc  0: in[b][i][y][x]; 1: in[b][y][x][i] (channels_last storage, 16-byte aligned; needs cin % 4 == 0 — other
+ *            widths are declined: the query says 0 and the launch returns FMGAN_EUNSUPPORTED);
+ *   out_nhwc as above;
+ *   epilogue 0: out = conv;  1: out = lrelu(conv + aux[o]) with lrelu(v) = v > 0 ? v : alpha*v (aux = bias, may be NULL);
+ *            2: out = conv > 0 ? conv : aux[o]*conv (aux = the per-channel PReLU slope, required; aten's prelu
+ *            arithmetic, no bias).  alpha is read by epilogue 1 only.
+ * fmgan_conv3x3s2_bf16x3_f32 is (stride 2, in_nhwc 0, epilogue 1) of it; same summation order in every member, so the
+ * channels_last-input result has the bits of the NCHW-input one.  wt_split, special values and refusals as above.
+ */
+int fmgan_conv3x3_bf16x3_supported(int batch, int cin, int cout, int h, int w, int stride, int in_nhwc);
+int fmgan_conv3x3_bf16x3_f32(const float *in, const void *wt_split, const float *aux, float *out,
+                             int batch, int cin, int cout, int h, int w, int stride, int in_nhwc, int out_nhwc,
+                             int epilogue, float alpha, void *stream);
+
+/*
  * Plain (mode 0) modulated conv with the FOLLOWING ToRGB layer folded into its epilogue.  In the reference these are
  * two modules and three HBM passes over the activation (StyledConv conv2 -> ToRGB, stylegan2.py:646-651 calling
  * :360-376 and :393-404).  When one block holds every output channel of its pixels (cout <= the tile's channel

@@ -300,6 +300,12 @@ def convolutions(d):
     img = _native.conv_weight_to_bf16x3(t('x3/w', (cout, cin, 3, 3), d))
     assert _native.conv3x3s2_bf16x3(x, img, bias, cout, 0.01) is not None
     assert _native.conv3x3s2_bf16x3(x, img, bias, cout, 0.01, channels_last=True) is not None
+    section('conv3x3_bf16x3')
+    xcl = x.contiguous(memory_format=torch.channels_last)
+    host('conv3x3_bf16x3_supported', b, cin, cout, h, w, 1, True)
+    assert _native.conv3x3_bf16x3(xcl, img, cout, 1, 'prelu', bias, channels_last=True) is not None
+    assert _native.conv3x3_bf16x3(xcl, img, cout, 2, None, channels_last=True) is not None
+    assert _native.conv3x3_bf16x3(x, img, cout, 2, 'lrelu', bias, 0.01) is not None
     section('torgb_backward')
     b, cin, hw = 2, 8, 4
     _native.torgb_backward(t('rgb/x', (b, cin, hw, hw), d), t('rgb/go', (b, 3, hw, hw), d), t('rgb/w', (1, 3, cin, 1, 1), d),
