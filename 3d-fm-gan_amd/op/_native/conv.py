@@ -1,5 +1,5 @@
 """The modulated convolution and what feeds it: csrc/modconv_prep.hip, modconv_fwd.hip, modconv_bf16.hip,
-modconv_wgrad.hip, winograd.hip, torgb.hip, linear.hip, style_bank.hip."""
+conv3x3_x3.hip, modconv_wgrad.hip, winograd.hip, torgb.hip, linear.hip, style_bank.hip."""
 import ctypes
 
 import torch
@@ -200,6 +200,7 @@ def conv_weight_to_bf16x3(weight):
         return modconv_weight_to_bf16x3(wt)
 
 
+# ----------------------------------------------------------------------------- csrc/conv3x3_x3.hip
 def conv3x3s2_bf16x3_supported(batch, cin, cout, h, w):
     return bool(lib().fmgan_conv3x3s2_bf16x3_supported(int(batch), int(cin), int(cout), int(h), int(w)))
 

@@ -107,6 +107,7 @@ def lib():
     _sig(L.fmgan_modconv_weight_to_bf16x3, [vp, vp, i, i, i, vp])
     _sig(L.fmgan_modconv2d_bf16x3_supported, [i] * 6)
     _sig(L.fmgan_modconv2d_bf16x3, [vp] * 5 + [i] * 6 + [vp] * 3 + [i, i, f, f, ll, i, vp])
+    # csrc/conv3x3_x3.hip
     _sig(L.fmgan_conv3x3s2_bf16x3_supported, [i] * 5)
     _sig(L.fmgan_conv3x3s2_bf16x3_f32, [vp] * 4 + [i] * 5 + [f, i, vp])
     _sig(L.fmgan_conv3x3_bf16x3_supported, [i] * 7)

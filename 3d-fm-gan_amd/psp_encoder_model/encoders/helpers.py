@@ -2,7 +2,7 @@
 
 Inference on the GPU (fused_body / fused_units): BN / SE / shortcut / add of the units run on the glue kernels of
 csrc/encoder_glue.hip, and the units' 3x3 convolutions whose output is at least BODY_X3_MIN_OUT = 32 wide run on the
-split-operand kernel family of csrc/modconv_bf16.hip (three bf16 pieces per fp32 operand, fp32 accumulation) instead of
+split-operand kernel family of csrc/conv3x3_x3.hip (three bf16 pieces per fp32 operand, fp32 accumulation) instead of
 MIOpen's fp32 implicit GEMM: conv1 with the unit's PReLU in its epilogue, conv2 (stride 1 or 2) with a plain store,
 channels_last in and out.  At a 256^2 photo these are both convolutions of units 0-5 and conv1 of unit 6; the 16^2 ones
 keep MIOpen + aten PReLU.  The rule is body_x3_serves, the switch BODY_X3 / FMGAN_PSP_BODY_X3=0
@@ -149,7 +149,7 @@ class bottleneck_IR_SE(Module):
 # evaluated in-kernel from the module's live vectors on every launch; modules, state_dict names and the training path
 # are untouched.  FMGAN_NO_ENCODER_FUSE=1 (or ENCODER_FUSE = False) keeps the module path.
 ENCODER_FUSE = os.environ.get('FMGAN_NO_ENCODER_FUSE', '0') != '1'
-# On that path the units' 3x3 convolutions themselves run on the split-operand contraction of csrc/modconv_bf16.hip
+# On that path the units' 3x3 convolutions themselves run on the split-operand contraction of csrc/conv3x3_x3.hip
 # (conv3x3_mfma_bf16x3: three bf16 pieces per fp32 operand, fp32 accumulation, fixed summation order) reading and writing
 # channels_last storage: conv1 with the PReLU in its epilogue (the aten PReLU pass goes), conv2 (stride 1 or 2) with a
 # plain store.  Which layers: body_x3_serves — every 3x3 convolution whose OUTPUT is at least BODY_X3_MIN_OUT wide (the

@@ -10,7 +10,7 @@ not provided.
 Not every convolution of the default inference path is MIOpen's: the body's 3x3 convolutions with an output at least 32
 wide (helpers.body_x3_serves; switch helpers.BODY_X3 / FMGAN_PSP_BODY_X3=0) and the fine heads' first convolution
 (HEADS_X3 / FMGAN_PSP_HEADS_X3=0, reading the level's channels_last feature map as it is) run on the split-operand bf16
-contraction with fp32 accumulation of csrc/modconv_bf16.hip (profiles/psp_body_x3.md, profiles/psp_heads_x3.md).
+contraction with fp32 accumulation of csrc/conv3x3_x3.hip (profiles/psp_body_x3.md, profiles/psp_heads_x3.md).
 """
 import math
 import os
@@ -49,7 +49,7 @@ GROUP_HEADS = os.environ.get('FMGAN_PSP_GROUPED', '0') == '1'
 
 # Inference: the FIRST convolution of a style head (3x3, stride 2, pad 1, 512 -> 512 on the level's shared feature map:
 # 425 of the heads' 627 GFLOP per step at B=8 are the eleven 64^2 -> 32^2 ones) runs on the split-operand contraction of
-# csrc/modconv_bf16.hip — each fp32 operand as three bf16 pieces, six v_mfma_f32_32x32x16_bf16 per product, fp32
+# csrc/conv3x3_x3.hip — each fp32 operand as three bf16 pieces, six v_mfma_f32_32x32x16_bf16 per product, fp32
 # accumulation, fixed summation order — with bias + LeakyReLU in its epilogue, instead of MIOpen's fp32 implicit GEMM
 # (+ fused_bias_act).  FMGAN_PSP_HEADS_X3=0 keeps MIOpen.  It serves the levels whose OUTPUT is at least
 # X3_MIN_OUT wide (profiles/psp_heads_x3.md: a 16-wide output fills half of the kernel's 32-column tile).

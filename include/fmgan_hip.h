@@ -658,7 +658,8 @@ int fmgan_modconv2d_bf16x3(const float *in, const void *wt_split, const float *s
                            long long out_plane_stride, int out_row_stride, void *stream);
 
 /*
- * The first convolution of a pSp style head (psp_encoders.py GradualStyleBlock) on the same split-operand contraction:
+ * The first convolution of a pSp style head (psp_encoders.py GradualStyleBlock) on the same split-operand contraction
+ * (csrc/conv3x3_x3.hip; the modulated entries above are csrc/modconv_bf16.hip):
  *     out[b,o,y,x] = lrelu(bias[o] + sum_{i,ky,kx} W[o,i,ky,kx] * in[b,i,2y+ky-1,2x+kx-1]),  lrelu(v) = v > 0 ? v : alpha*v
  * a plain 3x3 convolution with stride 2 and zero padding 1, NCHW fp32 in and out ([batch,cout,(h-1)/2+1,(w-1)/2+1]), no
  * style and no demodulation; bias may be NULL.  out_nhwc = 1 writes the same values as out[b][y][x][o] (channels_last
@@ -674,7 +675,7 @@ int fmgan_conv3x3s2_bf16x3_f32(const float *in, const void *wt_split, const floa
                                int batch, int cin, int cout, int h, int w, float alpha, int out_nhwc, void *stream);
 
 /*
- * The same kernel as a family (the pSp encoder body's 3x3 convolutions, helpers.py _fused_unit): a plain 3x3 convolution
+ * The same kernel as a family (csrc/conv3x3_x3.hip; the pSp encoder body's 3x3 convolutions, helpers.py _fused_unit): a plain 3x3 convolution
  * with zero padding 1 and
  *   stride   1 or 2 (out [batch,cout,(h-1)/stride+1,(w-1)/stride+1]); anything else is FMGAN_EINVAL;
  *   in_nhwc  0: in[b][i][y][x]; 1: in[b][y][x][i] (channels_last storage, 16-byte aligned; needs cin % 4 == 0 — other

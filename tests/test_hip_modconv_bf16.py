@@ -56,12 +56,18 @@ def test_bf16_kernel_matches_its_definition(cfg, demod):
     assert torch.equal(_native.modconv2d(xd, wt, sd, dm, mode), y32)        # and it is off again outside
 
 
-def test_bf16_fused_epilogue_and_strided_output():
+@pytest.mark.parametrize('precision', ['bf16', 'bf16x3'])
+@pytest.mark.parametrize('shape', [(2, 32, 64, 40, 64), (1, 16, 96, 9, 33)])
+def test_bf16_fused_epilogue_and_strided_output(precision, shape):
     """Plain conv with noise + bias + lrelu in the epilogue, and the transposed conv writing the aligned-row intermediate:
-    same values as the separate steps on the bf16 result."""
+    same values as the separate steps on the result of the same precision.  The second shape has a ragged last channel
+    tile on the bf16 kernel's 64-channel tile in mode 0 (the predicated stores, with the activation) and a 10 x 34 quad
+    grid in mode 1 (tiles stored through the buffer resource and ragged ones in both directions, in one launch)."""
     from op import _native
-    cfg = (2, 32, 64, 40, 64, 0)
+    cfg = shape + (0,)
     b, cin, cout, h, w, _ = cfg
+    supported = getattr(_native.lib(), f'fmgan_modconv2d_{precision}_supported')
+    assert supported(b, cin, cout, h, w, 0) == 1 and supported(b, cin, cout, h, w, 1) == 1
     x, wgt, s, scale = _inputs(cfg)
     d = dev()
     xd, wd, sd = x.to(d), wgt.to(d), s.to(d)
@@ -70,14 +76,14 @@ def test_bf16_fused_epilogue_and_strided_output():
     nz = synth.tensor('bf/ep/n', (b, 1, h, w)).to(d)
     nw = torch.tensor([0.41], device=d)
     bias = synth.tensor('bf/ep/b', (cout,)).to(d)
-    plain = _native.modconv2d(xd, wt, sd, dm, 0, precision='bf16')
-    fused = _native.modconv2d(xd, wt, sd, dm, 0, noise=nz, noise_weight=nw, bias=bias, fuse_act=True, precision='bf16')
+    plain = _native.modconv2d(xd, wt, sd, dm, 0, precision=precision)
+    fused = _native.modconv2d(xd, wt, sd, dm, 0, noise=nz, noise_weight=nw, bias=bias, fuse_act=True, precision=precision)
     assert torch.equal(fused, _native.noise_bias_act(plain, nz, nw, bias, 0.2, 2 ** 0.5))
-    up = _native.modconv2d(xd, wt, sd, dm, 1, precision='bf16')
+    up = _native.modconv2d(xd, wt, sd, dm, 1, precision=precision)
     oh, ow = 2 * h + 1, 2 * w + 1
     buf, p0, ps, rs = _native.aligned_rows_buffer(b, cout, oh, ow, 1, d)
     buf.fill_(float('nan'))
-    _native.modconv2d(xd, wt, sd, dm, 1, strided_out=(p0, ps, rs), precision='bf16')
+    _native.modconv2d(xd, wt, sd, dm, 1, strided_out=(p0, ps, rs), precision=precision)
     assert torch.equal(buf[:, :, 1:1 + ow].reshape(b, cout, oh, ow), up)
     assert torch.isnan(buf[:, :, 0]).all() and torch.isnan(buf[:, :, 1 + ow:]).all()
 

@@ -1,4 +1,4 @@
-"""The pSp encoder body's 3x3 convolutions on the split-operand kernel family (csrc/modconv_bf16.hip:
+"""The pSp encoder body's 3x3 convolutions on the split-operand kernel family (csrc/conv3x3_x3.hip:
 conv3x3_mfma_bf16x3<stride, channels_last input, epilogue>; op/_native/conv.py: conv3x3_bf16x3; helpers.py:
 body_x3_serves / _unit_convs with BODY_X3; psp_encoders.py: the heads' first convolution reading channels_last).
 

@@ -1,4 +1,4 @@
-"""The pSp style heads' first convolution on the split-operand kernel (csrc/modconv_bf16.hip: conv3x3s2_mfma_bf16x3;
+"""The pSp style heads' first convolution on the split-operand kernel (csrc/conv3x3_x3.hip: conv3x3_mfma_bf16x3<2, NCHW in, LeakyReLU>;
 op/_native/conv.py: conv3x3s2_bf16x3, conv_weight_to_bf16x3; op/live_weights.py: split_conv_weight; psp_encoders.py:
 GradualStyleBlock with HEADS_X3).
 

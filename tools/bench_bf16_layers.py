@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-layer time of the modulated conv, fp32 kernel vs bf16-operand kernel (GPU box):  python tools/bench_bf16_layers.py [B]
+"""Per-layer time of the modulated conv, fp32 kernel vs bf16-operand kernel (GPU box):  python tools/bench_bf16_layers.py [B [N]]
+(N launches per timing, default 5; FMGAN_LIB selects the library, e.g. to alternate two builds.)
 Layers of Generator(1024) the bf16 kernel serves (position grid >= 32 wide), forward modes 0 / 1 and the stride-2 data
 gradient (mode 2).  TFLOP/s = 2*9*cin*cout*positions / time."""
 import os
@@ -13,12 +14,13 @@ from op import _native  # noqa: E402
 
 d = torch.device('cuda', 0)
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
+N = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 LAYERS = [(32, 512, 512, 0), (32, 512, 512, 1), (64, 512, 512, 0), (64, 512, 256, 1), (128, 256, 256, 0), (128, 256, 128, 1),
           (256, 128, 128, 0), (256, 128, 64, 1), (512, 64, 64, 0), (512, 64, 32, 1), (1024, 32, 32, 0),
           (1025, 32, 64, 2), (513, 64, 128, 2)]
 
 
-def t(fn, n=5):
+def t(fn, n=N):
     fn()
     torch.cuda.synchronize()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
