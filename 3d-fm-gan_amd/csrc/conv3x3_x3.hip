@@ -4,7 +4,9 @@
 // inference path of the pSp encoder: the first convolution of the fine style heads and the body's 3x3 convolutions whose
 // output is at least 32 wide (at a 256^2 photo: both convolutions of units 0-5 and conv1 of unit 6, thirteen of
 // sixteen; helpers.py body_x3_serves is the rule, FMGAN_PSP_BODY_X3=0 the switch; DESIGN 3.3c / 3.4d,
-// profiles/psp_body_x3.md).
+// profiles/psp_body_x3.md), and — on the narrow-tile members conv3x3_tail_x3 below — the heads' convolutions with an
+// output 9 .. 16 wide (psp_encoders.py TAIL_X3_WIDTHS; FMGAN_PSP_TAIL_X3=0 gives MIOpen back; profiles/psp_tail_x3.md).
+// The default pairs1024 / pairs256 figures of bench.py have all of these on this contraction.
 //
 // Stride 2 first.  The first convolution of a pSp style head (psp_encoders.py GradualStyleBlock): out = LeakyReLU(conv(in, W) + bias), NCHW
 // in, NCHW or NHWC out (the MIOpen tail of the head reads NHWC), no style and no demodulation (nothing to multiply: compiled out), the six-product contraction of
@@ -51,9 +53,18 @@ struct C3Params {
   int in_nhwc, out_nhwc;                                 // 0: [b][c][y][x]; 1: [b][y][x][c] (channels_last storage)
 };
 
-template <int S>
+// A block is four waves, WM on channel groups of 32 by WN on position groups; a wave holds RNP position groups of one
+// MFMA's 32 position lanes each, and a position group is 32 / TW output rows of TW columns (one row of 32 by default).
+// A_RING: 0, a wave fetches its weights one tap ahead (two blocks per CU cover the rest of the latency); a divisor of 9
+// (the narrow tiles, whose grids leave one block per CU or fewer, use 9): a ring of that many taps' weights, fetched
+// A_RING - 1 taps ahead across chunk boundaries.
+template <int S, int TW_ = 32, int BM_ = 64, int RNP_ = 2, int A_RING_ = 0>
 struct C3Tile {
-  static constexpr int BM = 64, TH = 4, TW = 32;
+  static constexpr int BM = BM_, TW = TW_, RNP = RNP_, A_RING = A_RING_;
+  static_assert(A_RING == 0 || 9 % A_RING == 0, "a tap keeps its ring slot from chunk to chunk");
+  static constexpr int WM = BM / 32, WN = 4 / WM, RPG = 32 / TW, TH = WN * RNP * RPG;
+  static constexpr int TW_LOG2 = TW == 32 ? 5 : TW == 16 ? 4 : 3, NPOS = TH * TW, NPOS_LOG2 = NPOS == 128 ? 7 : 6;
+  static_assert((WM == 1 || WM == 2) && (TW == 32 || TW == 16 || TW == 8) && (NPOS == 128 || NPOS == 64), "tile");
   static constexpr int PH = S * (TH - 1) + 3, PWP = S * (TW - 1) + 3, EVEN = (PWP + 1) / 2;
   static constexpr int PLANE = PH * PWP;
   static constexpr size_t LDS = (size_t)(3 * 2 * PLANE) * 16;
@@ -61,11 +72,11 @@ struct C3Tile {
 };
 
 // the launch's plan; false when the shape is not served (stride, channels_last width, 32-bit buffer ranges, grid size)
-bool c3_plan(C3Params& p) {
+template <class Tile>
+bool c3_plan_tile(C3Params& p) {
   if (p.batch <= 0 || p.cin <= 0 || p.cout <= 0 || p.h <= 0 || p.w <= 0) return false;
   if (p.stride != 1 && p.stride != 2) return false;
   if (p.in_nhwc && (p.cin & 3)) return false;                                               // 16-byte channel quads
-  using Tile = C3Tile<1>;                                                                   // (the output tile of both strides)
   p.oh = (p.h - 1) / p.stride + 1; p.ow = (p.w - 1) / p.stride + 1;
   p.mp = (p.cout + 31) / 32 * 32;
   p.tiles_x = (p.ow + Tile::TW - 1) / Tile::TW;
@@ -78,12 +89,13 @@ bool c3_plan(C3Params& p) {
   if ((long long)p.batch * p.cout * p.oh * p.ow > (1LL << 40)) return false;
   return true;
 }
+bool c3_plan(C3Params& p) { return c3_plan_tile<C3Tile<1>>(p); }                             // (the output tile of both strides)
 
-template <int S, bool NHWC_IN, int EPI>
-__global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf16x3(const C3Params p) {
-  using Tile = C3Tile<S>;
-  constexpr int BM = Tile::BM, TH = Tile::TH, TW = Tile::TW, PWP = Tile::PWP, EVEN = Tile::EVEN, PLANE = Tile::PLANE;
-  constexpr int RNP = 2;
+// One block's tile; the body of every kernel of this file.
+template <class Tile, int S, bool NHWC_IN, int EPI>
+__device__ __forceinline__ void c3_block(const C3Params p) {
+  constexpr int BM = Tile::BM, TW = Tile::TW, PWP = Tile::PWP, EVEN = Tile::EVEN, PLANE = Tile::PLANE;
+  constexpr int RNP = Tile::RNP, RPG = Tile::RPG, WM = Tile::WM;
   // staging units per thread and floats per unit.  A thread owns whole slots: 16 channels a plane apart (NCHW input) or
   // as four 16-byte loads (channels_last input, stride 1: 204 slots, the staging is a small part of the block's work).
   // QUAD (channels_last input, stride 2: 585 slots for the same products): four lanes share a slot, each on one 16-byte
@@ -97,14 +109,15 @@ __global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf
   u32x4* Xs = smem_q;                                   // [3 pieces][2 k-halves][PLANE]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, khalf = lane >> 5, wm = wave & 1, wn = wave >> 1;
+  const int l31 = lane & 31, khalf = lane >> 5, wm = wave & (WM - 1), wn = wave >> (WM - 1);
+  const int lr = l31 >> Tile::TW_LOG2, lc = l31 & (TW - 1);      // this lane's row and column in its position group
   const int kq = tid & 3;                                // QUAD: this lane's channel quad of its slots
   unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
   const int o_tile = lb % p.o_tiles; lb /= p.o_tiles;
   const int tx_i = lb % p.tiles_x; lb /= p.tiles_x;
   const int ty_i = lb % p.tiles_y;
   const int b = lb / p.tiles_y;
-  const int o0 = o_tile * BM, x0 = tx_i * TW, y0 = ty_i * TH;
+  const int o0 = o_tile * BM, x0 = tx_i * TW, y0 = ty_i * Tile::TH;
   const int hw = p.h * p.w;
   const float* in_b = p.in + (long long)b * p.cin * hw;
 
@@ -219,7 +232,7 @@ __global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf
 
   int pbase[RNP];
 #pragma unroll
-  for (int g = 0; g < RNP; ++g) pbase[g] = khalf * PLANE + S * (wn * RNP + g) * PWP + l31;
+  for (int g = 0; g < RNP; ++g) pbase[g] = khalf * PLANE + S * ((wn * RNP + g) * RPG + lr) * PWP + lc;
 
   struct Ops { u32x4 a[3]; bf16x8 b[3][RNP]; };
   auto fetch_a = [&](Ops& o, unsigned soff_chunk, int t) {
@@ -229,7 +242,7 @@ __global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf
   };
   auto fetch_b = [&](Ops& o, int t) {
     const int ky = t / 3, kx = t - 3 * ky;
-    const int off = S == 1 ? ky * PWP + kx : ky * PWP + (kx & 1) * EVEN + (kx >> 1);     // patch column S*l31 + kx
+    const int off = S == 1 ? ky * PWP + kx : ky * PWP + (kx & 1) * EVEN + (kx >> 1);     // patch column S*lc + kx
 #pragma unroll
     for (int pc = 0; pc < 3; ++pc)
 #pragma unroll
@@ -240,6 +253,49 @@ __global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf
   const int chunks = (p.cin + 15) >> 4;
 #pragma unroll
   for (int kc = 0; kc < 16; ++kc) issue_x(0, kc);
+  if constexpr (Tile::A_RING != 0) {
+    // Weights A_RING - 1 taps ahead: tap t of every chunk lives in ring slot t % A_RING (A_RING divides 9), refilled for
+    // tap t + A_RING - 1 — of the next chunk past tap 8 — once tap t - 1 has used it.  Same products in the same order.
+    constexpr int AR = Tile::A_RING, AD = AR - 1;
+    Ops ring[AR];                          // (.a only; the patch operands alternate between ring[0].b and ring[1].b)
+#pragma unroll
+    for (int t = 0; t < AD; ++t) fetch_a(ring[t], 0u, t);
+    for (int ch = 0; ch < chunks; ++ch) {
+      const unsigned soff_chunk = (unsigned)ch * 54u * mp16;
+      const unsigned soff_next = ch + 1 < chunks ? soff_chunk + 54u * mp16 : 0u;       // (as the patch: chunk 0 again, unused)
+      __syncthreads();
+      commit_x(16 * ch);
+      __syncthreads();
+      __builtin_amdgcn_sched_barrier(0);
+      fetch_b(ring[0], 0);
+      const int i0n = ch + 1 < chunks ? 16 * (ch + 1) : 0;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        __builtin_amdgcn_sched_barrier(0);
+        fetch_a(ring[(t + AD) % AR], t + AD < 9 ? soff_chunk : soff_next, (t + AD) % 9);
+        __builtin_amdgcn_sched_barrier(0);
+        if (t == 0) {                      // the next chunk's whole patch at once: nine taps to arrive in
+#pragma unroll
+          for (int kc = 0; kc < 16; ++kc) issue_x(i0n, kc);
+        }
+        if (t + 1 < 9) fetch_b(ring[(t + 1) & 1], t + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        const Ops &oa = ring[t % AR], &ob = ring[t & 1];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) wflag |= ((oa.a[0][e] & 0x7f807f80u) + 0x00800080u) & 0x80008000u;
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int q = 0; q < 6; ++q)
+#pragma unroll
+          for (int g = 0; g < RNP; ++g) {
+            f32x16& dst = q == 5 ? acc[g] : acc_lo[g];
+            dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, oa.a[PA[q]]), ob.b[PB[q]][g], dst, 0, 0, 0);
+          }
+        __builtin_amdgcn_s_setprio(0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  } else
   for (int ch = 0; ch < chunks; ++ch) {
     const unsigned soff_chunk = (unsigned)ch * 54u * mp16;
     Ops ops[2];
@@ -297,11 +353,13 @@ __global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf
   };
   const long long ost_o = p.out_nhwc ? 1 : (long long)p.oh * p.ow, ost_p = p.out_nhwc ? p.cout : 1;   // channel / position strides
   if (__syncthreads_or((xflag != xflag) | (wflag != 0u))) {
-    // Inf / NaN among this block's operands: the tile again as fp32 products.  Thread = one position x 32 channels.
-    const int pp = tid & 127, oy = y0 + (pp >> 5), ox = x0 + (pp & 31);
+    // Inf / NaN among this block's operands: the tile again as fp32 products.  Thread = one position x CPT channels
+    // (32 for the 64 x 128 tile).
+    constexpr int CPT = BM * Tile::NPOS / 256;
+    const int pp = tid & (Tile::NPOS - 1), oy = y0 + (pp >> Tile::TW_LOG2), ox = x0 + (pp & (TW - 1));
     if (oy >= p.oh || ox >= p.ow) return;
-    for (int oo = 0; oo < 32; ++oo) {
-      const int o = o0 + (tid >> 7) * 32 + oo;
+    for (int oo = 0; oo < CPT; ++oo) {
+      const int o = o0 + (tid >> Tile::NPOS_LOG2) * CPT + oo;
       if (o >= p.cout) return;
       float s = 0.f;
       for (int i = 0; i < p.cin; ++i) {
@@ -323,7 +381,7 @@ __global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf
     return;
   }
 
-  // ---- store through the epilogue; NCHW: 32 lanes on 32 consecutive x; NHWC: a lane's four consecutive channels
+  // ---- store through the epilogue; NCHW: 32 lanes on 32 / TW rows of TW consecutive x; NHWC: a lane's four consecutive channels
   // (r & 3) as one 16-byte store, the two k-halves and four row groups of a position filling 128 consecutive bytes
   const int orow = o0 + wm * 32 + 4 * khalf;            // row r of the 32-row group adds (r&3) + 8*(r>>2)
   float aux_r[16];
@@ -332,7 +390,7 @@ __global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf
     aux_r[r] = (EPI != C3_NONE && p.aux) ? p.aux[min(orow + (r & 3) + 8 * (r >> 2), p.cout - 1)] : 0.f;
 #pragma unroll
   for (int g = 0; g < RNP; ++g) {
-    const int py_ = y0 + wn * RNP + g, px_ = x0 + l31;
+    const int py_ = y0 + (wn * RNP + g) * RPG + lr, px_ = x0 + lc;
     if (py_ >= p.oh || px_ >= p.ow) continue;
     float* dpos = out_b + ((long long)py_ * p.ow + px_) * ost_p;
     float v[16];
@@ -358,14 +416,54 @@ __global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf
 }
 
 template <int S, bool NHWC_IN, int EPI>
-int c3_launch(const C3Params& p, hipStream_t s) {
-  using Tile = C3Tile<S>;
-  void (*kernel)(const C3Params) = conv3x3_mfma_bf16x3<S, NHWC_IN, EPI>;
-  static bool opted_in = false;     // per instantiation
+__global__ __launch_bounds__(256, C3Tile<S>::BLOCKS_PER_CU) void conv3x3_mfma_bf16x3(const C3Params p) {
+  c3_block<C3Tile<S>, S, NHWC_IN, EPI>(p);
+}
+
+// The narrow-tile members: stride 2, channels_last input, bias + LeakyReLU, for outputs at most 16 wide, where the
+// 32-column tile above leaves MFMA position lanes empty (the pSp style heads' convolutions after the first, and the
+// first one of the middle and coarse heads).  A position group is 2 output rows of 16 columns (TW = 16) or 4 rows of 8
+// (TW = 8), one group per wave: TW = 16 is 64 channels x (4 rows x 16 columns), patch 9 x 33 slots (28 KB); TW = 8 is 64
+// channels x (8 rows x 8 columns), patch 17 x 17 slots (28 KB).  At the heads' B = 8 the grid is one block per CU or
+// fewer, so nothing covers a wave's waits but the wave itself: the weights come through a ring of nine taps (a whole
+// chunk ahead) and the next chunk's patch is requested at once at tap 0.  64 x (4 x 16) was measured against 64 x
+// (8 x 16) and 32 x (8 x 16) (profiles/psp_tail_x3.md).  Same staging, contraction, summation order and fallback: on
+// finite operands the bits are those of conv3x3_mfma_bf16x3<2, true, C3_LRELU>.
+template <int TW> struct TailTile { using type = C3Tile<2, TW, 64, 1, 9>; };
+
+template <int TW>
+__global__ __launch_bounds__(256, 2) void conv3x3_tail_x3(const C3Params p) {
+  c3_block<typename TailTile<TW>::type, 2, true, C3_LRELU>(p);
+}
+
+template <class Tile>
+int c3_launch_kernel(void (*kernel)(const C3Params), bool& opted_in, const C3Params& p, hipStream_t s) {
   opt_in_dynamic_lds(kernel, Tile::LDS, opted_in);
   const long long blocks = (long long)p.o_tiles * p.tiles_x * p.tiles_y * p.batch;
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), Tile::LDS, s, p);
   return fmgan_check_launch();
+}
+
+template <int S, bool NHWC_IN, int EPI>
+int c3_launch(const C3Params& p, hipStream_t s) {
+  static bool opted_in = false;     // per instantiation
+  return c3_launch_kernel<C3Tile<S>>(conv3x3_mfma_bf16x3<S, NHWC_IN, EPI>, opted_in, p, s);
+}
+
+template <int TW>
+int tail_launch(const C3Params& p, hipStream_t s) {
+  static bool opted_in = false;
+  return c3_launch_kernel<typename TailTile<TW>::type>(conv3x3_tail_x3<TW>, opted_in, p, s);
+}
+
+// The tail's plan: the tile width (16 or 8) that serves the shape, or the status the launch returns.
+int tail_plan(C3Params& p) {
+  if (p.batch <= 0 || p.cin <= 0 || p.cout <= 0 || p.h <= 0 || p.w <= 0) return FMGAN_EINVAL;
+  p.stride = 2; p.epi = C3_LRELU; p.in_nhwc = 1;
+  const int ow = (p.w - 1) / 2 + 1;
+  if (ow > 16 || ow <= 4) return FMGAN_EUNSUPPORTED;     // wider: conv3x3_mfma_bf16x3; narrower: launch-latency-bound, MIOpen's
+  if (ow > 8) return c3_plan_tile<TailTile<16>::type>(p) ? 16 : FMGAN_EUNSUPPORTED;
+  return c3_plan_tile<TailTile<8>::type>(p) ? 8 : FMGAN_EUNSUPPORTED;
 }
 
 template <int S, bool NHWC_IN>
@@ -417,4 +515,24 @@ extern "C" int fmgan_conv3x3_bf16x3_f32(const float* in, const void* wt_split, c
                                         int epilogue, float alpha, void* stream) {
   return conv3x3_bf16x3(in, wt_split, aux, out, batch, cin, cout, h, w, stride, in_nhwc, out_nhwc, epilogue, alpha,
                         (hipStream_t)stream);
+}
+
+// ---- pSp style heads, outputs 5 .. 16 wide: the narrow-tile members (stride 2, channels_last in, bias + LeakyReLU)
+extern "C" int fmgan_conv3x3_tail_bf16x3_select(int batch, int cin, int cout, int h, int w) {
+  C3Params p{};
+  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
+  return tail_plan(p);
+}
+
+extern "C" int fmgan_conv3x3_tail_bf16x3_f32(const float* in, const void* wt_split, const float* bias, float* out, int batch,
+                                             int cin, int cout, int h, int w, float alpha, int out_nhwc, void* stream) {
+  if (out_nhwc != 0 && out_nhwc != 1) return FMGAN_EINVAL;
+  C3Params p{};
+  p.in = in; p.wt = (const unsigned short*)wt_split; p.aux = bias; p.out = out;
+  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w; p.alpha = alpha; p.out_nhwc = out_nhwc;
+  const int tw = tail_plan(p);
+  if (tw < 0) return tw;
+  if (!in || !wt_split || !out) return FMGAN_EINVAL;
+  if (((uintptr_t)in & 15) || (out_nhwc && (cout & 3) == 0 && ((uintptr_t)out & 15))) return FMGAN_EINVAL;   // 16-byte loads / stores
+  return tw == 16 ? tail_launch<16>(p, (hipStream_t)stream) : tail_launch<8>(p, (hipStream_t)stream);
 }

@@ -190,12 +190,13 @@ def modconv_weight_to_bf16x3(wt):
     return wts
 
 
-def conv_weight_to_bf16x3(weight):
+def conv_weight_to_bf16x3(weight, bracket='conv_weight_bf16x3'):
     """A Conv2d weight [cout, cin, 3, 3] (any memory format) -> the split-operand image of conv3x3s2_bf16x3: the
-    [cin, 9, cout] order, then modconv_weight_to_bf16x3.  One bracket ('conv_weight_bf16x3') round the two steps."""
+    [cin, 9, cout] order, then modconv_weight_to_bf16x3.  One bracket round the two steps, named `bracket`
+    ('conv_weight_bf16x3'; the heads' narrow-tile convolutions build theirs under 'conv_tail_weight_bf16x3')."""
     require_gpu(weight, 'weight')
     cout, cin, kh, kw = weight.shape
-    with launching(weight, 'conv_weight_bf16x3', (cout, cin, kh * kw)):
+    with launching(weight, bracket, (cout, cin, kh * kw)):
         wt = weight.detach().permute(1, 2, 3, 0).reshape(cin, kh * kw, cout).contiguous()
         return modconv_weight_to_bf16x3(wt)
 
@@ -266,6 +267,30 @@ def conv3x3_bf16x3(x, wts, cout, stride=1, epilogue=None, aux=None, alpha=0.01, 
         st = lib().fmgan_conv3x3_bf16x3_f32(fp(x), ptr(wts), fp(aux), fp(out), b, cin, cout, h, w, stride, in_nhwc,
                                             int(bool(channels_last)), epi, float(alpha), stream)
     return out if served(st, 'conv3x3_bf16x3') else None
+
+
+def conv3x3_tail_bf16x3_select(batch, cin, cout, h, w):
+    """16 or 8: the tile width of conv3x3_tail_bf16x3 that serves the shape (stride-2 output 9 .. 16 or 5 .. 8 wide);
+    otherwise the negative status its launch returns (FMGAN_EUNSUPPORTED, FMGAN_EINVAL).  Host logic, no device."""
+    return int(lib().fmgan_conv3x3_tail_bf16x3_select(int(batch), int(cin), int(cout), int(h), int(w)))
+
+
+def conv3x3_tail_bf16x3(x, wts, bias, cout, alpha=0.01, channels_last=True):
+    """LeakyReLU(conv3x3(x, stride 2, pad 1) + bias) for outputs 5 .. 16 wide, on the narrow-tile members of the
+    split-operand family (the bits of conv3x3_bf16x3(x, wts, cout, 2, 'lrelu', bias) on finite operands).  x [B,cin,H,W]
+    f32 in dense channels_last storage, cin % 4 == 0; wts = conv_weight_to_bf16x3(weight); bias [cout] or None.  Returns
+    [B,cout,(H-1)//2+1,(W-1)//2+1] written in channels_last storage (channels_last=False: NCHW-contiguous), or None
+    where the library declines the shape.  Launch bracket 'conv3x3_tail_bf16x3' with info (b, cin, cout, h, w)."""
+    require_gpu(x, 'input')
+    if not nhwc_dense(x):
+        raise RuntimeError(f'conv3x3_tail_bf16x3: input must be dense channels_last, got strides {x.stride()}')
+    b, cin, h, w = x.shape
+    out = torch.empty((b, cout, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    with launching(x, 'conv3x3_tail_bf16x3', (b, cin, cout, h, w)) as stream:
+        st = lib().fmgan_conv3x3_tail_bf16x3_f32(fp(x), ptr(wts), fp(bias), fp(out), b, cin, cout, h, w, float(alpha),
+                                                 int(bool(channels_last)), stream)
+    return out if served(st, 'conv3x3_tail_bf16x3') else None
 
 
 # ----------------------------------------------------------------------------- csrc/modconv_wgrad.hip

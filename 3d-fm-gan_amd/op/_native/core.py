@@ -112,6 +112,8 @@ def lib():
     _sig(L.fmgan_conv3x3s2_bf16x3_f32, [vp] * 4 + [i] * 5 + [f, i, vp])
     _sig(L.fmgan_conv3x3_bf16x3_supported, [i] * 7)
     _sig(L.fmgan_conv3x3_bf16x3_f32, [vp] * 4 + [i] * 9 + [f, vp])
+    _sig(L.fmgan_conv3x3_tail_bf16x3_select, [i] * 5)
+    _sig(L.fmgan_conv3x3_tail_bf16x3_f32, [vp] * 4 + [i] * 5 + [f, i, vp])
     # csrc/modconv_wgrad.hip
     _sig(L.fmgan_modconv_wgrad_workspace_bytes, [i] * 5, ll)
     _sig(L.fmgan_modconv_wgrad_f32, [vp] * 5 + [i] * 5 + [f, vp, ll, vp])

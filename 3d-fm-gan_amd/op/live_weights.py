@@ -143,8 +143,9 @@ def live(module):
 _SPLIT = weakref.WeakKeyDictionary()      # Conv2d module -> (key, image, built event, stream); not copied with the module
 
 
-def split_conv_weight(conv):
-    """The three-piece bf16 image of `conv.weight` for _native.conv3x3s2_bf16x3, kept per module and rebuilt only when the
+def split_conv_weight(conv, bracket='conv_weight_bf16x3'):
+    """The three-piece bf16 image of `conv.weight` for _native.conv3x3s2_bf16x3 (built under the launch bracket `bracket`:
+    conv_weight_to_bf16x3), kept per module and rebuilt only when the
     parameter's storage, device or autograd version changes: an optimizer step, `copy_` (load_state_dict) and any other
     in-place update of the PARAMETER bump `_version`; `p.data = ...` changes the storage.  (A write through `p.data` in
     place changes neither — see the module docstring; such an updater of an encoder calls drop_split_weight.  The
@@ -154,7 +155,7 @@ def split_conv_weight(conv):
     kept = _SPLIT.get(conv)
     stream = torch.cuda.current_stream(w.device)
     if kept is None or kept[0] != key:
-        img = _native.conv_weight_to_bf16x3(w)
+        img = _native.conv_weight_to_bf16x3(w, bracket)
         built = torch.cuda.Event()
         built.record(stream)
         kept = (key, img, built, stream)

@@ -10,7 +10,10 @@ not provided.
 Not every convolution of the default inference path is MIOpen's: the body's 3x3 convolutions with an output at least 32
 wide (helpers.body_x3_serves; switch helpers.BODY_X3 / FMGAN_PSP_BODY_X3=0) and the fine heads' first convolution
 (HEADS_X3 / FMGAN_PSP_HEADS_X3=0, reading the level's channels_last feature map as it is) run on the split-operand bf16
-contraction with fp32 accumulation of csrc/conv3x3_x3.hip (profiles/psp_body_x3.md, profiles/psp_heads_x3.md).
+contraction with fp32 accumulation of csrc/conv3x3_x3.hip (profiles/psp_body_x3.md, profiles/psp_heads_x3.md), and so do
+the heads' convolutions whose output is 9 .. 16 wide, on its narrow-tile members (TAIL_X3 / FMGAN_PSP_TAIL_X3=0 gives
+MIOpen back; TAIL_X3_WIDTHS; profiles/psp_tail_x3.md).  The default `pairs1024` / `pairs256` figures of bench.py have all of these on
+the split-operand contraction.
 """
 import math
 import os
@@ -63,6 +66,17 @@ X3_TAIL_CHANNELS_LAST = True
 # (66 us for p1 at B=8).  profiles/psp_body_x3.md has the stand-alone comparison that decided it.
 X3_HEAD_CHANNELS_LAST_IN = True
 
+# Inference: the heads' FOLLOWING convolutions with an output 9 .. 16 wide ("16") or 5 .. 8 wide ("8") — for the middle and
+# coarse heads that includes the first one, on the level's feature map — run on the narrow-tile members of the same
+# family (conv3x3_tail_x3: an MFMA's 32 position lanes are two rows of 16 or four rows of 8) with bias + LeakyReLU in the
+# epilogue, channels_last in and out, instead of MIOpen's split-K implicit GEMM + zero-fill + fused_bias_act.
+# FMGAN_PSP_TAIL_X3=0 keeps MIOpen.  TAIL_X3_WIDTHS: the width classes that passed the per-layer rule of
+# profiles/psp_tail_x3.md (the kernel's slowest round beats MIOpen's fastest at B=8 and at B=32): the 16-wide class
+# does (77-83 against 90-105 us at B=8); the 8-wide one does at B=32 but not at B=8 (67-71 against MIOpen's split-K
+# 38-47 us: 64 blocks on 256 CUs), so those convolutions stay on MIOpen.
+TAIL_X3 = os.environ.get('FMGAN_PSP_TAIL_X3', '1') == '1'
+TAIL_X3_WIDTHS = (16,)
+
 _TAPS = {18: (3, 5, 7), 50: (6, 20, 23)}   # units whose outputs feed the pyramid (psp_encoders.py:105-108)
 
 
@@ -104,6 +118,17 @@ class GradualStyleBlock(Module):
             raise RuntimeError('conv3x3s2_bf16x3 declined a shape its query accepted')
         return y
 
+    @staticmethod
+    def tail_x3_serves(x, conv):
+        """Does `conv` (3x3, stride 2, pad 1, with bias) on x run on conv3x3_tail_bf16x3?  (inference, fp32, dense
+        channels_last x, a width class of TAIL_X3_WIDTHS)"""
+        if not (TAIL_X3 and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()):
+            return False
+        if conv.weight.dtype != torch.float32 or conv.bias is None or not _native.nhwc_dense(x):
+            return False
+        return _native.conv3x3_tail_bf16x3_select(x.shape[0], conv.in_channels, conv.out_channels, x.shape[2],
+                                                  x.shape[3]) in TAIL_X3_WIDTHS
+
     def forward(self, x, x_nchw=None):
         """x_nchw: the NCHW-contiguous copy of x, when the caller shares one among the heads of a pyramid level."""
         if x.is_cuda and x.dtype == torch.float32:
@@ -116,6 +141,12 @@ class GradualStyleBlock(Module):
             # conv, then bias + LeakyReLU(0.01) in ONE pass of the HIP fused_bias_act kernel (the same arithmetic as
             # MIOpen's separate bias add followed by aten leaky_relu: (v + b) > 0 ? . : 0.01 * .  — bit-identical).
             for conv, act in convs:
+                if self.tail_x3_serves(x, conv):
+                    x = _native.conv3x3_tail_bf16x3(x, split_conv_weight(conv, 'conv_tail_weight_bf16x3'), conv.bias,
+                                                    conv.out_channels, act.negative_slope)
+                    if x is None:
+                        raise RuntimeError('conv3x3_tail_bf16x3 declined a shape its query accepted')
+                    continue
                 y = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
                 if y.is_contiguous(memory_format=torch.channels_last) and not y.is_contiguous():
                     n, c, h, w = y.shape                       # NHWC storage: channel is the fastest dimension

@@ -693,6 +693,21 @@ int fmgan_conv3x3_bf16x3_f32(const float *in, const void *wt_split, const float 
                              int epilogue, float alpha, void *stream);
 
 /*
+ * The narrow-tile members of the family (csrc/conv3x3_x3.hip conv3x3_tail_x3; the pSp style heads' convolutions whose
+ * output is 5 .. 16 wide): stride 2, in[b][y][x][i] (channels_last storage, 16-byte aligned, cin % 4 == 0), epilogue
+ * lrelu(conv + bias[o]) (bias may be NULL), out_nhwc as above.  An MFMA's 32 position lanes are 2 output rows of 16
+ * columns (outputs 9 .. 16 wide) or 4 rows of 8 (5 .. 8 wide) instead of one row of 32; contraction, summation order,
+ * wt_split and special values are those of fmgan_conv3x3_bf16x3_f32, whose bits the result has on finite operands.
+ * fmgan_conv3x3_tail_bf16x3_select is the launch's plan without the launch: 16 or 8, the tile width that serves the
+ * shape, or the status the launch would return — FMGAN_EINVAL for a non-positive size, FMGAN_EUNSUPPORTED for an
+ * output wider than 16 (fmgan_conv3x3_bf16x3_f32 serves those) or at most 4 wide, cin % 4 != 0 and sizes past the
+ * 32-bit buffer ranges.  A declined launch launches nothing.
+ */
+int fmgan_conv3x3_tail_bf16x3_select(int batch, int cin, int cout, int h, int w);
+int fmgan_conv3x3_tail_bf16x3_f32(const float *in, const void *wt_split, const float *bias, float *out,
+                                  int batch, int cin, int cout, int h, int w, float alpha, int out_nhwc, void *stream);
+
+/*
  * Plain (mode 0) modulated conv with the FOLLOWING ToRGB layer folded into its epilogue.  In the reference these are
  * two modules and three HBM passes over the activation (StyledConv conv2 -> ToRGB, stylegan2.py:646-651 calling
  * :360-376 and :393-404).  When one block holds every output channel of its pixels (cout <= the tile's channel

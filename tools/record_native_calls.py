@@ -306,6 +306,13 @@ def convolutions(d):
     assert _native.conv3x3_bf16x3(xcl, img, cout, 1, 'prelu', bias, channels_last=True) is not None
     assert _native.conv3x3_bf16x3(xcl, img, cout, 2, None, channels_last=True) is not None
     assert _native.conv3x3_bf16x3(x, img, cout, 2, 'lrelu', bias, 0.01) is not None
+    section('conv3x3_tail_bf16x3')        # tests/test_psp_tail_x3.py's 5-wide case
+    b, cin, cout, h, w = 1, 16, 64, 10, 9
+    host('conv3x3_tail_bf16x3_select', b, cin, cout, h, w)
+    xcl, bias = t('tail/x', (b, cin, h, w), d).contiguous(memory_format=torch.channels_last), t('tail/b', (cout,), d)
+    img = _native.conv_weight_to_bf16x3(t('tail/w', (cout, cin, 3, 3), d), 'conv_tail_weight_bf16x3')
+    assert _native.conv3x3_tail_bf16x3(xcl, img, bias, cout, 0.01) is not None
+    assert _native.conv3x3_tail_bf16x3(xcl, img, bias, cout, 0.01, channels_last=False) is not None
     section('torgb_backward')
     b, cin, hw = 2, 8, 4
     _native.torgb_backward(t('rgb/x', (b, cin, hw, hw), d), t('rgb/go', (b, 3, hw, hw), d), t('rgb/w', (1, 3, cin, 1, 1), d),
