@@ -8,7 +8,9 @@
 // into LDS, the scaled weight once per forward by fmgan_modconv_weight_prep_bf16.  Products of two bf16 values are exact
 // in fp32, so the result equals a wide-accumulator convolution of the ROUNDED operands up to fp32 summation error — that
 // is what the tests check (tolerance 2e-5 of max|out| against a float64 convolution of the rounded operands), next to the
-// bf16-sized distance (~3e-3) from the fp32 kernel.
+// bf16-sized distance (~3e-3) from the fp32 kernel.  tests/test_hip_modconv_bf16_edges.py holds both kernels at their
+// edges: special values (bf16: NaN and signed Inf where the definition has them, a value beyond the largest bf16 being
+// Inf by definition; bf16x3: the contract at modconv_mfma_bf16x3), minimum grids and the data gradient.
 //
 // Mapping.  v_mfma_f32_32x32x16_bf16: lane l (r = l & 31, h = l >> 5) supplies A[row r][k = 8h + j] and
 // B[k = 8h + j][col r], j = 0..7, as one 16-byte register quad each (cdna_hip_programming.md §3).  K = input channels
@@ -412,8 +414,13 @@ __global__ __launch_bounds__(256, 2) void modconv_mfma_bf16(const BFParams p) {
 //     LDS per 16-channel chunk: 3 weight pieces [piece][tap][k-half][32][8] = 27 KB + 3 patch pieces — 60 KB for
 //     RNP = 2: two blocks per CU;
 //   * weights by LDS-DMA after the chunk's first barrier (single image: a second one would cost the second block),
-//     patch through registers one chunk ahead, split into its pieces on the way into LDS (11 VALU ops per pair);
+//     patch through registers one chunk ahead, split into its pieces on the way into LDS (13 VALU ops per pair);
 //   * per tap: 3 + 3*RNP operand reads (ds_read_b128) feed 6*RNP MFMAs.
+// Special values (tests/test_hip_modconv_bf16_edges.py): finite operands, up to the largest fp32, whose exact result is
+// finite give a finite result of fp32 accuracy — both splits clamp the value that forms the high piece to the largest
+// finite bf16, so the residual stays exact.  An Inf or NaN operand makes the outputs that read it non-finite, exactly
+// the positions where a direct convolution is non-finite, and no others; WHICH non-finite value appears (Inf, its sign,
+// NaN) is unspecified: there is no fp32 recomputation of such tiles here (conv3x3_x3.hip has one).
 __global__ __launch_bounds__(256) void modconv_weight_to_bf16x3(const float* __restrict__ wt, unsigned* __restrict__ wtb,
                                                                 int K, int M, int ktaps) {
   const int Mp = (M + 31) / 32 * 32, chunks = (K + 15) / 16;
@@ -498,7 +505,9 @@ __global__ __launch_bounds__(256, 2) void modconv_mfma_bf16x3(const BFParams p) 
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float v0 = xv[u][8 * hh + 2 * e] * sv[8 * hh + 2 * e], v1 = xv[u][8 * hh + 2 * e + 1] * sv[8 * hh + 2 * e + 1];
-            const unsigned h01 = pack_bf16(v0, v1);
+            // hi clamped to the largest finite bf16 (RNE would round a finite value beyond it to Inf and the residual
+            // to Inf - Inf): the residual stays exact in fp32 and goes to mid + lo
+            const unsigned h01 = pack_bf16(__builtin_amdgcn_fmed3f(v0, -BF16_MAX, BF16_MAX), __builtin_amdgcn_fmed3f(v1, -BF16_MAX, BF16_MAX));
             const float r0 = v0 - __uint_as_float(h01 << 16), r1 = v1 - __uint_as_float(h01 & 0xffff0000u);
             const unsigned m01 = pack_bf16(r0, r1);
             const float s0 = r0 - __uint_as_float(m01 << 16), s1 = r1 - __uint_as_float(m01 & 0xffff0000u);

@@ -108,6 +108,29 @@ def modconv_bf16_reference(x, weight, style, demod, mode, scale):
     return y
 
 
+def modconv_bf16_dgrad_reference(go, weight, demod, mode, scale, in_hw, rounded=True):
+    """The data gradient of the modulated conv w.r.t. its modulated input u = x * style, in float64, as the first-order
+    backward computes it on fmgan_modconv2d_bf16 (op/modconv.py, ModulatedConv2dFunction.backward): the adjoint of the
+    forward definition C(u) = conv_mode(u, wq), wq = bf16(fl32(scale*W)) fixed, applied to bf16(fl32(go * demod))
+    (demod = 1 when None) — obtained by autograd through C itself, so no second statement of the adjoint is involved.
+    go [B,Cout,OH,OW], weight [Cout,Cin,3,3], demod [B,Cout] or None, in_hw = (H, W) of the forward input.
+    rounded=False: the same adjoint of the unrounded operands (a shape the bf16 kernel does not serve)."""
+    g = go.float() if demod is None else go.float() * demod.float()[:, :, None, None]
+    wq = weight.float() * torch.tensor(scale, dtype=torch.float32)
+    if rounded:
+        g, wq = g.to(torch.bfloat16), wq.to(torch.bfloat16)
+    g, wq = g.double(), wq.double()
+    u = torch.zeros(go.shape[0], weight.shape[1], in_hw[0], in_hw[1], dtype=torch.float64, requires_grad=True)
+    if mode == 0:
+        y = F.conv2d(u, wq, padding=1)
+    elif mode == 1:
+        y = F.conv_transpose2d(u, wq.transpose(0, 1), stride=2)
+    else:
+        y = F.conv2d(u, wq, stride=2)
+    gu, = torch.autograd.grad(y, u, g)
+    return gu
+
+
 def styled_conv(sd, prefix, x, w_latent, noise, upsample, blur_kernel=(1, 3, 3, 1)):
     """StyledConv.forward, stylegan2.py:360-376 (conv -> NoiseInjection :307-312 -> FusedLeakyReLU)."""
     out = modulated_conv2d(x, w_latent, sd[prefix + '.conv.weight'], sd[prefix + '.conv.modulation.weight'],

@@ -10,6 +10,8 @@ import torch
 
 import synth
 from gpumem import dev
+from launches import observed
+from modconv_bf16_cases import inputs as _inputs
 from nets import load
 from parity import no_farther_than_reference
 
@@ -22,14 +24,6 @@ CASES = [
     (2, 32, 32, 64, 64, 1), (1, 16, 32, 9, 33, 1), (2, 64, 64, 32, 32, 1), (1, 48, 96, 21, 45, 1),
     (2, 32, 32, 129, 129, 2), (1, 16, 64, 75, 67, 2), (1, 64, 32, 67, 131, 2), (2, 32, 96, 11, 65, 2),
 ]
-
-
-def _inputs(cfg):
-    b, cin, cout, h, w, mode = cfg
-    x = synth.tensor(f'bf/{cfg}/x', (b, cin, h, w))
-    wgt = synth.tensor(f'bf/{cfg}/w', (cout, cin, 3, 3))
-    s = synth.tensor(f'bf/{cfg}/s', (b, cin), shift=1.0, scale=0.5)
-    return x, wgt, s, float(np.float32(1.0 / np.sqrt(cin * 9)))
 
 
 @pytest.mark.parametrize('cfg', CASES)
@@ -125,7 +119,10 @@ def test_bf16_generator_forward_within_stated_tolerance():
     kw['external_input_tensor'] = tsr_g
     g32, = torch.autograd.grad(G(None, **kw).abs().mean(), tsr_g)
     with _native.modconv_precision('bf16'):
-        g16, = torch.autograd.grad(G(None, **kw).abs().mean(), tsr_g)
+        loss = G(None, **kw).abs().mean()
+        with observed() as rec:
+            g16, = torch.autograd.grad(loss, tsr_g)
+    assert rec.count('modconv2d_bf16') >= 1, rec.names       # the data gradients ran on the bf16 kernel
     assert torch.isfinite(g16).all()
     assert float((g16 - g32).abs().max() / g32.abs().max()) < 0.1
 
