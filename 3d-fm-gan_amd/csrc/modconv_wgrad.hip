@@ -359,37 +359,73 @@ __global__ __launch_bounds__(256) void modconv_wgrad64_finish_f32(const float* _
   }
 }
 
+// ---- the plan: which kernel, which pixel tile, which split over pixels.  ONE decision, made here, for the launch, for the
+// workspace query and for fmgan_modconv_wgrad_select (the launch's plan with the launch left out).
 // mode 0: plain conv; 1: transposed stride-2 conv (x [h,w], go [2h+1,2w+1]); 2: stride-2 valid conv (x [h,w], go [(h-3)/2+1, ..])
-inline bool wgrad64_setup(WG64Params& q, const float* go, const float* demod, const float* x, const float* style,
-                          int batch, int cin, int cout, int h, int w, int mode) {
-  if (cin < 48 || cout < 48) return false;
-  q.batch = batch;
+struct WGPlan {
+  int family;                    // 0: declined (the host keeps MIOpen's wgrad); 32 / 64: the channel tile of the kernel
+  int tw_log2, sp;               // 64: modconv_wgrad64_f32<tw_log2, sp>;  32: WGParams::tw_log2, sp = 1
+  int ca, ha, wa, cb, hb, wb;    // channels and plane of the unshifted operand A and of the shifted one B (WG64Params);
+                                 // for the 32 x 32 tile A = go, B = x
+  int th;                        // rows of a pixel tile: 2 (64), 128 / TW (32)
+  int tiles_x, tiles_y, ntiles, a_tiles, b_tiles, ksplit, tiles_per_split;
+};
+
+inline WGPlan wgrad_plan(int batch, int cin, int cout, int h, int w, int mode) {
+  WGPlan pl{};
+  const bool wide = cin >= 48 && cout >= 48;               // 64 x 64 tile; narrower layers: the 32 x 32 tile, plain conv only
+  if (!wide && mode != 0) return pl;
   if (mode == 0) {
-    q.A = go; q.sa = demod; q.ca = cout; q.ha = h; q.wa = w;
-    q.B = x; q.sb = style; q.cb = cin; q.hb = h; q.wb = w;
+    pl.ca = cout; pl.ha = h; pl.wa = w;
+    pl.cb = cin; pl.hb = h; pl.wb = w;
   } else if (mode == 1) {
-    q.A = x; q.sa = style; q.ca = cin; q.ha = h; q.wa = w;
-    q.B = go; q.sb = demod; q.cb = cout; q.hb = 2 * h + 1; q.wb = 2 * w + 1;
+    pl.ca = cin; pl.ha = h; pl.wa = w;
+    pl.cb = cout; pl.hb = 2 * h + 1; pl.wb = 2 * w + 1;
   } else {
-    if (h < 3 || w < 3) return false;
-    q.A = go; q.sa = demod; q.ca = cout; q.ha = (h - 3) / 2 + 1; q.wa = (w - 3) / 2 + 1;
-    q.B = x; q.sb = style; q.cb = cin; q.hb = h; q.wb = w;
+    if (h < 3 || w < 3) return pl;
+    pl.ca = cout; pl.ha = (h - 3) / 2 + 1; pl.wa = (w - 3) / 2 + 1;
+    pl.cb = cin; pl.hb = h; pl.wb = w;
   }
-  if (q.wa < 16) return false;
-  const int TW = (mode == 0 && q.wa >= 32) ? 32 : 16;
-  q.tiles_x = (q.wa + TW - 1) / TW;
-  q.tiles_y = (q.ha + 1) / 2;
-  q.ntiles = batch * q.tiles_x * q.tiles_y;
-  q.a_tiles = (q.ca + 63) / 64;
-  q.b_tiles = (q.cb + 63) / 64;
-  const int pairs = q.a_tiles * q.b_tiles;
-  int ks = (FMGAN_NUM_CU * 4 + pairs - 1) / pairs;      // ~2 rounds of 2 blocks per CU
-  const int max_ks = q.ntiles / 4 > 0 ? q.ntiles / 4 : 1; // at least 4 tile steps per block
+  if (pl.wa < 16) return pl;                               // narrow / tiny layers: the host keeps MIOpen's wgrad
+  const int tile = wide ? 64 : 32;
+  pl.tw_log2 = (mode == 0 && pl.wa >= 32) ? 5 : 4;
+  pl.sp = mode == 0 ? 1 : 2;
+  const int TW = 1 << pl.tw_log2;
+  pl.th = wide ? 2 : 128 / TW;
+  pl.tiles_x = (pl.wa + TW - 1) / TW;
+  pl.tiles_y = (pl.ha + pl.th - 1) / pl.th;
+  pl.ntiles = batch * pl.tiles_x * pl.tiles_y;
+  pl.a_tiles = (pl.ca + tile - 1) / tile;
+  pl.b_tiles = (pl.cb + tile - 1) / tile;
+  const int pairs = pl.a_tiles * pl.b_tiles;
+  // 64: ~2 rounds of 2 blocks per CU, at least 4 tile steps per block;  32: ~3 rounds of 2 blocks per CU
+  int ks = (FMGAN_NUM_CU * (wide ? 4 : 6) + pairs - 1) / pairs;
+  const int max_ks = wide ? (pl.ntiles / 4 > 0 ? pl.ntiles / 4 : 1) : pl.ntiles;
   if (ks > max_ks) ks = max_ks;
   if (ks < 1) ks = 1;
-  q.tiles_per_split = (q.ntiles + ks - 1) / ks;
-  q.ksplit = (q.ntiles + q.tiles_per_split - 1) / q.tiles_per_split;
-  return true;
+  pl.tiles_per_split = (pl.ntiles + ks - 1) / ks;
+  pl.ksplit = (pl.ntiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
+  pl.family = tile;
+  return pl;
+}
+
+// What the entry points answer before they plan: bad sizes, unknown mode; then (wgrad_range) the 32-bit index ranges.
+inline int wgrad_sizes(int batch, int cin, int cout, int h, int w, int mode) {
+  if (batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return FMGAN_EINVAL;
+  if (mode < 0 || mode > 2) return FMGAN_EUNSUPPORTED;
+  return FMGAN_OK;
+}
+
+inline int wgrad_range(int batch, int cin, int cout, int h, int w, int mode) {
+  // go is the largest tensor of the transposed conv: [batch, cout, 2h+1, 2w+1]
+  const long long big_hw = mode == 1 ? (long long)(2 * h + 1) * (2 * w + 1) : (long long)h * w;
+  if ((long long)batch * (cin > cout ? cin : cout) * big_hw >= (1LL << 40)) return FMGAN_EOVERFLOW;
+  if (big_hw >= (1LL << 31) || cin > (1 << 20) || cout > (1 << 20)) return FMGAN_EOVERFLOW;
+  return FMGAN_OK;
+}
+
+inline long long wgrad_workspace(const WGPlan& pl) {
+  return (long long)pl.ksplit * 9 * pl.ca * pl.cb * (long long)sizeof(float);
 }
 
 template <int TWL2, int SP>
@@ -400,89 +436,88 @@ inline void wgrad64_launch(const WG64Params& q, long long nblk, hipStream_t s) {
   hipLaunchKernelGGL((modconv_wgrad64_f32<TWL2, SP>), dim3((unsigned)nblk), dim3(256), lds, s, q);
 }
 
-inline void wgrad_plan(WGParams& p) {
-  p.tw_log2 = p.w >= 32 ? 5 : 4;
-  const int TW = 1 << p.tw_log2;
-  p.th = 128 / TW;
-  p.tiles_x = (p.w + TW - 1) / TW;
-  p.tiles_y = (p.h + p.th - 1) / p.th;
-  p.ntiles = p.batch * p.tiles_x * p.tiles_y;
-  p.o_tiles = (p.cout + 31) / 32;
-  p.i_tiles = (p.cin + 31) / 32;
-  const int pairs = p.o_tiles * p.i_tiles;
-  int ks = (FMGAN_NUM_CU * 6 + pairs - 1) / pairs;     // ~3 rounds of 2 blocks per CU
-  if (ks > p.ntiles) ks = p.ntiles;
-  if (ks < 1) ks = 1;
-  p.tiles_per_split = (p.ntiles + ks - 1) / ks;
-  p.ksplit = (p.ntiles + p.tiles_per_split - 1) / p.tiles_per_split;
-}
-
 }  // namespace
 
 extern "C" long long fmgan_modconv_wgrad_mode_workspace_bytes(int batch, int cin, int cout, int h, int w, int mode) {
-  if (batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || mode < 0 || mode > 2) return 0;
-  WG64Params q{};
-  if (wgrad64_setup(q, nullptr, nullptr, nullptr, nullptr, batch, cin, cout, h, w, mode))
-    return (long long)q.ksplit * 9 * cout * cin * (long long)sizeof(float);
-  if (mode != 0 || w < 16) return 0;
-  WGParams p{};
-  p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
-  wgrad_plan(p);
-  return (long long)p.ksplit * 9 * cout * cin * (long long)sizeof(float);
+  if (wgrad_sizes(batch, cin, cout, h, w, mode) != FMGAN_OK) return 0;
+  const WGPlan pl = wgrad_plan(batch, cin, cout, h, w, mode);
+  return pl.family ? wgrad_workspace(pl) : 0;
 }
 
 extern "C" long long fmgan_modconv_wgrad_workspace_bytes(int batch, int cin, int cout, int h, int w) {
   return fmgan_modconv_wgrad_mode_workspace_bytes(batch, cin, cout, h, w, 0);
 }
 
+extern "C" int fmgan_modconv_wgrad_select(int batch, int cin, int cout, int h, int w, int mode, int aligned16, int* family,
+                                          int* tw, int* sp, int* ksplit, int* tiles_per_split, int* ntiles, int* vec) {
+  WGPlan pl{};
+  int st = wgrad_sizes(batch, cin, cout, h, w, mode);
+  if (st == FMGAN_OK) st = wgrad_range(batch, cin, cout, h, w, mode);
+  if (st == FMGAN_OK) {
+    pl = wgrad_plan(batch, cin, cout, h, w, mode);
+    if (!pl.family) st = FMGAN_EUNSUPPORTED;
+    else if ((long long)pl.a_tiles * pl.b_tiles * pl.ksplit > 0x7fffffffLL) st = FMGAN_EOVERFLOW;
+  }
+  const bool ok = st == FMGAN_OK;
+  if (family) *family = ok ? pl.family : 0;
+  if (tw) *tw = ok ? 1 << pl.tw_log2 : 0;
+  if (sp) *sp = ok ? pl.sp : 0;
+  if (ksplit) *ksplit = ok ? pl.ksplit : 0;
+  if (tiles_per_split) *tiles_per_split = ok ? pl.tiles_per_split : 0;
+  if (ntiles) *ntiles = ok ? pl.ntiles : 0;
+  // the 64 x 64 kernels' own `vec` predicate (its third term, a dword-aligned B, holds for every float tensor)
+  if (vec) *vec = ok && pl.family == 64 && (pl.wa & 3) == 0 && aligned16 ? 1 : 0;
+  return st;
+}
+
 extern "C" int fmgan_modconv_wgrad_mode_f32(const float* go, const float* demod, const float* x, const float* style,
                                             float* gw, int batch, int cin, int cout, int h, int w, int mode, float scale,
                                             void* workspace, long long workspace_bytes, void* stream) {
-  if (batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return FMGAN_EINVAL;
-  if (mode < 0 || mode > 2) return FMGAN_EUNSUPPORTED;
+  int st = wgrad_sizes(batch, cin, cout, h, w, mode);
+  if (st != FMGAN_OK) return st;
   if (!go || !x || !style || !gw || !workspace) return FMGAN_EINVAL;
-  // go is the largest tensor of the transposed conv: [batch, cout, 2h+1, 2w+1]
-  const long long big_hw = mode == 1 ? (long long)(2 * h + 1) * (2 * w + 1) : (long long)h * w;
-  if ((long long)batch * (cin > cout ? cin : cout) * big_hw >= (1LL << 40)) return FMGAN_EOVERFLOW;
-  if (big_hw >= (1LL << 31) || cin > (1 << 20) || cout > (1 << 20)) return FMGAN_EOVERFLOW;
+  st = wgrad_range(batch, cin, cout, h, w, mode);
+  if (st != FMGAN_OK) return st;
   hipStream_t s = (hipStream_t)stream;
-  WG64Params q{};
-  if (wgrad64_setup(q, go, demod, x, style, batch, cin, cout, h, w, mode)) {
+  const WGPlan pl = wgrad_plan(batch, cin, cout, h, w, mode);
+  if (!pl.family) return FMGAN_EUNSUPPORTED;               // narrow / tiny layers: the host keeps MIOpen's wgrad
+  if (workspace_bytes < wgrad_workspace(pl)) return FMGAN_EINVAL;
+  const long long nblk = (long long)pl.a_tiles * pl.b_tiles * pl.ksplit;
+  if (nblk > 0x7fffffffLL) return FMGAN_EOVERFLOW;
+  int fb = (cout * cin * 9 + 255) / 256;
+  if (fb > FMGAN_NUM_CU * 16) fb = FMGAN_NUM_CU * 16;
+  if (pl.family == 64) {
+    WG64Params q{};
+    if (mode == 1) { q.A = x; q.sa = style; q.B = go; q.sb = demod; }
+    else { q.A = go; q.sa = demod; q.B = x; q.sb = style; }
     q.partial = (float*)workspace;
-    if (workspace_bytes < (long long)q.ksplit * 9 * cout * cin * (long long)sizeof(float)) return FMGAN_EINVAL;
-    const long long nblk = (long long)q.a_tiles * q.b_tiles * q.ksplit;
-    if (nblk > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-    if (mode == 0) {
-      if (q.wa >= 32) wgrad64_launch<5, 1>(q, nblk, s); else wgrad64_launch<4, 1>(q, nblk, s);
+    q.batch = batch; q.ca = pl.ca; q.cb = pl.cb; q.ha = pl.ha; q.wa = pl.wa; q.hb = pl.hb; q.wb = pl.wb;
+    q.tiles_x = pl.tiles_x; q.tiles_y = pl.tiles_y; q.ntiles = pl.ntiles; q.ksplit = pl.ksplit;
+    q.tiles_per_split = pl.tiles_per_split; q.a_tiles = pl.a_tiles; q.b_tiles = pl.b_tiles;
+    if (pl.sp == 1) {
+      if (pl.tw_log2 == 5) wgrad64_launch<5, 1>(q, nblk, s); else wgrad64_launch<4, 1>(q, nblk, s);
     } else {
       wgrad64_launch<4, 2>(q, nblk, s);
     }
-    int st = fmgan_check_launch();
+    st = fmgan_check_launch();
     if (st != FMGAN_OK) return st;
-    int fb = (cout * cin * 9 + 255) / 256;
-    if (fb > FMGAN_NUM_CU * 16) fb = FMGAN_NUM_CU * 16;
     hipLaunchKernelGGL(modconv_wgrad64_finish_f32, dim3(fb), dim3(256), 0, s, (const float*)workspace, gw, cout, cin,
-                       q.ksplit, scale, mode == 1 ? 1 : 0);
+                       pl.ksplit, scale, mode == 1 ? 1 : 0);
     return fmgan_check_launch();
   }
-  if (mode != 0 || w < 16) return FMGAN_EUNSUPPORTED;   // narrow / tiny layers: the host keeps MIOpen's wgrad
   WGParams p{};
   p.go = go; p.d = demod; p.x = x; p.s = style; p.partial = (float*)workspace;
   p.batch = batch; p.cin = cin; p.cout = cout; p.h = h; p.w = w;
-  wgrad_plan(p);
-  if (workspace_bytes < (long long)p.ksplit * 9 * cout * cin * (long long)sizeof(float)) return FMGAN_EINVAL;
+  p.tw_log2 = pl.tw_log2; p.th = pl.th; p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.ntiles = pl.ntiles;
+  p.ksplit = pl.ksplit; p.tiles_per_split = pl.tiles_per_split; p.o_tiles = pl.a_tiles; p.i_tiles = pl.b_tiles;
   const int TW = 1 << p.tw_log2;
   const int patch = (p.th + 2) * (TW + 2);
   const int SB = patch + 1 + (patch & 1);
   size_t lds = sizeof(float) * (32 * 129 + 32 * (size_t)SB);
   if (lds < sizeof(float) * 4 * 32 * 33) lds = sizeof(float) * 4 * 32 * 33;
-  const long long blocks = (long long)p.o_tiles * p.i_tiles * p.ksplit;
-  if (blocks > 0x7fffffffLL) return FMGAN_EOVERFLOW;
-  hipLaunchKernelGGL(modconv_wgrad_f32, dim3((unsigned)blocks), dim3(256), lds, s, p);
-  int st = fmgan_check_launch();
+  hipLaunchKernelGGL(modconv_wgrad_f32, dim3((unsigned)nblk), dim3(256), lds, s, p);
+  st = fmgan_check_launch();
   if (st != FMGAN_OK) return st;
-  int fb = (cout * cin * 9 + 255) / 256;
-  if (fb > FMGAN_NUM_CU * 16) fb = FMGAN_NUM_CU * 16;
   hipLaunchKernelGGL(modconv_wgrad_finish_f32, dim3(fb), dim3(256), 0, s, (const float*)workspace, gw, cout, cin,
                      p.ksplit, scale);
   return fmgan_check_launch();

@@ -315,6 +315,20 @@ def modconv_wgrad(go, demod, x, style, scale, fast_only=False, mode=0):
     return gw
 
 
+def modconv_wgrad_select(batch, cin, cout, h, w, mode=0, aligned16=True):
+    """(family, TW, SP, ksplit, tiles_per_split, ntiles, vec): the kernel (family 32 or 64: its channel tile; 64 is
+    modconv_wgrad64_f32<log2 TW, SP>), the split over pixel tiles and the staging path (vec: 16-byte loads) that the library's
+    weight-gradient launch takes for this shape, from the launch's own plan — host logic, no device needed.  aligned16: the
+    unshifted operand (go; x in mode 1) is 16-byte aligned.  All zeros where the library declines the shape; raises as the
+    launch would for arguments it refuses."""
+    v = [ctypes.c_int() for _ in range(7)]
+    st = lib().fmgan_modconv_wgrad_select(int(batch), int(cin), int(cout), int(h), int(w), int(mode), int(bool(aligned16)),
+                                          *[ctypes.byref(c) for c in v])
+    served(st, 'modconv_wgrad_select')
+    family, tw, sp, ks, tps, ntiles, vec = (c.value for c in v)
+    return family, tw, sp, ks, tps, ntiles, bool(vec)
+
+
 # ----------------------------------------------------------------------------- csrc/winograd.hip
 def wino_weight(wt):
     """fp32 MFMA layout wt [cin, 9, cout] (scaled) -> Winograd F(2x2,3x3) weight U [16, cout, cin]."""

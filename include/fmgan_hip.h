@@ -778,6 +778,23 @@ int fmgan_modconv_wgrad_mode_f32(const float *go, const float *demod, const floa
 int fmgan_modconv_wgrad_f32(const float *go, const float *demod, const float *x, const float *style,
                             float *gw, int batch, int cin, int cout, int h, int w, float scale,
                             void *workspace, long long workspace_bytes, void *stream);
+/*
+ * Which kernel, which tile, which split (pure host logic, no launch — as fmgan_modconv2d_select): the plan of
+ * fmgan_modconv_wgrad_mode_f32 for these arguments, made by the one plan function that the launch and
+ * fmgan_modconv_wgrad_mode_workspace_bytes call too.  aligned16: the unshifted operand (go; x in mode 1) starts on a
+ * 16-byte boundary.
+ *   *family  0 = declined (FMGAN_EUNSUPPORTED is returned), 32 = the 32 x 32-tile kernel, 64 = a 64 x 64-tile kernel
+ *   *tw, *sp pixels per tile row (16 / 32) and the stride of the shifted operand (1; 2 in modes 1 and 2): the 64 x 64
+ *            kernel launched is modconv_wgrad64_f32<log2 tw, sp>
+ *   *ntiles  pixel tiles over the batch;  *tiles_per_split of them per block, in *ksplit splits (the last one may be
+ *            shorter); the workspace is ksplit * 9 * cout * cin floats
+ *   *vec     1 when the 64 x 64 kernel stages its operands with 16-byte loads (row length of the unshifted operand a
+ *            multiple of 4 and aligned16), 0 for its guarded scalar fill and for the 32 x 32 kernel, which has one path
+ * Any of the seven may be NULL.  Returns the status the launch returns before it launches (its pointer and workspace
+ * checks left out); on any status but FMGAN_OK all seven are 0.
+ */
+int fmgan_modconv_wgrad_select(int batch, int cin, int cout, int h, int w, int mode, int aligned16, int *family,
+                               int *tw, int *sp, int *ksplit, int *tiles_per_split, int *ntiles, int *vec);
 
 /*
  * ToRGB (stylegan2.py:389-404): 1x1 modulated conv without demodulation + bias + optional skip:

@@ -63,8 +63,8 @@ def equal_linear(x, weight, bias, lr_mul=1.0, activation=False):
 
 
 def modulated_conv2d(x, w_latent, weight, mod_weight, mod_bias, demodulate=True, upsample=False,
-                     blur_kernel=None):
-    """ModulatedConv2d.forward, stylegan2.py:250-298 (plain and upsample branches; weight-modulated,
+                     blur_kernel=None, downsample=False):
+    """ModulatedConv2d.forward, stylegan2.py:250-298 (plain, upsample and downsample branches; weight-modulated,
     groups=batch, exactly as the reference)."""
     batch, in_channel, height, width = x.shape
     _, out_channel, _, k, _ = weight.shape
@@ -84,6 +84,12 @@ def modulated_conv2d(x, w_latent, weight, mod_weight, mod_bias, demodulate=True,
         kern = make_kernel(blur_kernel).to(x) * 4
         return upfirdn2d(out, kern, pad=((p + 1) // 2 + 1, p // 2 + 1))        # :279
     w = w.view(batch * out_channel, in_channel, k, k)
+    if downsample:
+        p = (len(blur_kernel) - 2) + (k - 1)                                   # Blur(pad=(pad0,pad1)), :224-230
+        x = upfirdn2d(x, make_kernel(blur_kernel).to(x), pad=((p + 1) // 2, p // 2))          # :282
+        out = F.conv2d(x.reshape(1, batch * in_channel, x.shape[2], x.shape[3]), w, padding=0, stride=2,
+                       groups=batch)                                           # :285
+        return out.view(batch, out_channel, out.shape[2], out.shape[3])
     out = F.conv2d(x.reshape(1, batch * in_channel, height, width), w, padding=k // 2, groups=batch)  # :291
     return out.view(batch, out_channel, out.shape[2], out.shape[3])
 

@@ -532,6 +532,47 @@ def test_modconv_select_and_tiles_are_host_logic():
     assert any(_native.modconv2d_select(b, 512, 512, 8, 8, 0)[4] > 1 for b in (1, 8))
 
 
+def test_modconv_wgrad_select_is_host_logic_and_sizes_the_workspace():
+    """fmgan_modconv_wgrad_select answers without a device, returns the launch's status for arguments the launch refuses,
+    and names the split that fmgan_modconv_wgrad_mode_workspace_bytes sizes the workspace for — on served and on declined
+    shapes alike (the three entry points call one plan function)."""
+    from op import _native
+    L = lib()
+
+    def status(*args):
+        return L.fmgan_modconv_wgrad_select(*args, None, None, None, None, None, None, None)
+    assert status(1, 64, 64, 16, 16, 3, 1) == -2                     # as fmgan_modconv_wgrad_mode_f32: unknown mode
+    assert status(0, 64, 64, 16, 16, 0, 1) == -1 and status(1, 64, 0, 16, 16, 0, 1) == -1
+    assert status(1, 8, 8, 46341, 46341, 0, 1) == -4                 # 32-bit pixel indices
+    assert status(1, (1 << 20) + 1, 8, 32, 32, 0, 1) == -4
+    assert status(1, 64, 64, 16, 15, 0, 1) == -2 and status(1, 64, 64, 16, 16, 0, 1) == 0
+    with pytest.raises(RuntimeError):
+        _native.modconv_wgrad_select(1, 8, 8, 46341, 46341)
+    assert _native.modconv_wgrad_select(1, 64, 64, 16, 16, 3) == (0, 0, 0, 0, 0, 0, False)
+    seen = set()
+    for mode in (0, 1, 2):
+        for b in (1, 2, 8):
+            for cin, cout in ((3, 33), (47, 47), (48, 47), (47, 48), (48, 48), (64, 32), (100, 50), (512, 512), (512, 40)):
+                for h, w in ((1, 16), (2, 15), (4, 16), (5, 33), (9, 31), (16, 32), (18, 32), (33, 35), (64, 64), (6, 36)):
+                    family, tw, sp, ks, tps, ntiles, vec = sel = _native.modconv_wgrad_select(b, cin, cout, h, w, mode)
+                    need = L.fmgan_modconv_wgrad_mode_workspace_bytes(b, cin, cout, h, w, mode)
+                    assert need == ks * 9 * cout * cin * 4, (mode, b, cin, cout, h, w, sel, need)
+                    wa = w if mode < 2 else (w - 3) // 2 + 1
+                    if family == 0:
+                        assert sel == (0, 0, 0, 0, 0, 0, False)
+                        assert wa < 16 or (mode == 2 and h < 3) or (mode > 0 and min(cin, cout) < 48), (mode, cin, cout, h, w)
+                        continue
+                    assert family == (64 if min(cin, cout) >= 48 else 32) and (family == 64 or mode == 0)
+                    assert sp == (1 if mode == 0 else 2) and tw == (32 if mode == 0 and wa >= 32 else 16)
+                    assert ks >= 1 and (ks - 1) * tps < ntiles <= ks * tps       # no empty split; the last may be shorter
+                    assert vec == (family == 64 and wa % 4 == 0)
+                    unaligned = _native.modconv_wgrad_select(b, cin, cout, h, w, mode, aligned16=False)
+                    assert unaligned == sel[:6] + (False,)                       # alignment moves the staging path only
+                    seen.add((family, tw, sp, vec))
+    assert seen == {(32, 16, 1, False), (32, 32, 1, False), (64, 32, 1, True), (64, 32, 1, False), (64, 16, 1, True),
+                    (64, 16, 1, False), (64, 16, 2, True), (64, 16, 2, False)}
+
+
 def test_modconv_select_headline_forward_dispatch():
     """The documented dispatch of the batch-8 1024^2 forward (csrc/modconv_fwd.hip, the comment block above MC_TILES and
     launch_any; network widths 512 / 256 / 128 / 64 / 32 at 64^2 .. 1024^2), derived from those comments, not recorded:

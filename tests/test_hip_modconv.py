@@ -426,6 +426,68 @@ def test_torgb_kernel_vs_c_oracle_ragged():
         np.testing.assert_allclose(y.cpu().numpy(), ref, **_tol(ref))
 
 
+# ---------------------------------------------------------------------------------------- ToRGB above 128^2, directly
+# fmgan_torgb_f32 (csrc/torgb.hip) has three kernels: torgb_small_f32 up to 128 x 128 pixels (the shapes above), and beyond
+# that the grid-stride kernel torgb_f32<4> (16-byte loads: H*W a multiple of 4 and in / out / skip 16-byte aligned) or
+# torgb_f32<1>.  Its grid is capped at ceil(16 * compute units / batch) blocks of 256 pixel groups per sample.  The C oracle
+# (oracle/fmgan_oracle.c, oracle_to_rgb_f32) sums the fp32 products in double.
+def _torgb_inputs(cfg, cout=3):
+    b, cin, h, w = cfg
+    tag = f'rgbl/{cfg}/{cout}'
+    return (synth.tensor(tag + '/x', (b, cin, h, w)), synth.tensor(tag + '/w', (cout, cin)),
+            synth.tensor(tag + '/s', (b, cin), shift=1.0, scale=0.5), synth.tensor(tag + '/b', (cout,)),
+            synth.tensor(tag + '/k', (b, cout, h, w)))
+
+
+def _torgb_vs_c_oracle(cfg, cout=3, with_bias=True, with_skip=True):
+    from op import _native
+    from oracle import c_oracle
+    x, wgt, s, bias, skip = _torgb_inputs(cfg, cout)
+    bias, skip = bias if with_bias else None, skip if with_skip else None
+    ref = c_oracle.to_rgb(x.numpy(), wgt.numpy(), s.numpy(), None if bias is None else bias.numpy(),
+                          None if skip is None else skip.numpy())
+    d = dev()
+    args = [t if t is None else t.to(d) for t in (x, wgt, s, bias, skip)]
+    assert cfg[2] * cfg[3] > 128 * 128 and all(t is None or t.data_ptr() % 16 == 0 for t in args)
+    y = _native.torgb(*args, 1.0 / np.sqrt(cfg[1]))
+    assert tuple(y.shape) == (cfg[0], cout, cfg[2], cfg[3]) and y.data_ptr() % 16 == 0
+    np.testing.assert_allclose(y.cpu().numpy(), ref, **_tol(ref))
+    return y, args
+
+
+@pytest.mark.parametrize('cout,with_bias,with_skip', [(3, True, True), (1, True, True), (2, True, True), (4, True, True),
+                                                      (3, False, True), (3, True, False), (3, False, False)])
+def test_torgb_large_image_scalar_kernel_vs_c_oracle(cout, with_bias, with_skip):
+    """129 x 129: above 128^2 and H*W = 16641 is no multiple of 4 -> torgb_f32<1>; every output-channel count, with and
+    without bias and skip."""
+    cfg = (2, 5, 129, 129)
+    assert cfg[2] * cfg[3] % 4 != 0
+    _torgb_vs_c_oracle(cfg, cout, with_bias, with_skip)
+
+
+def test_torgb_large_image_vector_kernel_vs_c_oracle_and_its_misaligned_fallback():
+    """132 x 128: H*W a multiple of 4, aligned tensors -> torgb_f32<4>.  The same call with `skip` one float into a larger
+    buffer is the other half of the predicate -> torgb_f32<1>: the same fused multiply-adds in the same channel order, the
+    same two rounded adds, so the same bits."""
+    from op import _native
+    from gpumem import misaligned
+    cfg = (2, 5, 132, 128)
+    assert cfg[2] * cfg[3] % 4 == 0
+    y, (x, wgt, s, bias, skip) = _torgb_vs_c_oracle(cfg)
+    off = misaligned(skip)
+    assert off.data_ptr() % 16 == 4 and off.is_contiguous()
+    assert torch.equal(_native.torgb(x, wgt, s, bias, off, 1.0 / np.sqrt(cfg[1])), y)
+
+
+def test_torgb_large_image_second_trip_of_the_grid_stride_loop_vs_c_oracle():
+    """Batch 64 at 129 x 129: the grid cap ceil(16 * CUs / 64) (64 blocks on 256 compute units) is below the
+    ceil(16641 / 256) = 66 blocks that would give each thread one pixel, so the first threads take a second trip."""
+    cfg = (64, 2, 129, 129)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert -(-16 * cus // cfg[0]) < -(-cfg[2] * cfg[3] // 256), cus
+    _torgb_vs_c_oracle(cfg)
+
+
 def test_weight_prep_layouts():
     from op import _native
     w = synth.tensor('wprep/w', (20, 12, 3, 3))
@@ -464,32 +526,98 @@ def test_first_order_backward_on_hip_vs_oracle(cfg, monkeypatch):
     """loss.backward() without create_graph: data gradient on the MFMA kernel (swapped-role weight layouts, stride-2
     mode for the transposed conv), weight gradient + demodulation chain rule; vs float64 autograd through the CPU
     oracle's weight-modulated grouped conv (the reference's formulation)."""
+    # Every configuration has cin <= 40: ModulatedConv2dFunction.backward asks for the weight gradient with fast_only=True,
+    # which declines fewer than 48 channels on either side, so all nine take MIOpen's weight gradient whatever HIP_WGRAD says
+    # (the backward on this repo's weight-gradient kernel: test_first_order_backward_on_own_wgrad_kernel_vs_oracle below).
+    # monkeypatch restores the product default afterwards (round 2 assigned the module attribute and left it at 0 for
+    # every later test of the process)
+    check_first_order_backward(cfg, 1 if cfg[3] % 8 == 0 else 0, monkeypatch)
+
+
+def check_first_order_backward(cfg, hip_wgrad, monkeypatch, down=False):
+    """Body of the two first-order backward tests; returns the recorder of the launch brackets begun during backward."""
     import stylegan2
     from oracle import torch_oracle as T
     from op import modconv as _mc
     b, cin, cout, h, up, demod = cfg
-    # exercise both weight-gradient providers (MFMA kernel / MIOpen); monkeypatch restores the product default afterwards
-    # (round 2 assigned the module attribute and left it at 0 for every later test of the process)
-    monkeypatch.setattr(_mc, 'HIP_WGRAD', 1 if h % 8 == 0 else 0)
-    m = stylegan2.ModulatedConv2d(cin, cout, 3, 512, demodulate=demod, upsample=up)
+    monkeypatch.setattr(_mc, 'HIP_WGRAD', hip_wgrad)
+    m = stylegan2.ModulatedConv2d(cin, cout, 3, 512, demodulate=demod, upsample=up, downsample=down)
     m.load_state_dict(synth.state_dict('generator', m.state_dict(), seed=21))
     sd = {k: v.detach().double() for k, v in m.state_dict().items()}
     m = m.to(dev())
-    x = synth.tensor(f'bw/{cfg}/x', (b, cin, h, h))
-    w = synth.tensor(f'bw/{cfg}/w', (b, 512))
+    tag = f'bw/{cfg}/down' if down else f'bw/{cfg}'
+    x = synth.tensor(tag + '/x', (b, cin, h, h))
+    w = synth.tensor(tag + '/w', (b, 512))
     xo, wo = x.double().requires_grad_(True), w.double().requires_grad_(True)
     wt_o, mw_o, mb_o = (sd[k].clone().requires_grad_(True) for k in ('weight', 'modulation.weight', 'modulation.bias'))
-    yo = T.modulated_conv2d(xo, wo, wt_o, mw_o, mb_o, demod, up, [1, 3, 3, 1])
-    go = synth.tensor(f'bw/{cfg}/go', yo.shape)
+    yo = T.modulated_conv2d(xo, wo, wt_o, mw_o, mb_o, demod, up, [1, 3, 3, 1], downsample=down)
+    go = synth.tensor(tag + '/go', yo.shape)
     ref = torch.autograd.grad(yo, (xo, wo, wt_o, mw_o, mb_o), go.double())
     xd, wd = x.to(dev()).requires_grad_(True), w.to(dev()).requires_grad_(True)
     yd = m(xd, wd)
-    yd.backward(go.to(dev()))                     # no graph requested -> HIP first-order path
+    with launches.observed() as obs:
+        yd.backward(go.to(dev()))                 # no graph requested -> HIP first-order path
     got = (xd.grad, wd.grad, m.weight.grad, m.modulation.weight.grad, m.modulation.bias.grad)
     for name, g, r in zip(('x', 'latent', 'weight', 'mod.weight', 'mod.bias'), got, ref):
         r = r.numpy()
         np.testing.assert_allclose(g.cpu().numpy(), r, atol=2e-4 * max(1e-6, float(np.abs(r).max())), rtol=2e-4,
                                    err_msg=name)
+    return obs
+
+
+@pytest.mark.parametrize('hip_wgrad', ['own', 0], ids=['own_kernel', 'miopen'])
+@pytest.mark.parametrize('cfg,down,setting,bracket,plan', [
+    # (b, cin, cout, h, upsample, demodulate), downsample, the HIP_WGRAD that puts the layer on this repo's kernel, the
+    # launch bracket (b, cin, cout, conv input h, w, mode) that must then be begun, and its (family, TW, SP, vec)
+    ((2, 48, 64, 16, False, True), False, 1, (2, 48, 64, 16, 16, 0), (64, 16, 1, True)),     # d and scale ride in the kernel
+    ((1, 64, 48, 16, False, False), False, 1, (1, 64, 48, 16, 16, 0), (64, 16, 1, True)),    # demodulate=False: d = None
+    ((2, 50, 70, 17, False, True), False, 1, (2, 50, 70, 17, 17, 0), (64, 16, 1, False)),    # ragged channels, scalar staging
+    ((1, 48, 48, 16, True, True), False, 2, (1, 48, 48, 16, 16, 1), (64, 16, 2, True)),      # transposed conv, go 33 x 33
+    # downsample: the 4-tap blur with pad (2, 2) makes the 32 x 32 input 33 x 33, the stride-2 conv's input; its backward
+    # is the DenseConv family's (mode 2 takes the composite form), whose weight gradient passes demod = None, scale 1
+    ((1, 48, 48, 32, False, True), True, 2, (1, 48, 48, 33, 33, 2), (64, 16, 2, True)),
+], ids=['plain_demod', 'plain_no_demod', 'plain_ragged', 'upsample', 'downsample'])
+def test_first_order_backward_on_own_wgrad_kernel_vs_oracle(cfg, down, setting, bracket, plan, hip_wgrad, monkeypatch):
+    """The body of test_first_order_backward_on_hip_vs_oracle at >= 48 channels on both sides, where the module's backward
+    takes this repo's weight-gradient kernel: the demodulation and the scale riding in the kernel (or d = None), the
+    demodulation's chain-rule term added on top, modes 1 and 2 under HIP_WGRAD = 2.  The bracket of the expected launch must
+    have been begun, on the kernel the library's own plan names; under HIP_WGRAD = 0 (MIOpen's weight gradient, same
+    reference, same bound) none may be."""
+    from op import _native
+    b, cin, cout, h, w, mode = bracket
+    family, tw, sp, _ks, _tps, _ntiles, vec = _native.modconv_wgrad_select(b, cin, cout, h, w, mode)
+    assert (family, tw, sp, vec) == plan
+    obs = check_first_order_backward(cfg, setting if hip_wgrad == 'own' else 0, monkeypatch, down=down)
+    assert obs.infos('modconv_wgrad') == ([bracket] if hip_wgrad == 'own' else []), obs.seen
+
+
+def test_dense_conv_wgrad_under_create_graph_runs_own_kernel_without_demod(monkeypatch):
+    """DenseConvWgrad (the weight gradient of the create_graph=True path) at cin = cout = 48: op.modconv._wgrad hands the
+    kernel demod = None, a style of ones and scale 1.  First order against float64 autograd of F.conv2d on the CPU at the
+    weight-gradient kernels' bound (tests/test_hip_modconv_wgrad.py), and one derivative further — through the graph the
+    Function recorded — at test_dense_conv_family_differentiates_into_itself's bound for that order."""
+    from op import _native, modconv
+    import torch.nn.functional as F
+    monkeypatch.setattr(modconv, 'HIP_WGRAD', 1)
+    b, cin, cout, h, w = 2, 48, 48, 8, 16
+    assert _native.modconv_wgrad_select(b, cin, cout, h, w, 0)[:3] == (64, 16, 1)
+    u = synth.tensor('dcw/u', (b, cin, h, w))
+    wt = synth.tensor('dcw/w', (cout, cin, 3, 3), scale=0.3)
+    g1 = synth.tensor('dcw/g1', (b, cout, h, w))
+
+    def chain(conv, uu, ww, g):
+        gu, gw = torch.autograd.grad(conv(uu, ww), (uu, ww), g, create_graph=True)
+        hu, = torch.autograd.grad(gw.pow(2).mean(), uu)                  # d/du of G_0(u, g): a data gradient with weight dL/dgw
+        return gw.detach().cpu().double(), hu.cpu().double()
+
+    gw_o, hu_o = chain(lambda a, c: F.conv2d(a, c, padding=1), u.double().requires_grad_(True),
+                       wt.double().requires_grad_(True), g1.double())
+    with launches.observed() as obs:
+        gw_d, hu_d = chain(lambda a, c: modconv.DenseConv.apply(a, c, 0), u.to(dev()).requires_grad_(True),
+                           wt.to(dev()).requires_grad_(True), g1.to(dev()))
+    assert obs.infos('modconv_wgrad') == [(b, cin, cout, h, w, 0)], obs.seen
+    torch.testing.assert_close(gw_d, gw_o, atol=2e-5 * float(gw_o.abs().max()), rtol=2e-5)
+    torch.testing.assert_close(hu_d, hu_o, atol=1e-4 * float(hu_o.abs().max()), rtol=1e-3)
 
 
 @pytest.mark.parametrize('shape', [

@@ -7,7 +7,8 @@ import torch
 import launches
 import synth
 
-# dir(op._native) of the last one-file version: every name without a leading underscore, the imported modules left out.
+# dir(op._native) of the last one-file version: every name without a leading underscore, the imported modules left out;
+# plus the wrappers added since (modconv_wgrad_select).
 PUBLIC_NAMES = (
     'BANK_GATHER_BANKS', 'BANK_GATHER_GROUPS', 'BF16', 'BLUR_PATHS', 'EMA_CHUNK', 'F16', 'F32', 'F64', 'FMGAN_EINVAL',
     'FMGAN_EUNSUPPORTED', 'FMGAN_OK', 'HEATMAP_SIZE', 'INCEPTION_SIZE', 'LIB_PATH', 'LOSS_ROW_COLUMNS', 'LPIPS_SIZE',
@@ -23,7 +24,7 @@ PUBLIC_NAMES = (
     'lbfgs_update', 'lib', 'loss_row', 'lpips_distance', 'lpips_distance_backward', 'lpips_pair_input', 'modconv2d',
     'modconv2d_rgb', 'modconv2d_rgb_fusable', 'modconv2d_select', 'modconv2d_tiles', 'modconv2d_winograd',
     'modconv_demod', 'modconv_precision', 'modconv_weight_prep', 'modconv_weight_to_bf16', 'modconv_weight_to_bf16x3',
-    'modconv_wgrad', 'modconv_wsq', 'nhwc_dense', 'noise_bias_act', 'on_device', 'prelu_backward', 'projection_loss_bwd',
+    'modconv_wgrad', 'modconv_wgrad_select', 'modconv_wsq', 'nhwc_dense', 'noise_bias_act', 'on_device', 'prelu_backward', 'projection_loss_bwd',
     'projection_loss_fwd', 'ptr', 'render_mask', 'require_f32_gpu', 'require_gpu', 'resize_images', 'resize_output_size',
     'resize_plan', 'se_gate', 'se_pool', 'served', 'set_observer', 'style_bank', 'tensor_to_images', 'tiles_to_canvas',
     'torgb', 'torgb_backward', 'upfirdn2d', 'upfirdn2d16', 'upfirdn2d_out_size', 'upfirdn2d_strided', 'wino_input',
@@ -38,7 +39,7 @@ FAMILIES = ('activation', 'conv', 'encoder', 'loss', 'evaluation', 'image', 'opt
 def test_every_public_name_is_a_package_attribute():
     import os
     from op import _native
-    assert len(set(PUBLIC_NAMES)) == len(PUBLIC_NAMES) == 117
+    assert len(set(PUBLIC_NAMES)) == len(PUBLIC_NAMES) == 118
     missing = [n for n in PUBLIC_NAMES if not hasattr(_native, n)]
     assert not missing, missing
     for name in PUBLIC_NAMES:

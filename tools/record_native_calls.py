@@ -332,6 +332,8 @@ def convolutions(d):
     host('modconv2d_select', 8, 32, 32, 1024, 1024, 0, rgb=True)
     host('modconv2d_rgb_fusable', 8, 32, 32, 1024, 1024)
     host('modconv2d_tiles')
+    host('modconv_wgrad_select', 1, 48, 200, 9, 16, 0)
+    host('modconv_wgrad_select', 2, 64, 64, 16, 16, 1, aligned16=False)
 
 
 def live_weights(d):
