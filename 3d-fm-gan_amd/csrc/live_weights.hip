@@ -11,10 +11,13 @@
 //   kind 1  wt[i][t][o] = scale * W[o][i][t]   and   wsq[o][i] = sum_t W[o][i][t]^2
 //           (MFMA A-operand layout of ModulatedConv2d + the demodulation sums; same arithmetic, same order as
 //           modconv_weight_prep_f32 / modconv_wsq_f32 in modconv_prep.hip -> identical bits)
+//           and, for the wide plain 3x3 layers that can run in Winograd form, U[xi][o][i] = (G (scale W) Gt)[xi]
+//           (wino_weight_f32's arithmetic on the same products: the bits of fmgan_wino_weight_f32(wt))
 // Kind 1 is an LDS-tiled transpose: a block owns 64 output channels x 16 input channels x ktaps; reads are runs of
 // 16*ktaps contiguous floats per output channel (576 B for 3x3), writes are runs of 64 contiguous floats (256 B).
 // (32 x 8 tiles — 288-byte reads, 128-byte writes — ran the refresh of Generator(1024) at ~0.8 TB/s.)
 #include "common.h"
+#include "winograd_weight.h"
 
 namespace {
 
@@ -65,6 +68,22 @@ __global__ __launch_bounds__(256) void live_weights_f32(const fmgan_refresh_entr
         float q = 0.f;
         for (int t = 0; t < kt; ++t) { const float w = tile[o][i * kt + t]; q = fmaf(w, w, q); }
         wsq[(long long)(o0 + o) * e.cin + i0 + i] = q;
+      }
+    }
+  }
+  float* __restrict__ u = (float*)e.dst3;
+  if (u && kt == 9) {
+    // U = G g Gt of g = scale * W, the product and the transform being wino_weight_f32's own (of wt): the same bits.
+    // i fastest over the lanes: runs of 16 floats of U[xi][o][.], tile rows read at a stride of 9 floats (odd: no conflict)
+    for (int idx = threadIdx.x; idx < LW_TO * LW_TI; idx += 256) {
+      const int o = idx / LW_TI, i = idx % LW_TI;
+      if (o0 + o < e.cout && i < i_n) {
+        float g[3][3], uu[16];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = e.scale * tile[o][i * 9 + t];
+        wino_weight_transform(g, uu);
+#pragma unroll
+        for (int xi = 0; xi < 16; ++xi) u[((long long)xi * e.cout + o0 + o) * e.cin + i0 + i] = uu[xi];
       }
     }
   }

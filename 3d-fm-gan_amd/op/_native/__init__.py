@@ -21,7 +21,7 @@ from .conv import (  # noqa: F401
     current_modconv_precision, modconv2d, modconv2d_rgb_fusable, modconv2d_select, modconv2d_tiles, modconv2d_rgb,
     modconv_weight_to_bf16, modconv_weight_to_bf16x3, conv_weight_to_bf16x3, conv3x3s2_bf16x3_supported,
     conv3x3s2_bf16x3, conv3x3_bf16x3_supported, conv3x3_bf16x3, C3_EPILOGUES, conv3x3_tail_bf16x3_select,
-    conv3x3_tail_bf16x3, modconv_wgrad, modconv_wgrad_select, wino_weight,
+    conv3x3_tail_bf16x3, modconv_wgrad, modconv_wgrad_select, wino_select, wino_weight,
     wino_input, wino_output, modconv2d_winograd, torgb,
     torgb_backward, equal_linear, style_bank, style_bank_concat, demod_bank)
 from .encoder import bn_prelu, se_pool, se_gate, ir_tail  # noqa: F401

@@ -330,6 +330,18 @@ def modconv_wgrad_select(batch, cin, cout, h, w, mode=0, aligned16=True):
 
 
 # ----------------------------------------------------------------------------- csrc/winograd.hip
+def wino_select(transform, batch, c, h, w, *tensors):
+    """Which kernel wino_input (transform 'input') or wino_output ('output', c = cout) takes for these sizes: 'strip' (one
+    thread per four horizontally adjacent tiles, 16-byte accesses) or 'tile' (one thread per tile) — the launch's own rule,
+    host logic.  tensors: what the launch reads through 16-byte accesses (x; M and the noise plane) — None entries are
+    skipped; the transform's own V / out are fresh allocations and always aligned.  Raises as the launch would for sizes it
+    refuses."""
+    aligned = all(t.data_ptr() % 16 == 0 for t in tensors if t is not None)
+    k = lib().fmgan_wino_select(('input', 'output').index(transform), int(batch), int(c), int(h), int(w), int(aligned))
+    check(min(k, 0), 'wino_select')
+    return ('tile', 'strip')[k]
+
+
 def wino_weight(wt):
     """fp32 MFMA layout wt [cin, 9, cout] (scaled) -> Winograd F(2x2,3x3) weight U [16, cout, cin]."""
     cin, taps, cout = wt.shape

@@ -121,6 +121,7 @@ def lib():
     _sig(L.fmgan_modconv_wgrad_mode_f32, [vp] * 5 + [i] * 6 + [f, vp, ll, vp])
     _sig(L.fmgan_modconv_wgrad_select, [i] * 7 + [ctypes.POINTER(i)] * 7)
     # csrc/winograd.hip
+    _sig(L.fmgan_wino_select, [i] * 6)
     _sig(L.fmgan_wino_weight_f32, [vp, vp, i, i, vp])
     _sig(L.fmgan_wino_input_f32, [vp] * 3 + [i] * 4 + [vp])
     _sig(L.fmgan_wino_output_f32, [vp] * 6 + [i] * 6 + [f, f, vp])

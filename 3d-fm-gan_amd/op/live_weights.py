@@ -18,8 +18,9 @@ import torch
 
 from . import _native
 
-_ENTRY = np.dtype([('src', '<u8'), ('dst', '<u8'), ('dst2', '<u8'), ('n', '<i8'), ('kind', '<i4'), ('cout', '<i4'),
-                   ('cin', '<i4'), ('ktaps', '<i4'), ('scale', '<f4'), ('block_begin', '<u4')])
+_ENTRY = np.dtype([('src', '<u8'), ('dst', '<u8'), ('dst2', '<u8'), ('dst3', '<u8'), ('n', '<i8'), ('kind', '<i4'),
+                   ('cout', '<i4'), ('cin', '<i4'), ('ktaps', '<i4'), ('scale', '<f4'), ('block_begin', '<u4')])
+WINOGRAD_MIN_CHANNELS = 256     # stylegan2.winograd_pays: cin, cout >= 256
 
 
 def _check_layout():
@@ -60,17 +61,18 @@ class LiveWeights:
         return lin, conv
 
     def _build(self, lin, conv, key):
+        from stylegan2 import WINOGRAD
         _check_layout()
         rows, bufs = [], []
         blocks = 0
 
-        def add(kind, src, dst, dst2, cout, cin, ktaps, scale, n):
+        def add(kind, src, dst, dst2, cout, cin, ktaps, scale, n, dst3=None):
             nonlocal blocks
             nb = _native.lib().fmgan_weight_refresh_blocks(kind, cout, cin, ktaps, n)
             if nb <= 0:
                 raise RuntimeError('live_weights: unsupported entry')
-            rows.append((src.data_ptr(), dst.data_ptr(), 0 if dst2 is None else dst2.data_ptr(), n, kind, cout, cin,
-                         ktaps, scale, blocks))
+            rows.append((src.data_ptr(), dst.data_ptr(), 0 if dst2 is None else dst2.data_ptr(),
+                         0 if dst3 is None else dst3.data_ptr(), n, kind, cout, cin, ktaps, scale, blocks))
             blocks += nb
 
         for m in lin:
@@ -88,9 +90,15 @@ class LiveWeights:
             cout, cin, k, _ = w.shape[-4:]
             wt = torch.empty((cin, k * k, cout), dtype=torch.float32, device=w.device)
             wsq = torch.empty((cout, cin), dtype=torch.float32, device=w.device)
-            add(1, w, wt, wsq, cout, cin, k * k, m.scale, 0)
+            # the Winograd weight of every layer stylegan2.winograd_pays can name at some batch and plane (plain, wide);
+            # a layer without one derives it per call (_native.wino_weight)
+            u = None
+            if WINOGRAD and k == 3 and not (m.upsample or m.downsample) and min(cin, cout) >= WINOGRAD_MIN_CHANNELS:
+                u = torch.empty((16, cout, cin), dtype=torch.float32, device=w.device)
+            add(1, w, wt, wsq, cout, cin, k * k, m.scale, 0, u)
             m._live = (self, wt, wsq)
-            bufs += [wt, wsq]
+            m._live_u = u
+            bufs += [wt, wsq, u]
         table = np.array(rows, dtype=_ENTRY)
         dev = (lin[0].weight if lin else conv[0].weight).device
         self._table = torch.from_numpy(table.view(np.uint8).copy()).to(dev)
@@ -138,6 +146,12 @@ def live(module):
     if lv is not None and lv[0].active and not torch.is_grad_enabled():
         return lv[1], lv[2]
     return None
+
+
+def live_u(module):
+    """The Winograd weight U [16, cout, cin] of a ModulatedConv2d from this forward's refresh, under live()'s condition; None
+    outside a live forward and for a layer the table keeps no U for (the caller then derives it with _native.wino_weight)."""
+    return getattr(module, '_live_u', None) if live(module) is not None else None
 
 
 _SPLIT = weakref.WeakKeyDictionary()      # Conv2d module -> (key, image, built event, stream); not copied with the module

@@ -20,7 +20,7 @@ from torch.nn import functional as F
 from op import FusedLeakyReLU, fused_leaky_relu, upfirdn2d
 from op import _native, conv_grad, modconv, placement
 from op._native import amp_fwd as _amp_fwd, amp_bwd as _amp_bwd
-from op.live_weights import LiveWeights, live
+from op.live_weights import LiveWeights, live, live_u
 from op.style_bank import Modulation, StyleBank, comod_column, concat_column, sliced_columns
 from Util.streams import side_streams, run_on, overlap_ok
 
@@ -202,6 +202,7 @@ class ModulatedConv2d(nn.Module):
         self.modulation = EqualLinear(style_dim, in_channel, bias_init=1)
         self.demodulate = demodulate
         self._live = None     # set by op.live_weights.LiveWeights of the enclosing network
+        self._live_u = None   # likewise: the Winograd weight, for the wide plain layers only
 
     def __repr__(self):
         return (f'{self.__class__.__name__}({self.in_channel}, {self.out_channel}, {self.kernel_size}, '
@@ -222,6 +223,11 @@ class ModulatedConv2d(nn.Module):
             return lv[1]
         with torch.no_grad():
             return _native.modconv_wsq(self.weight.detach())
+
+    def wino_weight(self):
+        """U = G (scale * weight) Gt [16, cout, cin]: this forward's refreshed table entry, or None (modconv2d_winograd
+        then derives it from mfma_weight() on the spot)."""
+        return live_u(self)
 
     def styles(self, style):
         return self.modulation(style)
@@ -412,7 +418,7 @@ class StyledConv(nn.Module):
             # direct kernel is already at 0.84-0.88 of the fp32 matrix peak on these layers
             out = _native.modconv2d_winograd(input, conv.mfma_weight(), s, demod, noise=noise,
                                              noise_weight=self.noise.weight, bias=act.bias, fuse_act=True,
-                                             alpha=act.negative_slope, act_scale=act.scale)
+                                             alpha=act.negative_slope, act_scale=act.scale, u=conv.wino_weight())
         else:
             out = _native.modconv2d(input, conv.mfma_weight(), s, demod, 0, noise=noise,
                                     noise_weight=self.noise.weight, bias=act.bias, fuse_act=True,

@@ -478,7 +478,16 @@ int fmgan_modconv_demod_f32(const float *weight, const float *style, float *demo
  *   fmgan_wino_input_f32:   x [B,C,H,W], style [B,C] -> V [16, C, B*T]   (column b*T + ty*(W/2) + tx; modulated, zero padded)
  *   fmgan_wino_output_f32:  M [16, cout, B*T] -> out [B,cout,H,W] contiguous = epilogue(demod * At M A); demod / noise /
  *                           bias may be NULL; epilogue as fmgan_modconv2d_f32 with fuse_act
+ * The two activation transforms each have two kernels that give the same bits: one thread per strip of four horizontally
+ * adjacent tiles with 16-byte accesses throughout, taken where (W/2) % 4 == 0 and x and V (M, out and the noise plane) start
+ * on 16-byte boundaries — by the output transform only on rows of at least 32 floats —, and one thread per tile for
+ * everything else.
+ *   fmgan_wino_select:      which of them a launch with these sizes takes (pure host logic, no launch): 1 = strips, 0 = one
+ *                           tile per thread; output: 0 = fmgan_wino_input_f32, 1 = fmgan_wino_output_f32 (c = cout);
+ *                           all_aligned16: every such pointer of the launch is 16-byte aligned.  Sizes the launch refuses
+ *                           return its FMGAN_EINVAL.
  */
+int fmgan_wino_select(int output, int batch, int c, int h, int w, int all_aligned16);
 int fmgan_wino_weight_f32(const float *wt, float *u, int cin, int cout, void *stream);
 int fmgan_wino_input_f32(const float *x, const float *style, float *v, int batch, int c, int h, int w, void *stream);
 int fmgan_wino_output_f32(const float *m, const float *demod, const float *noise, const float *noise_weight,
@@ -526,13 +535,15 @@ int fmgan_modconv_weight_prep_f32(const float *weight, float *wt, int cout, int 
  *              [block_begin_k, block_begin_k + fmgan_weight_refresh_blocks(entry k)) ); total_blocks = their sum.
  *   kind 0: dst[k] = src[k] * scale, k < n
  *   kind 1: dst = wt[i][tap][o] = scale * src[o][i][tap] (layout kind 0 of fmgan_modconv_weight_prep_f32), and, if
- *           dst2 != NULL, dst2 = wsq[o][i] = sum_tap src[o][i][tap]^2 (fmgan_modconv_wsq_f32); ktaps <= 9.
+ *           dst2 != NULL, dst2 = wsq[o][i] = sum_tap src[o][i][tap]^2 (fmgan_modconv_wsq_f32); ktaps <= 9.  If
+ *           dst3 != NULL (ktaps == 9 only), dst3 = U [16, cout, cin], the Winograd weight fmgan_wino_weight_f32 makes of wt.
  * Bit-identical to the separate kernels (same operations in the same order).
  */
 typedef struct fmgan_refresh_entry {
   const void *src;
   void *dst;
   void *dst2;
+  void *dst3;
   long long n;            /* kind 0: element count */
   int kind, cout, cin, ktaps;
   float scale;

@@ -334,6 +334,9 @@ def convolutions(d):
     host('modconv2d_tiles')
     host('modconv_wgrad_select', 1, 48, 200, 9, 16, 0)
     host('modconv_wgrad_select', 2, 64, 64, 16, 16, 1, aligned16=False)
+    host('wino_select', 'input', 8, 512, 16, 16)
+    host('wino_select', 'output', 8, 512, 16, 16)
+    host('wino_select', 'output', 8, 256, 128, 128)
 
 
 def live_weights(d):
